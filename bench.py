@@ -29,6 +29,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
                  the counter widths real assemblies take, first (cold) step included
   cpu_baseline - the reference-shaped Python oracle timed on one host core on a bounded sample
                  (+ cpu_baseline_numpy, cpu_baseline_c: the vectorised and the compiled multi-thread restatements)
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's emitted rows) as DIR/<array>.npy, so that two builds can
+be compared output for output on the same seeded workload (dump_outputs).
 """
 import argparse
 import json
@@ -42,6 +45,9 @@ if ROOT not in sys.path:
 
 KMIN, KMAX, W, INC = 1, 8, 5000, 1000
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_COLUMNS = ("seq_index", "start", "stop", "status", "kld", "gc")     # the arrays of the ScanResult a step returns
+DUMP_ROWS = 1 << 20            # --dump-outputs: 7 float64 arrays of at most 2^20 rows = 58.7 MB, under the 64 MB bound
+DUMP_SEED = 0xD0
 
 
 def host_cpu():
@@ -212,6 +218,23 @@ def csrc_hash():
     return h.hexdigest()
 
 
+def dump_outputs(path, res):
+    """--dump-outputs: the rows of the last timed step's ScanResult that the reference emits (`kept`; the windows it drops
+    carry NaN scores and are no output) as <path>/<array>.npy in float64 (exact: the integer columns stay below 2^53),
+    beside candidate.npy, the candidate index of every row written.  More than DUMP_ROWS rows (the C5 shape has 3.08 M) are
+    written as a fixed, seeded sample of DUMP_ROWS of them in candidate order.  Call it before the engine scans again: res's
+    arrays are views of its page-locked buffers."""
+    import numpy as np
+    kept = np.nonzero(res.kept)[0]
+    if len(kept) > DUMP_ROWS:
+        kept = kept[np.sort(np.random.default_rng(DUMP_SEED).choice(len(kept), DUMP_ROWS, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "candidate.npy"), kept.astype(np.float64))
+    for name in DUMP_COLUMNS:
+        np.save(os.path.join(path, name + ".npy"), getattr(res, name)[kept].astype(np.float64))
+    return {"dir": path, "candidate_windows": len(res), "rows_written": len(kept)}
+
+
 def timed_steps(step, fence, warmup, steps):
     """(seconds per step, last result, kernel times) - barrier + synchronize on both sides, as the headline loop."""
     for _ in range(warmup):
@@ -350,7 +373,11 @@ def main(argv=None):
     ap.add_argument("--no-extra", action="store_true", help="skip the cold / strong / realistic blocks (profiling runs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only (gloo, no GPU): proves the N-rank launch path; rank 0 prints {dry_run, world}")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows the last timed step emitted (rank 0) as DIR/<array>.npy, float64, at most 64 MB")
     opts = ap.parse_args(argv)
+    if opts.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if opts.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(opts, argv))
@@ -427,6 +454,7 @@ def main(argv=None):
     fence()
     elapsed = time.perf_counter() - t0
     rows = int(res.kept.sum())                              # (every step emits the same rows: counted once, outside the timed region)
+    dumped = dump_outputs(opts.dump_outputs, res) if opts.dump_outputs and rank == 0 else None
     if dist is not None:
         t = torch.tensor([elapsed, float(rows), float(total_bases), float(n_cand)], dtype=torch.float64, device=red_dev)
         tmax = t.clone()
@@ -536,6 +564,7 @@ def main(argv=None):
             "binding": binding,
             "allreduce_path": getattr(eng, "allreduce_path", None) if world > 1 else "none (one rank: no collective)",
             **({"rehearsal_on_one_gpu": True} if rehearsal else {}),
+            **({"dump_outputs": dumped} if dumped else {}),
             "inclusive": inclusive,
             "cold": cold,
             "shard": shard,
