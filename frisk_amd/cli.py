@@ -6,7 +6,8 @@ caches, GFF3) and the same row echo on stdout.  Phase A and phase B run through 
 (frisk_amd.hotpath); thresholds, merging and GFF3 writing are host numpy (frisk_amd.postprocess).
 
 --hmmKLD runs frisk_amd.hmm (own 2-state Gaussian HMM; hmmlearn is absent and seeds randomly - parity unpinned).
-Out of scope here: --runProjection/--cluster (sklearn analysis on a few hundred rows),
+--runProjection PCA with --cluster DBSCAN / KMEANS runs frisk_amd.projection on the GPU and writes the cluster-labelled GFF3.
+Out of scope here: the other projections (t-SNE, IncrementalPCA, NMF, MDS) and SPECTRAL clustering,
 --graphics (seaborn/matplotlib), --gffIn intersections (bedtools).
 Those options are accepted, as in the reference, and reported as unavailable if used.
 
@@ -66,7 +67,7 @@ def build_parser():
     p.add_argument("--peakCRI", type=float, default=1.0)
     p.add_argument("--minPI", type=float, default=1.0)
     p.add_argument("--maxSI", type=float, default=1.0)
-    # projection / clustering (accepted, not available in this build)
+    # projection / clustering (PCA, DBSCAN and KMEANS built; the other methods accepted, not available in this build)
     p.add_argument("--runProjection", default=None, choices=[None, "PCA", "PY-TSNE", "SKL-TSNE", "IncrementalPCA", "NMF", "MDS"])
     p.add_argument("--projectionDims", type=int, default=2)
     p.add_argument("--dimReduce", default="windows", choices=["features", "windows"])
@@ -87,6 +88,22 @@ def build_parser():
     p.add_argument("--updateInc", type=int, default=500)
     p.add_argument("--findSelf", action="store_true", default=False, help="report windows BELOW the threshold instead")
     return p
+
+
+PROJECTIONS = ("PCA",)                  # --runProjection methods built here (frisk_amd.projection)
+CLUSTERINGS = ("DBSCAN", "KMEANS")      # --cluster methods built here
+
+
+def unavailable(args):
+    """(option, reason) of every given option this build accepts but does not run.  --cluster runs only as DBSCAN or KMEANS
+    after --runProjection PCA (the reference clusters the projection, L1635-1655)."""
+    clustering = args.runProjection in PROJECTIONS and args.cluster in CLUSTERINGS
+    out = []
+    for opt, why in (("cluster", "sklearn clustering is out of scope"),
+                     ("graphics", "plotting is out of scope"), ("gffIn", "bedtools intersections are out of scope")):
+        if getattr(args, opt) and not (opt == "cluster" and clustering):
+            out.append((opt, why))
+    return out
 
 
 def mainArgs(argv=None):
@@ -203,6 +220,27 @@ class _Clock:
             sys.stderr.write(json.dumps({"frisk_timing": dict(self.parts), "total_s": total}) + "\n")
 
 
+def _project(args, anomCounts, device, clock):
+    """--runProjection PCA on the anomalies' k-mer proportions (L1612-1613), then --cluster DBSCAN / KMEANS on the projection
+    (L1635-1655).  Returns the cluster labels (None without a clustering this build runs)."""
+    from . import projection as P
+    res = P.pca(anomCounts, args.projectionDims, device=device)
+    log.info("PCA of %s x %s k-mer proportions: explained variance %s; covariance %.1f ms, eigh %.1f ms, transform %.1f ms",
+             anomCounts.shape[0], anomCounts.shape[1], res.explained_variance.tolist(), res.timings["cov_ms"],
+             res.timings["eigh_ms"], res.timings["transform_ms"])
+    clock.lap("PCA")
+    y_pred = None
+    if args.cluster == "DBSCAN":
+        y_pred = P.dbscan(res.Y, args.epsDBSCAN, device=device)
+    elif args.cluster == "KMEANS":
+        # the reference passes random_state=None (not reproducible); --seed, 0 when not given, seeds k-means++ here
+        y_pred = P.kmeans(res.Y, args.kClusters, seed=int(args.seed) if args.seed is not None else 0, device=device).labels
+    if y_pred is not None:
+        log.info("%s: %s clusters, %s unclassified", args.cluster, len(set(y_pred.tolist()) - {-1}), int(np.sum(y_pred == -1)))
+        clock.lap(args.cluster)
+    return y_pred
+
+
 def _main(argv=None):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(funcName)s - %(message)s")
     args = mainArgs(argv)
@@ -237,10 +275,10 @@ def _main(argv=None):
         os.makedirs(os.path.abspath(args.tempDir))
     if sharded:
         dist.barrier()      # tempDir exists, and every rank sees the same cache files, before anyone looks for them
-    for opt, why in (("cluster", "sklearn clustering is out of scope"),
-                     ("graphics", "plotting is out of scope"), ("gffIn", "bedtools intersections are out of scope")):
-        if getattr(args, opt):
-            log.warning("--%s is not available in this build: %s", opt, why)
+    projection = args.runProjection in PROJECTIONS            # a projection this build runs
+    clustering = projection and args.cluster in CLUSTERINGS
+    for opt, why in unavailable(args):
+        log.warning("--%s is not available in this build: %s", opt, why)
 
     from .hotpath import HotPath
     from . import distributed as D
@@ -419,14 +457,23 @@ def _main(argv=None):
                     pickle.dump(anomLabels, fh, protocol=2)
                 with open(os.path.join(args.tempDir, "anomCounts"), "wb") as fh:
                     pickle.dump(anomCounts, fh, protocol=2)
-            log.info("Symmetric k-mer proportions of %s anomalous windows computed; the %s projection is not built here.",
-                     len(labelled), args.runProjection)
-        anomalies, _sel = pp.thresholdKLD(table, threshold, args, merge=True)
+            if projection:
+                y_pred = _project(args, anomCounts, local_rank, clock)
+            else:
+                log.info("Symmetric k-mer proportions of %s anomalous windows computed; the %s projection is not built here.",
+                         len(labelled), args.runProjection)
+        if projection:
+            anomalies = feats           # L1672-1675: the projection's own anomaly set (single windows under --dimReduce windows)
+        else:
+            anomalies, _sel = pp.thresholdKLD(table, threshold, args, merge=True)
         log.info("Detected %s features above KLD threshold.", len(anomalies))
         if args.gffOutfile:
             with open(os.path.join(args.tempDir, args.gffOutfile), "w") as fh:
                 for line in pp.anomaly2GFF(anomalies, args):
                     fh.write(line)
+            if clustering:                                                  # L1688-1697
+                with open(os.path.join(args.tempDir, pp.clusterGffName(args)), "w") as fh:
+                    fh.writelines(pp.anomClust2gff(pp.cluster_rows(anomLabels, y_pred)))
         if rip:
             feats = pp.thresholdRIP(table, args)
             if feats:

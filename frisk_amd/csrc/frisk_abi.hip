@@ -29,6 +29,7 @@
 #include "fasta_pack2.h"
 #include "seq_pack2.h"
 #include "hmm_host.h"
+#include "proj_kernels.h"
 
 #ifndef FRISK_K7_WPS
 #define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
@@ -2057,5 +2058,50 @@ int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, co
 }
 
 int64_t frisk_last_scan_stat(const frisk_ctx* c, int which) { return (c && which >= 0 && which < 5) ? c->scan_stat[which] : -1; }
+
+// ---- projection and clustering (proj_kernels.h): context-free, host arrays in and out, device memory freed on every return
+namespace {
+bool all_finite(const double* x, int64_t count) {
+    for (int64_t e = 0; e < count; ++e) if (!std::isfinite(x[e])) return false;
+    return true;
+}
+}  // namespace
+
+int frisk_proj_cov(int device, const double* X, int64_t n, int64_t f, double* mean_out, double* cov_out) {
+    if (!X || !mean_out || !cov_out || n < 1 || f < 1 || !all_finite(X, n * f)) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    return frisk_proj::cov(X, n, f, mean_out, cov_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_proj_transform(int device, const double* X, const double* mean, const double* V, int64_t n, int64_t f, int32_t d,
+                         double* Y_out) {
+    if (!X || !mean || !V || !Y_out || n < 1 || f < 1 || d < 1 || d > f || !all_finite(X, n * f) || !all_finite(mean, f) ||
+        !all_finite(V, f * d))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    return frisk_proj::transform(X, mean, V, n, f, d, Y_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_dbscan(int device, const double* Y, int64_t n, int32_t d, double eps, int32_t min_samples, int32_t* labels_out) {
+    if (!Y || !labels_out || n < 1 || n > INT32_MAX || d < 1 || d > frisk_proj::MAX_DIMS || !(eps > 0.0) || !std::isfinite(eps) ||
+        min_samples < 1 || !all_finite(Y, n * d))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    return frisk_proj::dbscan(Y, n, d, eps, min_samples, labels_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_kmeans(int device, const double* Y, int64_t n, int32_t d, int32_t k, const double* init_centers, int32_t max_iter,
+                 double tol, int32_t* labels_out, double* centers_out, double* inertia_out, int32_t* n_iter_out) {
+    if (!Y || !init_centers || !labels_out || !centers_out || n < 1 || n > INT32_MAX || d < 1 || d > frisk_proj::MAX_DIMS ||
+        k < 1 || k > n || max_iter < 1 || !(tol >= 0.0) || !all_finite(Y, n * d) || !all_finite(init_centers, int64_t(k) * d))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    return frisk_proj::kmeans(Y, n, d, k, init_centers, max_iter, tol, labels_out, centers_out, inertia_out, n_iter_out)
+               ? FRISK_E_HIP : FRISK_OK;
+}
 
 }  // extern "C"

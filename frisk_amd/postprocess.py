@@ -336,3 +336,39 @@ def RIP2GFF(features, version=FRISK_VERSION):
         if n == 1:
             yield "##gff-version 3\n"
         yield "\t".join([str(f[0]), "frisk_" + version, "RIP", str(f[1]), str(f[2]), ".", "+", ".", ";".join(attrs)]) + "\n"
+
+
+# ------------------------------------------------------------------------------------------------ cluster-labelled GFF3
+def cluster_rows(labels, y_pred):
+    """What cluster2df (L598-645) keeps for the writer, one (chrom, start, end, class label) per anomaly in anomaly order.
+    Class names follow the position of each label among the sorted unique labels: Class_<position>, and -1 (DBSCAN noise) is
+    Unclassified - so with noise present the first real cluster is Class_1.  chrom, start and end are the fields of the
+    anomaly's label text chrom:start:end."""
+    y_pred = np.asarray(y_pred)
+    uniq = np.unique(y_pred).tolist()
+    names = {u: ("Unclassified" if u == -1 else "Class_" + str(pos)) for pos, u in enumerate(uniq)}
+    out = []
+    for lab, y in zip(labels, y_pred.tolist()):
+        text = str(lab[0] if isinstance(lab, (list, tuple, np.ndarray)) else lab)
+        chrom, start, end = text.split(":")[:3]
+        out.append((chrom, start, end, names[y]))
+    return out
+
+
+def anomClust2gff(rows, version=FRISK_VERSION):
+    """GFF3 lines of cluster-labelled anomalies (L569-575): the class name as the feature type, IDs Clustered_Anom_<n>
+    zero-padded to the width of the row count; the header is written even when there are no rows."""
+    width = len(str(len(rows)))
+    yield "##gff-version 3\n"
+    for n, (chrom, start, end, cls) in enumerate(rows, 1):
+        yield "\t".join([chrom, "frisk_" + version, cls, start, end, ".", "+", ".", "ID=Clustered_Anom_" + str(n).zfill(width)]) + "\n"
+
+
+def clusterGffName(args):
+    """File name of the cluster-labelled GFF3 (L1689-1694): the method tag carries k_<kClusters> whenever kClusters is
+    non-zero, whatever the clustering method."""
+    if args.kClusters:
+        tag = "_".join((args.runProjection, args.cluster, "k", str(args.kClusters), "cluster_labeled", args.dimReduce))
+    else:
+        tag = "_".join((args.runProjection, args.cluster, "cluster_labeled", args.dimReduce))
+    return tag + "_" + args.gffOutfile

@@ -1,5 +1,6 @@
-"""Symmetric k-mer proportions of anomalous windows - the input of the reference's projection/clustering step
-(SURVEY.md section 8, row f4).  The projection itself (sklearn PCA/t-SNE/..., DBSCAN/k-means) is out of scope.
+"""Symmetric k-mer proportions of anomalous windows, and their projection and clustering:
+PCA, DBSCAN and k-means as the reference runs them through sklearn (L1597-1665), on the GPU (frisk_proj_* / frisk_dbscan /
+frisk_kmeans, csrc/proj_kernels.h).  t-SNE, IncrementalPCA, NMF, MDS and spectral clustering are not built.
 
 Reference (frisk/__init__.py): computeKmers(sym=True, pcaMode=True) L280-367 counts every valid word AND its
 reverse complement for orders pcaMin..pcaMax; scrubMirrors L797-811 keeps one key of each reverse-complement pair
@@ -8,8 +9,12 @@ order's kept counts into proportions of their sum and concatenates the orders (l
 The counting runs on the GPU (per-window forward counts from frisk_scan's count dump); folding and proportions are
 host numpy.
 """
+import ctypes as C
+import time
+
 import numpy as np
 
+from . import _ffi
 from .engine import Engine, table_offset
 from .hotpath import kmerString
 
@@ -66,3 +71,144 @@ def symmetricCounts(labelled_seqs, pcaMin, pcaMax, device=0):
         rows.append(proportions_from_forward(res.counts[hit[0]], pcaMin, pcaMax))
     labels = np.array([[lab] for lab, _ in labelled_seqs])
     return labels, np.vstack(rows)
+
+
+# ------------------------------------------------------------------------------------------------ projection / clustering
+DBSCAN_MIN_SAMPLES = 50         # DBSCAN(eps=args.epsDBSCAN, min_samples=50) (L1639)
+KMEANS_N_INIT, KMEANS_MAX_ITER, KMEANS_TOL = 20, 500, 1e-4      # KMeans(n_init=20, max_iter=500, tol=0.0001) (L1647-1649)
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _call(name, *args):
+    rc = getattr(_ffi.lib(), name)(*args)
+    if rc != _ffi.OK:
+        raise _ffi.FriskHipError(rc, "%s rejected its input" % name if rc == _ffi.E_ARG else "%s failed" % name)
+
+
+def _f64(a, ndim):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != ndim:
+        raise ValueError("expected a %d-d array, got shape %s" % (ndim, a.shape))
+    return a
+
+
+def cov(X, device=0):
+    """(column means, covariance / (n - 1)) of X on the GPU (two-pass centring, FP64)."""
+    X = _f64(X, 2)
+    n, f = X.shape
+    mean, c = np.empty(f), np.empty((f, f))
+    _call("frisk_proj_cov", device, _ptr(X), n, f, _ptr(mean), _ptr(c))
+    return mean, c
+
+
+def transform(X, mean, V, device=0):
+    """(X - mean) V on the GPU; V: f x d, one component per column."""
+    X, mean, V = _f64(X, 2), _f64(mean, 1), _f64(V, 2)
+    n, f = X.shape
+    Y = np.empty((n, V.shape[1]))
+    _call("frisk_proj_transform", device, _ptr(X), _ptr(mean), _ptr(V), n, f, V.shape[1], _ptr(Y))
+    return Y
+
+
+class PCAResult:
+    """Y (n x dims), components (dims x f, rows), explained_variance (dims), mean (f); timings in ms (cov / eigh / transform)."""
+
+    def __init__(self, Y, components, explained_variance, mean, timings):
+        self.Y, self.components, self.explained_variance, self.mean, self.timings = Y, components, explained_variance, mean, timings
+
+
+def pca(X, dims, device=0):
+    """sklearn's PCA(n_components=dims).fit(X).transform(X) (L1612-1613): covariance on the GPU, its eigendecomposition (one f x f
+    torch.linalg.eigh on the same device: on the host, numpy.linalg.eigh took ~2 s at f = 2 772, ten times the covariance - see
+    DESIGN.md), the top `dims` components in descending eigenvalue order with sklearn's sign rule (svd_flip(u_based_decision=False):
+    the entry of largest absolute value of each component is positive), transform on the GPU."""
+    import torch
+    X = _f64(X, 2)
+    n, f = X.shape
+    if not 1 <= dims <= min(n, f):
+        raise ValueError("n_components=%d must be between 1 and min(n_samples, n_features)=%d" % (dims, min(n, f)))
+    if n < 2:
+        raise ValueError("PCA needs at least 2 samples")
+    t0 = time.perf_counter()
+    mean, c = cov(X, device)
+    t1 = time.perf_counter()
+    tw, tv = torch.linalg.eigh(torch.from_numpy(c).to(torch.device("cuda", device)))
+    w, v = tw.cpu().numpy(), tv.cpu().numpy()
+    t2 = time.perf_counter()
+    order = np.argsort(w, kind="stable")[::-1][:dims]
+    comps = v[:, order].T.copy()
+    big = np.argmax(np.abs(comps), axis=1)
+    comps *= np.sign(comps[np.arange(dims), big])[:, None]
+    Y = transform(X, mean, comps.T, device)
+    t3 = time.perf_counter()
+    return PCAResult(Y, comps, w[order].copy(), mean, {"cov_ms": 1e3 * (t1 - t0), "eigh_ms": 1e3 * (t2 - t1),
+                                                       "transform_ms": 1e3 * (t3 - t2)})
+
+
+def dbscan(Y, eps, min_samples=DBSCAN_MIN_SAMPLES, device=0):
+    """sklearn's DBSCAN(eps, min_samples).fit(Y).labels_ (Euclidean): int32 labels, -1 = noise."""
+    Y = _f64(Y, 2)
+    labels = np.empty(Y.shape[0], dtype=np.int32)
+    _call("frisk_dbscan", device, _ptr(Y), Y.shape[0], Y.shape[1], float(eps), int(min_samples), _ptr(labels))
+    return labels
+
+
+def kmeans_plusplus(Y, k, rs):
+    """Greedy k-means++ seeding as sklearn's _kmeans_plusplus (2 + floor(ln k) local trials), drawing from the RandomState rs."""
+    n = Y.shape[0]
+    trials = 2 + int(np.log(k))
+    sq = np.einsum("ij,ij->i", Y, Y)
+
+    def dist2(P):
+        d = sq[None, :] - 2.0 * (P @ Y.T) + np.einsum("ij,ij->i", P, P)[:, None]
+        return np.maximum(d, 0.0)
+    first = rs.choice(n, p=np.full(n, 1.0 / n))
+    idx = [int(first)]
+    closest = dist2(Y[[first]])[0]
+    pot = closest.sum()
+    for _ in range(1, k):
+        r = rs.uniform(size=trials) * pot
+        cand = np.minimum(np.searchsorted(np.cumsum(closest), r), n - 1)
+        dc = np.minimum(closest, dist2(Y[cand]))
+        pots = dc.sum(axis=1)
+        b = int(np.argmin(pots))
+        pot, closest = pots[b], dc[b]
+        idx.append(int(cand[b]))
+    return Y[idx].copy(), np.array(idx)
+
+
+class KMeansResult:
+    def __init__(self, labels, centers, inertia, n_iter):
+        self.labels, self.centers, self.inertia, self.n_iter = labels, centers, inertia, n_iter
+
+
+def kmeans(Y, k, seed=0, n_init=KMEANS_N_INIT, max_iter=KMEANS_MAX_ITER, tol=KMEANS_TOL, device=0):
+    """sklearn's KMeans(n_clusters=k, init='k-means++', n_init, max_iter, tol).fit(Y) with random_state=seed: n_init Lloyd runs
+    on the GPU from k-means++ seeds drawn in turn from one RandomState(seed); the run of lowest inertia is kept (the earliest on
+    a tie).  Cluster ids are renumbered by first occurrence in row order."""
+    Y = _f64(Y, 2)
+    n, d = Y.shape
+    if not 1 <= k <= n:
+        raise ValueError("n_clusters=%d must be between 1 and n_samples=%d" % (k, n))
+    rs = np.random.RandomState(seed)
+    tol_abs = float(np.mean(np.var(Y, axis=0))) * tol          # sklearn's _tolerance
+    best = None
+    for _ in range(n_init):
+        init, _idx = kmeans_plusplus(Y, k, rs)
+        labels, centers = np.empty(n, dtype=np.int32), np.empty((k, d))
+        inertia, iters = C.c_double(), C.c_int32()
+        _call("frisk_kmeans", device, _ptr(Y), n, d, k, _ptr(np.ascontiguousarray(init)), max_iter, tol_abs, _ptr(labels),
+              _ptr(centers), C.byref(inertia), C.byref(iters))
+        if best is None or inertia.value < best.inertia:
+            best = KMeansResult(labels, centers, inertia.value, iters.value)
+    _, first = np.unique(best.labels, return_index=True)
+    order = np.unique(best.labels)[np.argsort(first, kind="stable")]
+    remap = np.empty(k, dtype=np.int32)
+    remap[:] = -1
+    remap[order] = np.arange(order.size, dtype=np.int32)
+    best.labels = remap[best.labels]
+    best.centers = best.centers[order]
+    return best

@@ -267,6 +267,27 @@ int frisk_hmm_fit(const double* x, int64_t n, int32_t n_iter, double tol, double
 int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, const double* means, const double* covars,
                       const double* startprob, const double* transmat, int8_t* states);
 
+/* Projection and clustering of the anomalous windows' k-mer proportions (the reference's L1597-1697: sklearn PCA, DBSCAN and
+ * KMeans), on `device`, without a context.  Inputs and outputs are host arrays (row-major); every result is bit-identical from
+ * run to run (fixed-order reductions, no floating-point atomics).  Each returns FRISK_OK, FRISK_E_ARG on a bad argument (n < 1,
+ * d > f, eps <= 0 or NaN, k < 1 or k > n, non-finite data, points of more than 64 dimensions for the two clusterings)
+ * or FRISK_E_HIP.
+ * frisk_proj_cov: mean_out[f] = column means of X[n][f]; cov_out[f][f] = (X - mean)T (X - mean) / (n - 1) (two-pass centring,
+ *   FP64 matrix cores; n = 1 divides by 1).
+ * frisk_proj_transform: Y_out[n][d] = (X - mean) V for V[f][d] (column q = component q).
+ * frisk_dbscan: labels_out[n] of DBSCAN with Euclidean distance (neighbours: sqrt(sum of squares) <= eps, the point itself
+ *   included; core: >= min_samples neighbours); clusters numbered 0, 1, ... in increasing order of their smallest core index,
+ *   a border point in the first cluster that reaches it, noise -1 - sklearn's dbscan_inner labelling.
+ * frisk_kmeans: Lloyd's algorithm from init_centers[k][d] until the labels stop changing, the squared centre shift is <= tol, or
+ *   max_iter steps; then one more assignment to the final centres.  labels_out[n] (nearest centre, lowest index on a tie),
+ *   centers_out[k][d], the inertia of that assignment and the steps run (both nullable).  An empty cluster keeps its centre. */
+int frisk_proj_cov(int device, const double* X, int64_t n, int64_t f, double* mean_out, double* cov_out);
+int frisk_proj_transform(int device, const double* X, const double* mean, const double* V, int64_t n, int64_t f, int32_t d,
+                         double* Y_out);
+int frisk_dbscan(int device, const double* Y, int64_t n, int32_t d, double eps, int32_t min_samples, int32_t* labels_out);
+int frisk_kmeans(int device, const double* Y, int64_t n, int32_t d, int32_t k, const double* init_centers, int32_t max_iter,
+                 double tol, int32_t* labels_out, double* centers_out, double* inertia_out, int32_t* n_iter_out);
+
 /* Page-locked host memory for result buffers: D2H copies into it are asynchronous and run at PCIe rate
  * (pageable buffers work too, at a fraction of it).  Free with frisk_host_free before frisk_destroy. */
 void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);

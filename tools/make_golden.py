@@ -101,15 +101,17 @@ class PyBedToolsStub:
     BedTool = BedToolStub
 
 
-def load_reference_functions():
+def load_reference_functions(extra=()):
+    """The functions of HOT_FUNCS (plus `extra`) from the reference module, run through lib2to3, in one namespace."""
+    names = list(HOT_FUNCS) + list(extra)
     scratch = tempfile.mkdtemp(prefix="frisk_oracle_")
     dst = os.path.join(scratch, "frisk_py2.py")
     shutil.copy(REF_SRC, dst)
     subprocess.run([sys.executable, "-m", "lib2to3", "-w", "-n", dst], check=True,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     tree = ast.parse(open(dst).read())
-    keep = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in HOT_FUNCS]
-    assert sorted(n.name for n in keep) == sorted(HOT_FUNCS), [n.name for n in keep]
+    keep = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in names]
+    assert sorted(n.name for n in keep) == sorted(names), [n.name for n in keep]
     mod = ast.Module(body=keep, type_ignores=[])
 
     class _NP:  # calcRIP uses np.NaN (removed in numpy 2)
