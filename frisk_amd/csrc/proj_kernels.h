@@ -6,7 +6,8 @@
 //   covariance    v_mfma_f64_16x16x4_f64 over fixed row ranges (one per split), partial tiles summed in split order;
 //   transform     one wave per row, lanes over features in stride order, then a fixed xor butterfly;
 //   DBSCAN        integer counts; union-find whose result does not depend on the order of the unions (see dbscan below);
-//   k-means       per-block partials (fixed wave butterfly + waves in order), blocks summed in order by one thread per value.
+//   k-means       per-block partials (fixed wave butterfly + waves in order), blocks summed in order by one thread per value;
+//                 empty clusters take the farthest points by exact comparisons (descending distance, lowest index on a tie).
 // Included from frisk_abi.hip (one translation unit); the C entry points there are thin wrappers of the drivers below.
 #pragma once
 
@@ -248,12 +249,13 @@ __device__ inline double block_sum(double v, double* red) {
     return s;
 }
 
-// One Lloyd step, first half: nearest centre of each point (lowest index on a tie), whether any label changed, and per block
-// part[b][c (d+1) + q] = sum of coordinate q (q = d: the count) of the block's points of centre c, part[b][k (d+1)] = their
-// squared distances.
+// One Lloyd step, first half: nearest centre of each point (lowest index on a tie), whether any label changed, dist[i] = the
+// squared distance of point i to that centre, and per block part[b][c (d+1) + q] = sum of coordinate q (q = d: the count) of the
+// block's points of centre c, part[b][k (d+1)] = their squared distances.
 template <int MAXD>
 __global__ __launch_bounds__(256) void km_assign(const double* __restrict__ Y, int64_t n, int d, int k, const double* __restrict__ C,
-                                                 int32_t* __restrict__ lab, int32_t* __restrict__ changed, double* __restrict__ part) {
+                                                 int32_t* __restrict__ lab, int32_t* __restrict__ changed, double* __restrict__ dist,
+                                                 double* __restrict__ part) {
     __shared__ double red[4];
     const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
     const bool valid = i < n;
@@ -275,6 +277,7 @@ __global__ __launch_bounds__(256) void km_assign(const double* __restrict__ Y, i
             if (c == 0 || s < bd) { bd = s; best = c; }
         }
         if (lab[i] != best) { lab[i] = best; *changed = 1; }
+        dist[i] = bd;
     }
     const int stride = k * (d + 1) + 1;
     double* out = part + int64_t(blockIdx.x) * stride;
@@ -292,19 +295,105 @@ __global__ __launch_bounds__(256) void km_assign(const double* __restrict__ Y, i
     if (threadIdx.x == 0) out[k * (d + 1)] = s;
 }
 
-// Second half (one block): block partials summed in block order; Cn = the new centres (an empty cluster keeps its centre);
-// res[0] = sum over centres of |Cn_c - C_c|^2 (sklearn's center_shift_tot), res[1] = the inertia of the assignment.
-__global__ __launch_bounds__(256) void km_update(const double* __restrict__ part, int64_t nblocks, int d, int k,
-                                                 const double* __restrict__ C, double* __restrict__ Cn, double* __restrict__ res) {
+// (distance, index) of the farthest point strictly after (pd, pi) in the order "descending distance, lowest index on a tie"
+// (first = true: of all points), over the block: each thread scans its stride, then a wave butterfly and the waves in order.
+// Exact comparisons only, so the result does not depend on the reduction order.
+__device__ inline void km_farthest(const double* __restrict__ dist, int64_t n, bool first, double pd, int64_t pi, double* rd,
+                                   int64_t* ri, double& od, int64_t& oi) {
+    double bd = -1.0;
+    int64_t bi = -1;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const double v = dist[i];
+        if (!first && !(v < pd || (v == pd && i > pi))) continue;
+        if (v > bd) { bd = v; bi = i; }           // i increases along the stride: the first of equal distances is kept
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double od_ = __shfl_xor(bd, m, 64);
+        const int64_t oi_ = __shfl_xor(bi, m, 64);
+        if (oi_ >= 0 && (bi < 0 || od_ > bd || (od_ == bd && oi_ < bi))) { bd = od_; bi = oi_; }
+    }
+    if ((threadIdx.x & 63) == 0) { rd[threadIdx.x >> 6] = bd; ri[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    od = -1.0; oi = -1;
+    for (int w = 0; w < 4; ++w)
+        if (ri[w] >= 0 && (oi < 0 || rd[w] > od || (rd[w] == od && ri[w] < oi))) { od = rd[w]; oi = ri[w]; }
+    __syncthreads();
+}
+
+// Second half (one block), sklearn's Lloyd step (lloyd_iter_chunked_dense: _relocate_empty_clusters_dense, then
+// _average_centers).  S[c][q], W[c] = the block partials of coordinate sums and counts, summed in block order.  When clusters are
+// empty, and the largest of the point distances dist[] is not 0, the empty clusters in increasing id take the farthest points in
+// descending distance order (lowest index on a tie): each such point's coordinates and weight move out of its cluster's sums
+// into the empty one's.  Then Cn[c] = S[c] / W[c]; a cluster still empty is placed where sklearn places it, on the cluster a of
+// largest weight (the first of equal weights): S[a] / W[a] if a < c, else S[a] (sklearn averages in id order and copies
+// whichever it finds).  res[0] = sum over centres of |Cn_c - C_c|^2 (sklearn's center_shift_tot), res[1] = the inertia of the
+// assignment.  Scratch: S[k d], W[k], emp[k] (int32), far[k] (int64).
+__global__ __launch_bounds__(256) void km_update(const double* __restrict__ part, int64_t nblocks, const double* __restrict__ Y,
+                                                 int64_t n, int d, int k, const int32_t* __restrict__ lab,
+                                                 const double* __restrict__ dist, const double* __restrict__ C, double* __restrict__ Cn,
+                                                 double* __restrict__ S, double* __restrict__ W, int32_t* __restrict__ emp,
+                                                 int64_t* __restrict__ far, double* __restrict__ res) {
+    __shared__ double rd[4];
+    __shared__ int64_t ri[4];
+    __shared__ int n_empty_s, argmax_s;
     const int stride = k * (d + 1) + 1;
     for (int e = threadIdx.x; e < k * d; e += 256) {
         const int c = e / d, q = e % d;
-        double s = 0.0, w = 0.0;
-        for (int64_t b = 0; b < nblocks; ++b) {
-            s += part[b * stride + c * (d + 1) + q];
-            w += part[b * stride + c * (d + 1) + d];
+        double s = 0.0;
+        for (int64_t b = 0; b < nblocks; ++b) s += part[b * stride + c * (d + 1) + q];
+        S[e] = s;
+    }
+    for (int c = threadIdx.x; c < k; c += 256) {
+        double w = 0.0;
+        for (int64_t b = 0; b < nblocks; ++b) w += part[b * stride + c * (d + 1) + d];
+        W[c] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int m = 0;
+        for (int c = 0; c < k; ++c)
+            if (W[c] == 0.0) emp[m++] = c;
+        n_empty_s = m;
+    }
+    __syncthreads();
+    const int n_empty = n_empty_s;
+    if (n_empty > 0) {
+        double pd = 0.0;
+        int64_t pi = -1;
+        bool relocate = true;
+        for (int t = 0; t < n_empty; ++t) {
+            km_farthest(dist, n, t == 0, pd, pi, rd, ri, pd, pi);
+            if (t == 0 && pd == 0.0) { relocate = false; break; }     // duplicates only: relocating is pointless (as sklearn)
+            if (threadIdx.x == 0) far[t] = pi;
         }
-        Cn[e] = w > 0.0 ? s / w : C[e];
+        __syncthreads();
+        if (relocate && threadIdx.x == 0) {
+            for (int t = 0; t < n_empty; ++t) {
+                const int nc = emp[t];
+                const int64_t i = far[t];
+                const int oc = lab[i];
+                for (int q = 0; q < d; ++q) {
+                    S[oc * d + q] -= Y[i * d + q];
+                    S[nc * d + q] = Y[i * d + q];
+                }
+                W[nc] = 1.0;
+                W[oc] -= 1.0;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        int a = 0;
+        for (int c = 1; c < k; ++c)
+            if (W[c] > W[a]) a = c;
+        argmax_s = a;
+    }
+    __syncthreads();
+    const int a = argmax_s;
+    for (int e = threadIdx.x; e < k * d; e += 256) {
+        const int c = e / d, q = e % d;
+        Cn[e] = W[c] > 0.0 ? S[e] / W[c] : (a < c ? S[a * d + q] / W[a] : S[a * d + q]);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -478,15 +567,21 @@ inline int kmeans(const double* Y, int64_t n, int d, int k, const double* init_c
     double* res = mem.get<double>(2);
     int32_t* lab = mem.get<int32_t>(size_t(n));
     int32_t* changed = mem.get<int32_t>(1);
-    if (!dY || !C || !Cn || !part || !res || !lab || !changed) return -2;
+    double* dist = mem.get<double>(size_t(n));
+    double* S = mem.get<double>(size_t(k) * size_t(d));
+    double* W = mem.get<double>(size_t(k));
+    int32_t* emp = mem.get<int32_t>(size_t(k));
+    int64_t* far = mem.get<int64_t>(size_t(k));
+    if (!dY || !C || !Cn || !part || !res || !lab || !changed || !dist || !S || !W || !emp || !far) return -2;
     PROJ_CHECK(hipMemcpy(dY, Y, size_t(n) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
     PROJ_CHECK(hipMemcpy(C, init_centers, size_t(k) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
     PROJ_CHECK(hipMemset(lab, 0xff, size_t(n) * sizeof(int32_t)));          // -1: every label changes in the first step
     auto step = [&](double* from, double* to) {
-        if (d <= 4) hipLaunchKernelGGL(km_assign<4>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, part);
-        else if (d <= 16) hipLaunchKernelGGL(km_assign<16>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, part);
-        else hipLaunchKernelGGL(km_assign<MAX_DIMS>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, part);
-        hipLaunchKernelGGL(km_update, dim3(1), dim3(256), 0, 0, part, nblocks, d, k, from, to, res);
+        if (d <= 4) hipLaunchKernelGGL(km_assign<4>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, dist, part);
+        else if (d <= 16)
+            hipLaunchKernelGGL(km_assign<16>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, dist, part);
+        else hipLaunchKernelGGL(km_assign<MAX_DIMS>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, dist, part);
+        hipLaunchKernelGGL(km_update, dim3(1), dim3(256), 0, 0, part, nblocks, dY, n, d, k, lab, dist, from, to, S, W, emp, far, res);
     };
     int32_t it = 0;
     double h[2];

@@ -280,7 +280,10 @@ int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, co
  *   a border point in the first cluster that reaches it, noise -1 - sklearn's dbscan_inner labelling.
  * frisk_kmeans: Lloyd's algorithm from init_centers[k][d] until the labels stop changing, the squared centre shift is <= tol, or
  *   max_iter steps; then one more assignment to the final centres.  labels_out[n] (nearest centre, lowest index on a tie),
- *   centers_out[k][d], the inertia of that assignment and the steps run (both nullable).  An empty cluster keeps its centre. */
+ *   centers_out[k][d], the inertia of that assignment and the steps run (both nullable).  Empty clusters follow sklearn's Lloyd
+ *   step: unless every point sits on its centre, they take, in increasing id, the points farthest from their centres (descending
+ *   distance, lowest index on a tie), each moved out of its own cluster; a cluster still empty is placed on the cluster of
+ *   largest weight (its centre if that cluster's id is lower, its coordinate sum otherwise, as sklearn's _average_centers). */
 int frisk_proj_cov(int device, const double* X, int64_t n, int64_t f, double* mean_out, double* cov_out);
 int frisk_proj_transform(int device, const double* X, const double* mean, const double* V, int64_t n, int64_t f, int32_t d,
                          double* Y_out);

@@ -95,3 +95,72 @@ def test_projection_abi_is_declared():
     from frisk_amd import _ffi
     names = {n for n, _, _ in _ffi.SYMBOLS}
     assert {"frisk_proj_cov", "frisk_proj_transform", "frisk_dbscan", "frisk_kmeans"} <= names
+
+
+# ------------------------------------------------------------------------------------------------ the GPU tests' oracles
+@pytest.mark.parametrize("case", sorted(G["kmeans_init"]))
+def test_lloyd_restatement_matches_sklearn_golden(case):
+    """proj_oracles.lloyd, the restatement the GPU k-means tests compare with (sklearn's empty-cluster relocation included),
+    gives sklearn's labels, centres, inertia and n_iter_ on every explicit-init golden."""
+    import proj_oracles as PO
+    g = G["kmeans_init"][case]
+    lab, cen, inertia, it = PO.lloyd(A(g["Y"]), A(g["init"]), g["max_iter"], g["tol"])
+    want = A(g["centers"])
+    assert lab.tolist() == A(g["labels"]).tolist() and it == g["n_iter"]
+    assert np.abs(cen - want).max() <= 1e-12 * max(np.abs(want).max(), 1.0)
+    assert abs(inertia - g["inertia"]) <= 1e-12 * max(g["inertia"], 1.0)
+
+
+def test_relocation_goldens_tell_the_rules_apart():
+    """The relocation goldens end elsewhere under the old rule (an empty cluster keeps its centre)."""
+    import proj_oracles as PO
+    for case in ("empty_one_0", "empty_one_1", "empty_two", "dups_after", "dups_before"):
+        g = G["kmeans_init"][case]
+        Y, C = A(g["Y"]), A(g["init"]).copy()
+        trace = []
+        PO.lloyd(Y, C, g["max_iter"], g["tol"], trace)
+        assert any(t["empty"] for t in trace)
+        old = np.full(len(Y), -1)
+        for _ in range(g["max_iter"]):
+            lab = np.argmin(PO.sq_dist(Y, C), axis=1)
+            Cn = np.array([Y[lab == c].mean(axis=0) if (lab == c).any() else C[c] for c in range(len(C))])
+            shift, C = float(np.sum((Cn - C) ** 2)), Cn
+            if np.array_equal(lab, old) or shift <= g["tol"]:
+                break
+            old = lab
+        lab = np.argmin(PO.sq_dist(Y, C), axis=1)
+        assert lab.tolist() != A(g["labels"]).tolist() or not np.allclose(C, A(g["centers"])), case
+
+
+@pytest.mark.parametrize("group", ["dbscan", "dbscan_edges"])
+def test_bruteforce_dbscan_oracle_matches_sklearn_goldens(group):
+    import proj_oracles as PO
+    for case, g in sorted(G[group].items()):
+        labels, _gap = PO.dbscan_oracle(A(g["Y"]), g["eps"], g.get("min_samples", G["min_samples"]))
+        assert labels.tolist() == A(g["labels"]).tolist(), case
+
+
+def test_covariance_tolerance_rejects_near_misses():
+    """The per-entry bound of proj_oracles.cov_oracle at n = 3 000, F = 2 772 is tight enough to fail an oracle computed with
+    one row dropped, and a 16 x 16 block shifted by one column, in the small-variance order-6 block as well as overall."""
+    import proj_oracles as PO
+    n = 3000
+    X = PO.kmer_like(n, 5)
+    assert X.shape[1] == 2772
+    order6 = 2772 - 2080
+    cols = PO.tile_edge_columns(2772)
+    _, want, tol = PO.cov_oracle(X, cols)
+    want = np.asarray(want, dtype=np.float64)
+    _, drop, _ = PO.cov_oracle(np.delete(X, 1234, axis=0), cols)
+    bad = np.abs(np.asarray(drop, dtype=np.float64) - want) > tol
+    small = np.ix_(cols >= order6, cols >= order6)
+    assert bad.mean() > 0.5 and bad[small].mean() > 0.5
+    # a 16 x 16 block of order-6 features (rows 2000..2015, columns 2736..2751) against the same block one column over
+    blk = np.r_[2000:2016, 2736:2753]
+    _, c, t = PO.cov_oracle(X, blk)
+    c = np.asarray(c, dtype=np.float64)
+    right, shifted, bound = c[:16, 16:32], c[:16, 17:33], t[:16, 16:32]
+    assert (np.abs(shifted - right) > bound).mean() > 0.9
+    # and the bound is not vacuous: the float64 two-pass product stays inside it
+    Xc = X[:, cols] - X.mean(axis=0)[cols]
+    assert np.all(np.abs((Xc.T @ Xc) / (n - 1) - want) <= tol)

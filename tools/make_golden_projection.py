@@ -6,6 +6,8 @@ and the fixture FASTA tests/golden/inputs/proj_islands.fa.
 Everything here comes from the reference's own functions (tools/make_golden.load_reference_functions) and sklearn: PCA with
 svd_solver="full", DBSCAN(min_samples=50) and KMeans(n_init=20, max_iter=500, tol=1e-4, random_state=0).  This script does
 not use the package under test.  Every random input is drawn from a fixed numpy RandomState, so a rerun writes the same bytes.
+The edge goldens (keys dbscan_edges, kmeans_init, kmeans_more, pca_large) also use the numpy restatements of tests/proj_oracles.py
+to keep only cases whose decisions the kernels can reproduce exactly.
 
     python tools/make_golden_projection.py
 """
@@ -21,6 +23,9 @@ import numpy as np  # noqa: E402
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import make_golden as MG  # noqa: E402
+
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+import proj_oracles as PO  # noqa: E402     numpy restatements shared with the tests (no package code)
 
 GOLD, INP = MG.GOLD, MG.INP
 ARR = os.path.join(GOLD, "projection_cluster")
@@ -126,6 +131,181 @@ def kmeans_cases():
     return out
 
 
+# ------------------------------------------------------------------------------------------------ edge goldens
+def _embed(rs, d, vec):
+    """vec (length <= d) spread over d dimensions at random positions"""
+    out = np.zeros(d)
+    out[rs.permutation(d)[:len(vec)]] = vec
+    return out
+
+
+def dbscan_edge_cases():
+    """Integer-coordinate DBSCAN cases at d = 5, 16, 17 and 64 (every instantiation of db_pairs past MAXD = 4; sklearn takes its
+    brute-force path for d > 15), where every squared distance is an exact small integer, so a tie at eps is a tie in sklearn and
+    in the kernel alike:
+      ties_<d>     two core groups that reach one another only through Pythagorean offsets of length exactly eps (3-4-5 with
+                   eps = 5, 1-2-2-3 with eps = 3) and a border point at exactly eps from a core point of each of two clusters;
+      blobs_<d>    integer blobs with jitter in {-2..2}: many pairs at exactly eps, noise between;
+      noise_<d>    points at pairwise distance > eps: every label -1."""
+    from sklearn.cluster import DBSCAN
+    rs = np.random.RandomState(29)
+    cases = {}
+    for d in (5, 16, 17, 64):
+        for name, o, eps in (("ties345", (3.0, 4.0), 5.0), ("ties1223", (1.0, 2.0, 2.0), 3.0)):
+            O = rs.randint(-50, 50, size=d).astype(float)
+            o = _embed(rs, d, o)
+            axis = np.zeros(d)                                  # a unit axis orthogonal to o
+            free = [q for q in range(d) if o[q] == 0.0]
+            axis[free[rs.randint(len(free))]] = 1.0
+            # core a0 = O with tails O - j axis (j = 1..3), core c0 = O + 2 o with tails c0 - j axis; border X = O + o at exactly
+            # eps from a0 and from c0 and farther than eps from every tail point
+            grpC = [O + 2 * o] + [O + 2 * o - j * axis for j in (1, 2, 3)]
+            grpA = [O] + [O - j * axis for j in (1, 2, 3)]
+            X = O + o
+            far = [O + 40.0 * j * axis + _embed(rs, d, rs.randint(-2, 3, size=3).astype(float)) for j in range(1, 7)]
+            Y = np.array(grpC + [X] + grpA + far)
+            cases["%s_d%d" % (name, d)] = (Y, eps, 4)
+        centres = [rs.randint(-30, 30, size=d) * 3 for _ in range(3)]
+        pts = np.vstack([c + rs.randint(-2, 3, size=(m, d)) for c, m in zip(centres, (70, 50, 30))] +
+                        [rs.randint(-120, 120, size=(12, d))]).astype(float)
+        pts = pts[rs.permutation(len(pts))]
+        sq = ((pts[:, None, :] - pts[None, :, :]) ** 2).sum(-1)
+        eps = float(np.floor(np.sqrt(np.percentile(sq[sq > 0], 15))))    # an integer eps inside the blobs: many pairs tie at it
+        cases["blobs_d%d" % d] = (pts, eps, 10)
+        cases["noise_d%d" % d] = (np.array([rs.randint(-3, 4, size=d) + 100 * j for j in range(20)], dtype=float), 5.0, 2)
+    out = {}
+    for name, (Y, eps, ms) in cases.items():
+        sq = ((Y[:, None, :] - Y[None, :, :]) ** 2).sum(-1)
+        assert np.array_equal(Y, np.round(Y)) and np.abs(Y).max() < 2 ** 20        # integer data: every distance decision exact
+        lab = DBSCAN(eps=eps, min_samples=ms).fit(Y).labels_
+        want, _gap = PO.dbscan_oracle(Y, eps, ms)
+        assert np.array_equal(lab, want), name
+        if name.startswith("ties"):
+            assert (sq == eps * eps).any() and (lab[:5] == 0).all() and (lab[5:9] == 1).all() and (lab[9:] == -1).all(), name
+        if name.startswith("noise"):
+            assert (lab == -1).all(), name
+        out[name] = {"eps": eps, "min_samples": ms, "Y": _arr("dbscan_" + name + ".Y", Y),
+                     "labels": _arr("dbscan_" + name + ".labels", lab, np.int32)}
+    return out
+
+
+def _stale_lloyd(Y, C0, max_iter, tol):
+    """the pre-relocation rule (an empty cluster keeps its centre): used only to keep cases that tell the two rules apart"""
+    C = np.array(C0, dtype=float)
+    old = np.full(len(Y), -1)
+    for _ in range(max_iter):
+        lab = np.argmin(PO.sq_dist(Y, C), axis=1)
+        Cn = C.copy()
+        for c in range(len(C)):
+            if (lab == c).any():
+                Cn[c] = Y[lab == c].mean(axis=0)
+        shift, C = float(np.sum((Cn - C) ** 2)), Cn
+        if np.array_equal(lab, old) or shift <= tol:
+            break
+        old = lab
+    return np.argmin(PO.sq_dist(Y, C), axis=1), C
+
+
+def _sk_tol(Y, tol):
+    return float(np.mean(np.var(Y, axis=0)) * tol)        # sklearn's _tolerance
+
+
+def kmeans_init_cases():
+    """KMeans(init=C0, n_init=1, max_iter=500, tol=1e-4) from explicit centres: clusters that go empty mid-run (one per step with
+    a unique farthest point, and two in one step), points duplicated at fewer than k locations (no relocation: the largest
+    distance is 0), d = 5, 17 and 64, k = 1 and k = n.  A case is kept only where PO.lloyd (the kernel's rule restated) gives
+    sklearn's labels and n_iter_; the relocation cases also only where the pre-relocation rule ends elsewhere."""
+    from sklearn.cluster import KMeans
+    cases = {}
+    one, two = [], []
+    for seed in range(4000):
+        if len(one) >= 2 and len(two) >= 1:
+            break
+        rs = np.random.RandomState(seed)
+        n, k = rs.randint(20, 41), rs.randint(4, 7)
+        Y = rs.uniform(0.0, 10.0, size=(n, 2))
+        C0 = rs.uniform(-2.0, 12.0, size=(k, 2))
+        trace = []
+        lab, C, _, _ = PO.lloyd(Y, C0, 500, _sk_tol(Y, 1e-4), trace)
+        steps = [t for t in trace if t["moved"]]
+        if not steps or not all(t["unique_far"] for t in trace):
+            continue
+        slab, sC = _stale_lloyd(Y, C0, 500, _sk_tol(Y, 1e-4))
+        if np.array_equal(slab, lab) and np.allclose(sC, C):
+            continue
+        if all(t["empty"] == 1 for t in trace if t["empty"]) and len(one) < 2:
+            one.append((seed, Y, C0))
+        elif any(t["empty"] == 2 and len(t["moved"]) == 2 for t in trace) and not two:
+            two.append((seed, Y, C0))
+    assert len(one) == 2 and len(two) == 1
+    for j, (seed, Y, C0) in enumerate(one):
+        cases["empty_one_%d" % j] = (Y, C0)
+    cases["empty_two"] = (two[0][1], two[0][2])
+    # duplicates at two locations, k = 4: clusters stay empty and are placed on the largest cluster a - its centre when a comes
+    # first in id order, its coordinate sum when it comes after (sklearn's _average_centers).  sklearn runs on X - mean(X): the
+    # column means here are exact binary fractions (so every distance to a centre is exactly 0), and 0 in the second case (so
+    # that sklearn's sum of centred coordinates is the plain sum).
+    cases["dups_after"] = (np.array([(0.0, 0.0)] * 6 + [(4.0, 8.0)] * 2), np.array([(0.0, 0.0), (4.0, 8.0), (5.0, 5.0), (-4.0, 2.0)]))
+    cases["dups_before"] = (np.array([(1.0, 2.0)] * 6 + [(-2.0, -4.0)] * 3), np.array([(5.0, 5.0), (-2.0, -4.0), (1.0, 2.0), (-4.0, 2.0)]))
+    rs = np.random.RandomState(31)
+    for d in (5, 17, 64):
+        Y = np.vstack([rs.normal(rs.uniform(-4, 4, size=d), 1.0, size=(m, d)) for m in (90, 70, 50, 40)])
+        Y = Y[rs.permutation(len(Y))]
+        cases["d%d" % d] = (Y, Y[rs.choice(len(Y), 4, replace=False)] + rs.normal(0, 0.5, size=(4, d)))
+    Y = rs.normal(size=(50, 3))
+    cases["k1"] = (Y, rs.normal(size=(1, 3)))
+    Y = rs.uniform(0, 5, size=(12, 2))
+    cases["kn"] = (Y, Y[rs.permutation(12)] + rs.normal(0, 1e-3, size=(12, 2)))
+    out = {}
+    for name, (Y, C0) in cases.items():
+        tol = _sk_tol(Y, 1e-4)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            km = KMeans(n_clusters=len(C0), init=C0, n_init=1, max_iter=500, tol=1e-4).fit(Y)
+        lab, C, inertia, it = PO.lloyd(Y, C0, 500, tol)
+        assert np.array_equal(lab, km.labels_) and it == km.n_iter_, name
+        assert np.allclose(C, km.cluster_centers_, rtol=1e-12, atol=1e-12 * np.abs(Y).max()), name
+        assert abs(inertia - km.inertia_) <= 1e-12 * max(km.inertia_, 1.0), name
+        key = "kminit_" + name
+        out[name] = {"k": len(C0), "tol": tol, "max_iter": 500, "inertia": float(km.inertia_), "n_iter": int(km.n_iter_),
+                     "Y": _arr(key + ".Y", Y), "init": _arr(key + ".init", C0), "labels": _arr(key + ".labels", km.labels_, np.int32),
+                     "centers": _arr(key + ".centers", km.cluster_centers_)}
+    return out
+
+
+def kmeans_more_cases():
+    """KMeans(n_init=20, max_iter=500, tol=1e-4, random_state=0) (k-means++ seeding) at d = 5 and d = 17, as kmeans_cases."""
+    from sklearn.cluster import KMeans
+    rs = np.random.RandomState(37)
+    out = {}
+    for name, d, k in (("blobs_d5_k4", 5, 4), ("blobs_d17_k3", 17, 3)):
+        Y = np.vstack([rs.normal(rs.uniform(-6, 6, size=d), 1.0, size=(120 + 30 * i, d)) for i in range(k)])
+        Y = Y[rs.permutation(len(Y))]
+        km = KMeans(n_clusters=k, n_init=20, max_iter=500, tol=1e-4, random_state=0).fit(Y)
+        out[name] = {"k": k, "inertia": float(km.inertia_), "Y": _arr("kmeans_" + name + ".Y", Y),
+                     "labels": _arr("kmeans_" + name + ".labels", km.labels_, np.int32)}
+    return out
+
+
+def pca_large_cases():
+    """PCA(n_components=d, svd_solver="full") at F = 2 772 (--pcaMin 1 --pcaMax 6) on PO.planted_pca_input: X is not stored, its
+    seed and sha256 are; eigengap = (lambda_d - lambda_(d+1)) / lambda_1 scales the tests' tolerances."""
+    from sklearn.decomposition import PCA
+    out = {}
+    for n in (300, 3000):
+        for d in (2, 5):
+            seed = 1000 + n + d
+            X = PO.planted_pca_input(n, d, seed)
+            p = PCA(n_components=d + 1, svd_solver="full").fit(X)
+            ev = p.explained_variance_
+            name = "pca_n%d_f%d_d%d" % (n, X.shape[1], d)
+            out[name] = {"n": n, "f": X.shape[1], "d": d, "seed": seed, "sha256": PO.sha256(X),
+                         "eigengap": float((ev[d - 1] - ev[d]) / ev[0]),
+                         "Y": _arr(name + ".Y", p.transform(X)[:, :d]), "components": _arr(name + ".components", p.components_[:d]),
+                         "explained_variance": _arr(name + ".explained_variance", ev[:d])}
+    return out
+
+
 def writer_cases(ns):
     rs = np.random.RandomState(17)
     labels = np.array([["chr%s:%d:%d" % ("AB"[i % 2], 1 + 250 * i, 500 + 250 * i)] for i in range(12)])
@@ -218,7 +398,9 @@ def main():
     write_fixture()
     ns = MG.load_reference_functions(extra=("getBEDSeq", "cluster2df", "anomClust2gff"))
     doc = {"sklearn": sklearn.__version__, "min_samples": MIN_SAMPLES, "pca": pca_cases(), "dbscan": dbscan_cases(),
-           "kmeans": kmeans_cases(), "writers": writer_cases(ns), "e2e": end_to_end(ns)}
+           "kmeans": kmeans_cases(), "writers": writer_cases(ns), "e2e": end_to_end(ns),
+           "dbscan_edges": dbscan_edge_cases(), "kmeans_init": kmeans_init_cases(), "kmeans_more": kmeans_more_cases(),
+           "pca_large": pca_large_cases()}
     with open(os.path.join(GOLD, "projection_cluster.json"), "w") as fh:
         json.dump(doc, fh, indent=1, sort_keys=True)
         fh.write("\n")
