@@ -79,6 +79,12 @@ SYMBOLS = [
     ("frisk_dbscan", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
     ("frisk_kmeans", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_double, _P, _P,
                                C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    ("frisk_tsne_create", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(_P)]),
+    ("frisk_tsne_affinities", C.c_int, [_P, _P, _P, _P]),
+    ("frisk_tsne_run", C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    ("frisk_tsne_get", C.c_int, [_P, _P, _P, _P]),
+    ("frisk_tsne_set", C.c_int, [_P, _P, _P, _P]),
+    ("frisk_tsne_destroy", None, [_P]),
     ("frisk_host_alloc", C.c_void_p, [_P, C.c_int64]),
     ("frisk_host_free", None, [_P, _P]),
     ("frisk_last_kernel_ms", C.c_double, [_P, C.c_int]),

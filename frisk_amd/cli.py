@@ -6,8 +6,9 @@ caches, GFF3) and the same row echo on stdout.  Phase A and phase B run through 
 (frisk_amd.hotpath); thresholds, merging and GFF3 writing are host numpy (frisk_amd.postprocess).
 
 --hmmKLD runs frisk_amd.hmm (own 2-state Gaussian HMM; hmmlearn is absent and seeds randomly - parity unpinned).
---runProjection PCA with --cluster DBSCAN / KMEANS runs frisk_amd.projection on the GPU and writes the cluster-labelled GFF3.
-Out of scope here: the other projections (t-SNE, IncrementalPCA, NMF, MDS) and SPECTRAL clustering,
+--runProjection PCA or PY-TSNE (the reference's exact t-SNE, Y0 seeded by --seed, 0 when not given) with --cluster DBSCAN / KMEANS
+runs frisk_amd.projection on the GPU and writes the cluster-labelled GFF3.
+Out of scope here: the other projections (SKL-TSNE, IncrementalPCA, NMF, MDS) and SPECTRAL clustering,
 --graphics (seaborn/matplotlib), --gffIn intersections (bedtools).
 Those options are accepted, as in the reference, and reported as unavailable if used.
 
@@ -67,7 +68,7 @@ def build_parser():
     p.add_argument("--peakCRI", type=float, default=1.0)
     p.add_argument("--minPI", type=float, default=1.0)
     p.add_argument("--maxSI", type=float, default=1.0)
-    # projection / clustering (PCA, DBSCAN and KMEANS built; the other methods accepted, not available in this build)
+    # projection / clustering (PCA, PY-TSNE, DBSCAN and KMEANS built; the other methods accepted, not available in this build)
     p.add_argument("--runProjection", default=None, choices=[None, "PCA", "PY-TSNE", "SKL-TSNE", "IncrementalPCA", "NMF", "MDS"])
     p.add_argument("--projectionDims", type=int, default=2)
     p.add_argument("--dimReduce", default="windows", choices=["features", "windows"])
@@ -90,13 +91,13 @@ def build_parser():
     return p
 
 
-PROJECTIONS = ("PCA",)                  # --runProjection methods built here (frisk_amd.projection)
+PROJECTIONS = ("PCA", "PY-TSNE")        # --runProjection methods built here (frisk_amd.projection)
 CLUSTERINGS = ("DBSCAN", "KMEANS")      # --cluster methods built here
 
 
 def unavailable(args):
     """(option, reason) of every given option this build accepts but does not run.  --cluster runs only as DBSCAN or KMEANS
-    after --runProjection PCA (the reference clusters the projection, L1635-1655)."""
+    after --runProjection PCA or PY-TSNE (the reference clusters the projection, L1635-1655)."""
     clustering = args.runProjection in PROJECTIONS and args.cluster in CLUSTERINGS
     out = []
     for opt, why in (("cluster", "sklearn clustering is out of scope"),
@@ -220,21 +221,35 @@ class _Clock:
             sys.stderr.write(json.dumps({"frisk_timing": dict(self.parts), "total_s": total}) + "\n")
 
 
+def _seed(args):
+    # the reference passes random_state=None and leaves numpy unseeded (not reproducible); --seed, 0 when not given, seeds here
+    return int(args.seed) if args.seed is not None else 0
+
+
 def _project(args, anomCounts, device, clock):
-    """--runProjection PCA on the anomalies' k-mer proportions (L1612-1613), then --cluster DBSCAN / KMEANS on the projection
-    (L1635-1655).  Returns the cluster labels (None without a clustering this build runs)."""
+    """--runProjection PCA (L1612-1613) or PY-TSNE (L1622-1623) on the anomalies' k-mer proportions, then --cluster DBSCAN /
+    KMEANS on the projection (L1635-1655).  Returns the cluster labels (None without a clustering this build runs)."""
     from . import projection as P
-    res = P.pca(anomCounts, args.projectionDims, device=device)
-    log.info("PCA of %s x %s k-mer proportions: explained variance %s; covariance %.1f ms, eigh %.1f ms, transform %.1f ms",
-             anomCounts.shape[0], anomCounts.shape[1], res.explained_variance.tolist(), res.timings["cov_ms"],
-             res.timings["eigh_ms"], res.timings["transform_ms"])
-    clock.lap("PCA")
+    if args.runProjection == "PY-TSNE":
+        n = anomCounts.shape[0]
+        if not 2 <= n <= P.TSNE_MAX_N:
+            raise ValueError("PY-TSNE needs between 2 and %d anomalous windows, got %d" % (P.TSNE_MAX_N, n))
+        res = P.tsne(anomCounts, args.projectionDims, args.perplexity, seed=_seed(args), device=device,
+                     log=lambda it, c: log.info("Iteration %s : error is %s", it, c))
+        log.info("PY-TSNE of %s x %s k-mer proportions: mean sigma %s; PCA %.1f ms, affinities %.1f ms, 1000 iterations %.1f ms",
+                 n, anomCounts.shape[1], float(np.mean(np.sqrt(1.0 / res.beta))), res.timings["pca_ms"],
+                 res.timings["affinities_ms"], res.timings["iterations_ms"])
+    else:
+        res = P.pca(anomCounts, args.projectionDims, device=device)
+        log.info("PCA of %s x %s k-mer proportions: explained variance %s; covariance %.1f ms, eigh %.1f ms, transform %.1f ms",
+                 anomCounts.shape[0], anomCounts.shape[1], res.explained_variance.tolist(), res.timings["cov_ms"],
+                 res.timings["eigh_ms"], res.timings["transform_ms"])
+    clock.lap(args.runProjection)
     y_pred = None
     if args.cluster == "DBSCAN":
         y_pred = P.dbscan(res.Y, args.epsDBSCAN, device=device)
     elif args.cluster == "KMEANS":
-        # the reference passes random_state=None (not reproducible); --seed, 0 when not given, seeds k-means++ here
-        y_pred = P.kmeans(res.Y, args.kClusters, seed=int(args.seed) if args.seed is not None else 0, device=device).labels
+        y_pred = P.kmeans(res.Y, args.kClusters, seed=_seed(args), device=device).labels
     if y_pred is not None:
         log.info("%s: %s clusters, %s unclassified", args.cluster, len(set(y_pred.tolist()) - {-1}), int(np.sum(y_pred == -1)))
         clock.lap(args.cluster)

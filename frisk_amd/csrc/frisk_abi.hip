@@ -30,6 +30,7 @@
 #include "seq_pack2.h"
 #include "hmm_host.h"
 #include "proj_kernels.h"
+#include "tsne_kernels.h"
 
 #ifndef FRISK_K7_WPS
 #define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
@@ -2102,6 +2103,94 @@ int frisk_kmeans(int device, const double* Y, int64_t n, int32_t d, int32_t k, c
     if (!on.ok) return FRISK_E_HIP;
     return frisk_proj::kmeans(Y, n, d, k, init_centers, max_iter, tol, labels_out, centers_out, inertia_out, n_iter_out)
                ? FRISK_E_HIP : FRISK_OK;
+}
+
+// ---- exact t-SNE (tsne_kernels.h): a handle whose state stays on its device between calls
+struct frisk_tsne {
+    frisk_tsne_impl::State s;
+};
+
+int frisk_tsne_create(int device, const double* X, int64_t n, int32_t f, double perplexity, int32_t dims, const double* Y0,
+                      frisk_tsne** out) {
+    if (!out) return FRISK_E_ARG;
+    *out = nullptr;
+    if (!X || !Y0 || n < 2 || n > frisk_tsne_impl::MAX_N || f < 1 || f > frisk_tsne_impl::MAX_F || dims < 1 ||
+        dims > frisk_tsne_impl::MAX_D || !(perplexity > 0.0) || !std::isfinite(perplexity) || !all_finite(X, n * f) ||
+        !all_finite(Y0, n * dims))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    frisk_tsne* h = new (std::nothrow) frisk_tsne;
+    if (!h) return FRISK_E_HIP;
+    h->s.device = device;
+    h->s.n = n;
+    h->s.f = f;
+    h->s.d = dims;
+    h->s.perplexity = perplexity;
+    if (h->s.alloc(X, Y0)) {
+        delete h;
+        return FRISK_E_HIP;
+    }
+    *out = h;
+    return FRISK_OK;
+}
+
+int frisk_tsne_affinities(frisk_tsne* h, double* beta_out, int32_t* tries_out, double* q_out) {
+    if (!h) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    const int64_t n = h->s.n;
+    if (!h->s.have_p) {
+        const int e = h->s.affinities();
+        if (e) return e == -1 ? FRISK_E_ARG : FRISK_E_HIP;
+    }
+    if (beta_out && hipMemcpy(beta_out, h->s.beta, size_t(n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    if (tries_out && hipMemcpy(tries_out, h->s.tries, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return FRISK_E_HIP;
+    if (q_out && hipMemcpy(q_out, h->s.P, size_t(n) * size_t(n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return FRISK_E_HIP;
+    return FRISK_OK;
+}
+
+int frisk_tsne_run(frisk_tsne* h, int32_t iter_begin, int32_t iter_end, double* cost_out) {
+    if (!h || iter_begin < 0 || iter_end < iter_begin || iter_end > frisk_tsne_impl::MAX_ITER) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    if (!h->s.have_p) {
+        const int e = h->s.affinities();
+        if (e) return e == -1 ? FRISK_E_ARG : FRISK_E_HIP;
+    }
+    return h->s.run(iter_begin, iter_end, cost_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_tsne_get(frisk_tsne* h, double* Y, double* iY, double* gains) {
+    if (!h) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    const size_t bytes = size_t(h->s.n) * size_t(h->s.d) * sizeof(double);
+    if (Y && hipMemcpy(Y, h->s.Y, bytes, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    if (iY && hipMemcpy(iY, h->s.iY, bytes, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    if (gains && hipMemcpy(gains, h->s.gains, bytes, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    return FRISK_OK;
+}
+
+int frisk_tsne_set(frisk_tsne* h, const double* Y, const double* iY, const double* gains) {
+    if (!h) return FRISK_E_ARG;
+    const int64_t nd = h->s.n * h->s.d;
+    if ((Y && !all_finite(Y, nd)) || (iY && !all_finite(iY, nd)) || (gains && !all_finite(gains, nd))) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    const size_t bytes = size_t(nd) * sizeof(double);
+    if (Y && hipMemcpy(h->s.Y, Y, bytes, hipMemcpyHostToDevice) != hipSuccess) return FRISK_E_HIP;
+    if (iY && hipMemcpy(h->s.iY, iY, bytes, hipMemcpyHostToDevice) != hipSuccess) return FRISK_E_HIP;
+    if (gains && hipMemcpy(h->s.gains, gains, bytes, hipMemcpyHostToDevice) != hipSuccess) return FRISK_E_HIP;
+    return FRISK_OK;
+}
+
+void frisk_tsne_destroy(frisk_tsne* h) {
+    if (!h) return;
+    frisk_proj::OnDevice on(h->s.device);
+    delete h;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 """Symmetric k-mer proportions of anomalous windows, and their projection and clustering:
 PCA, DBSCAN and k-means as the reference runs them through sklearn (L1597-1665), on the GPU (frisk_proj_* / frisk_dbscan /
-frisk_kmeans, csrc/proj_kernels.h).  t-SNE, IncrementalPCA, NMF, MDS and spectral clustering are not built.
+frisk_kmeans, csrc/proj_kernels.h), and the reference's own exact t-SNE, PY-TSNE (frisk/tsne.py, L1622-1623), on the GPU
+(frisk_tsne_*, csrc/tsne_kernels.h).  sklearn's t-SNE, IncrementalPCA, NMF, MDS and spectral clustering are not built.
 
 Reference (frisk/__init__.py): computeKmers(sym=True, pcaMode=True) L280-367 counts every valid word AND its
 reverse complement for orders pcaMin..pcaMax; scrubMirrors L797-811 keeps one key of each reverse-complement pair
@@ -212,3 +213,107 @@ def kmeans(Y, k, seed=0, n_init=KMEANS_N_INIT, max_iter=KMEANS_MAX_ITER, tol=KME
     best.labels = remap[best.labels]
     best.centers = best.centers[order]
     return best
+
+
+# ------------------------------------------------------------------------------------------------ PY-TSNE
+TSNE_ITERATIONS = 1000              # tsne.py max_iter
+TSNE_MAX_N = 50000                  # the dense n x n affinities: 20 GB at the cap
+
+
+class TSNE:
+    """A t-SNE run on the GPU (frisk_tsne_*): X (n x f, f <= 64) already reduced, Y0 (n x dims) the start.  The state stays on
+    the device between calls; use as a context manager (or call close())."""
+
+    def __init__(self, X, Y0, perplexity=20.0, device=0):
+        X, Y0 = _f64(X, 2), _f64(Y0, 2)
+        if X.shape[0] != Y0.shape[0]:
+            raise ValueError("X has %d rows, Y0 %d" % (X.shape[0], Y0.shape[0]))
+        self.n, self.f = X.shape
+        self.dims = Y0.shape[1]
+        self._h = C.c_void_p()
+        _call("frisk_tsne_create", device, _ptr(X), self.n, self.f, float(perplexity), self.dims, _ptr(Y0), C.byref(self._h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._h:
+            _ffi.lib().frisk_tsne_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def affinities(self, q=False):
+        """(beta, tries) of every row, plus the n x n q = max(normalised symmetric P, 1e-12 / 4) when q is True."""
+        beta, tries = np.empty(self.n), np.empty(self.n, dtype=np.int32)
+        qm = np.empty((self.n, self.n)) if q else None
+        _call("frisk_tsne_affinities", self._h, _ptr(beta), _ptr(tries), _ptr(qm) if q else None)
+        return (beta, tries, qm) if q else (beta, tries)
+
+    def run(self, begin, end):
+        """Iterations begin .. end - 1; returns the costs of the t with (t + 1) % 10 == 0 among them."""
+        cost = np.empty(max(0, end // 10 - begin // 10))
+        _call("frisk_tsne_run", self._h, int(begin), int(end), _ptr(cost))
+        return cost
+
+    def get(self):
+        """(Y, iY, gains), each n x dims."""
+        out = [np.empty((self.n, self.dims)) for _ in range(3)]
+        _call("frisk_tsne_get", self._h, *[_ptr(a) for a in out])
+        return tuple(out)
+
+    def set(self, Y=None, iY=None, gains=None):
+        arrs = [None if a is None else _f64(a, 2) for a in (Y, iY, gains)]
+        for a in arrs:
+            if a is not None and a.shape != (self.n, self.dims):
+                raise ValueError("expected shape %s, got %s" % ((self.n, self.dims), a.shape))
+        _call("frisk_tsne_set", self._h, *[None if a is None else _ptr(a) for a in arrs])
+
+
+class TSNEResult:
+    """Y (n x dims), cost (the 100 logged costs, iterations 10, 20, ..., 1000), beta (n), tries (n); timings in ms."""
+
+    def __init__(self, Y, cost, beta, tries, timings):
+        self.Y, self.cost, self.beta, self.tries, self.timings = Y, cost, beta, tries, timings
+
+
+def tsne_input(X, initial_dims=50, device=0):
+    """Step 1 of tsne.tsne (its pca(), L83-91): X centred and projected on the top min(initial_dims, f) eigenvectors of its
+    covariance (covariance and transform on the GPU, eigh on the same device).  The reference keeps numpy's eig columns, whose
+    signs and order differ, but only the pairwise distances of the result are used.  Unlike pca(), any n >= 1 is allowed."""
+    import torch
+    X = _f64(X, 2)
+    f = X.shape[1]
+    keep = min(initial_dims, f)
+    mean, c = cov(X, device)
+    w, v = torch.linalg.eigh(torch.from_numpy(c).to(torch.device("cuda", device)))
+    w, v = w.cpu().numpy(), v.cpu().numpy()
+    order = np.argsort(w, kind="stable")[::-1][:keep]
+    return transform(X, mean, np.ascontiguousarray(v[:, order]), device)
+
+
+def tsne(X, dims=2, perplexity=20.0, seed=0, initial_dims=50, device=0, log=None):
+    """The reference's tsne.tsne(X, dims, initial_dims, perplexity) (L1622-1623) from Y0 = RandomState(seed).randn(n, dims)
+    (the reference's draw after np.random.seed(seed)): exact t-SNE, 1000 iterations on the GPU.  log, if given, is called with
+    (iteration, cost) every 10 iterations, as the reference logs them.  The trajectory is chaotic: the result matches the
+    reference's step by step and in structure, not in its final coordinates."""
+    X = _f64(X, 2)
+    n = X.shape[0]
+    if not 2 <= n <= TSNE_MAX_N:
+        raise ValueError("PY-TSNE needs between 2 and %d samples, got %d" % (TSNE_MAX_N, n))
+    t0 = time.perf_counter()
+    Xp = tsne_input(X, initial_dims, device)
+    t1 = time.perf_counter()
+    Y0 = np.random.RandomState(seed).randn(n, dims)
+    with TSNE(Xp, Y0, perplexity, device) as h:
+        beta, tries = h.affinities()
+        t2 = time.perf_counter()
+        cost = h.run(0, TSNE_ITERATIONS)
+        t3 = time.perf_counter()
+        Y = h.get()[0]
+    if log is not None:
+        for k, c in enumerate(cost):
+            log(10 * (k + 1), c)
+    return TSNEResult(Y, cost, beta, tries, {"pca_ms": 1e3 * (t1 - t0), "affinities_ms": 1e3 * (t2 - t1),
+                                             "iterations_ms": 1e3 * (t3 - t2)})

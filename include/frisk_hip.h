@@ -291,6 +291,31 @@ int frisk_dbscan(int device, const double* Y, int64_t n, int32_t d, double eps, 
 int frisk_kmeans(int device, const double* Y, int64_t n, int32_t d, int32_t k, const double* init_centers, int32_t max_iter,
                  double tol, int32_t* labels_out, double* centers_out, double* inertia_out, int32_t* n_iter_out);
 
+/* Exact t-SNE of the reference's --runProjection PY-TSNE (frisk/tsne.py: x2p, then 1000 iterations of gradient descent with
+ * momentum, gains and early exaggeration), FP64 on `device`.  The handle keeps X, the affinities and the optimiser state (Y, iY,
+ * gains) on the device between calls, so a caller can step the optimiser; every result is bit-identical from run to run.
+ * frisk_tsne_create: X[n][f] (the input after the caller's PCA step), perplexity, dims output columns, Y0[n][dims] the start;
+ *   iY = 0 and gains = 1.  FRISK_E_ARG, with nothing allocated, unless 2 <= n <= 50 000, 1 <= f <= 64, 1 <= dims <= 64,
+ *   perplexity > 0 and X, Y0 and perplexity finite.  Device memory: 8 n^2 bytes for the affinities plus O(n (f + dims)).
+ * frisk_tsne_affinities: computes the affinities once (later calls only copy): squared distances by direct differences; per row
+ *   the reference's bisection on beta from 1 (target entropy log(perplexity), tolerance 1e-5, at most 50 tries); P + PT
+ *   normalised by its total; q = max(that, 1e-12 / 4), so that the reference's P is 4 q for iterations 0 .. 100 and q after.
+ *   Outputs (each nullable): beta_out[n], tries_out[n], q_out[n][n].  FRISK_E_ARG when a row's sum of exp(-D beta) is 0 or not
+ *   finite (the reference's row would be NaN).
+ * frisk_tsne_run: iterations t = iter_begin .. iter_end - 1 (0 <= iter_begin <= iter_end <= 1000) on one stream, without a host
+ *   sync inside; momentum (0.5 for t < 20, then 0.8) and exaggeration (t <= 100) follow from t, so run(0, 1000) equals run(0, 400)
+ *   then run(400, 1000) bit for bit.  cost_out (nullable): the reference's logged cost sum P log(P / Q) of every t with
+ *   (t + 1) % 10 == 0, in order.  Computes the affinities first if frisk_tsne_affinities has not.
+ * frisk_tsne_get / frisk_tsne_set: the state Y, iY, gains (each [n][dims], each nullable); set rejects non-finite values. */
+typedef struct frisk_tsne frisk_tsne;
+int  frisk_tsne_create(int device, const double* X, int64_t n, int32_t f, double perplexity, int32_t dims, const double* Y0,
+                       frisk_tsne** out);
+int  frisk_tsne_affinities(frisk_tsne* h, double* beta_out, int32_t* tries_out, double* q_out);
+int  frisk_tsne_run(frisk_tsne* h, int32_t iter_begin, int32_t iter_end, double* cost_out);
+int  frisk_tsne_get(frisk_tsne* h, double* Y, double* iY, double* gains);
+int  frisk_tsne_set(frisk_tsne* h, const double* Y, const double* iY, const double* gains);
+void frisk_tsne_destroy(frisk_tsne* h);
+
 /* Page-locked host memory for result buffers: D2H copies into it are asynchronous and run at PCIe rate
  * (pageable buffers work too, at a fraction of it).  Free with frisk_host_free before frisk_destroy. */
 void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);

@@ -4,12 +4,15 @@
   covariance, eigh (torch.linalg.eigh on the device) and transform ms at n = 30 000 and 100 000 windows of F = 2 772 features
   (--pcaMin 1 --pcaMax 6), and the covariance call's FP64 rate (2 n F^2 FLOP over its time; the kernels do half of that, the upper triangle);
   DBSCAN ms at n = 1e5 and 1e6 points of d = 2; k-means ms (k = 2, 20 starts) at n = 1e6;
-  numpy / sklearn on the host's CPUs for the same work (null where sklearn is absent).
+  numpy / sklearn on the host's CPUs for the same work (null where sklearn is absent);
+  PY-TSNE (exact t-SNE, d = 2, perplexity 20) at n = 5 000, 20 000 and 50 000 windows of F = 2 772 reduced to 50 columns:
+  PCA-step, affinity and per-iteration ms, the 1000-iteration total, and the numpy restatement's ms per iteration on the host
+  (tests/tsne_oracle.py, 20 iterations at n = 5 000).
 
 Every GPU time is a host clock around one call, which ends in a device-to-host copy (so it includes the host-to-device copy of the
 input); each shape is run once untimed first.  --small: tiny sizes, for a profiler run.
 
-    python tools/proj_timing.py [--small] [--no-cpu]
+    python tools/proj_timing.py [--small] [--no-cpu] [--tsne-only]
 """
 import argparse
 import json
@@ -45,7 +48,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--tsne-only", action="store_true", help="only the PY-TSNE legs")
     opts = ap.parse_args()
+    if opts.tsne_only:
+        print(json.dumps({"tool": "proj_timing", "tsne": tsne_legs(opts)}))
+        return
     from frisk_amd import projection as P
     F = 2772
     pca_ns = (3000,) if opts.small else (30000, 100000)
@@ -87,7 +94,43 @@ def main():
         except ImportError:
             out["cpu"]["sklearn"] = None
     out["cpu"]["threads"] = os.cpu_count()
+    out["tsne"] = tsne_legs(opts)
     print(json.dumps(out))
+
+
+def tsne_legs(opts):
+    from frisk_amd import projection as P
+    F, iters = 2772, P.TSNE_ITERATIONS
+    out = {"F": F, "initial_dims": 50, "d": 2, "perplexity": 20.0, "iterations": iters}
+    for n in ((1000,) if opts.small else (5000, 20000, 50000)):
+        X = _proportions(n, F, n)
+        t0 = time.perf_counter()
+        Xp = P.tsne_input(X, 50)
+        t1 = time.perf_counter()
+        with P.TSNE(Xp, np.random.RandomState(0).randn(n, 2), 20.0) as h:
+            t1c = time.perf_counter()
+            beta, tries = h.affinities()
+            t2 = time.perf_counter()
+            h.run(0, 10)                  # warm-up of the iteration kernels (counted in the total below)
+            t3 = time.perf_counter()
+            cost = h.run(10, iters)
+            t4 = time.perf_counter()
+        out[str(n)] = {"pca_step_ms": 1e3 * (t1 - t0), "create_ms": 1e3 * (t1c - t1), "affinity_ms": 1e3 * (t2 - t1c), "tries_mean": float(tries.mean()),
+                       "tries_max": int(tries.max()), "ms_per_iteration": 1e3 * (t4 - t3) / (iters - 10),
+                       "iterations_total_ms": 1e3 * (t4 - t2), "final_cost": float(cost[-1])}
+    if not opts.no_cpu:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+        import tsne_oracle as TO
+        n = 1000 if opts.small else 5000
+        Xp = P.tsne_input(_proportions(n, F, n), 50)
+        _b, _t, q = TO.affinities(Xp, 20.0)
+        Y, iY, gains = np.random.RandomState(0).randn(n, 2), np.zeros((n, 2)), np.ones((n, 2))
+        t0 = time.perf_counter()
+        for t in range(20):
+            st = TO.step(Y, iY, gains, q, t)
+            Y, iY, gains = st.Y, st.iY, st.gains
+        out["numpy_oracle_ms_per_iteration_%d" % n] = 1e3 * (time.perf_counter() - t0) / 20
+    return out
 
 
 if __name__ == "__main__":
