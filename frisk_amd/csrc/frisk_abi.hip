@@ -32,15 +32,9 @@
 #include "proj_kernels.h"
 #include "tsne_kernels.h"
 
-#ifndef FRISK_K7_WPS
 #define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
-#endif
-#ifndef FRISK_SIDE_SHARE
 #define FRISK_SIDE_SHARE 0.06       // 4-bit bulk takes the side-table form when the plain form would hand on more than this share of the sample
-#endif
-#ifndef FRISK_K8_WIDTH
 #define FRISK_K8_WIDTH 0            // order-8 counters of the default K = 8 path (scan8_kernel.h): 0 = adaptive 4/8 bits, 4, 8, 16 = off
-#endif
 
 namespace {
 
@@ -1306,10 +1300,7 @@ static int profile_add_range(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1
     // counter sends its workgroup to the two-half form).  The walk halves, the flush doubles (65 536 fields per workgroup instead of
     // 32 768 bins): measured 2.42 -> 1.33 ms on the 3.29 Gb shape, 0.345 -> 0.55 ms on the 410 Mb shard (tools/exp/prof_ab.py) - so from
     // 2^30 positions per launch on.  (mask_host bit 1 = FRISK_PROFILE_ONE_PASS forces it: the tests' way to the overflow path.)
-#ifndef FRISK_PROF16
-#define FRISK_PROF16 1
-#endif
-    const bool one_pass = c->kmax == 8 && FRISK_PROF16 && ((mask_host & 2) || p1 - p0 >= (int64_t(1) << 30));
+    const bool one_pass = c->kmax == 8 && ((mask_host & 2) || p1 - p0 >= (int64_t(1) << 30));
     mask_host &= 1;
     if (one_pass) {
         const int64_t span16 = p1 - p0;
@@ -1333,10 +1324,8 @@ static int profile_add_range(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1
     const size_t lds = (size_t(1) << (2 * c->kmax)) / size_t(halves) * 4;
     const int64_t span = p1 - p0;
     const int64_t nwords = span > 0 ? ((p1 + 31) >> 5) - (p0 >> 5) : 0;     // a lane takes one 32-position bitmap word
-#ifndef FRISK_PROF_WG_PER_CU
-#define FRISK_PROF_WG_PER_CU 1      // measured on the 410 Mb shard: 1 -> 0.34 ms, 2 -> 0.41, 4 -> 0.51 (the flush of the private tables dominates)
-#endif
-    int64_t nchunks = std::min<int64_t>(std::max<int64_t>(1, span / 65536), int64_t(c->num_cu) * FRISK_PROF_WG_PER_CU / halves);
+    constexpr int64_t wg_per_cu = 1;        // measured on the 410 Mb shard: 1 -> 0.34 ms, 2 -> 0.41, 4 -> 0.51 (the flush of the private tables dominates)
+    int64_t nchunks = std::min<int64_t>(std::max<int64_t>(1, span / 65536), int64_t(c->num_cu) * wg_per_cu / halves);
     const int64_t chunk_len = (nwords + nchunks - 1) / std::max<int64_t>(nchunks, 1);   // in words
     nchunks = chunk_len > 0 ? (nwords + chunk_len - 1) / chunk_len : 0;
     if (first) HIPC(c, hipEventRecord(c->evp0, c->stream));
@@ -1609,17 +1598,11 @@ static int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64
         HIPC(c, hipMemsetAsync(c->o_ivom.p, 0, N * 2 * nk * sizeof(double), c->stream));
         P.dbg_ivom = c->o_ivom.p;
     }
-    P.stamps = nullptr;
+    P.unused_stamps = nullptr;
     P.rc_tab = c->d_rctab.p; P.in_list = nullptr; P.in_count = nullptr; P.out_list = nullptr; P.out_count = nullptr;
     P.sel_mode = 0; P.sel_mod = 16; P.queue = nullptr; P.queue_n = 1; P.slide_pp = 0; P.ig_ring = nullptr;
     P.verdict = nullptr; P.my_form = 0u;
     c->scan_stat[0] = 16; c->scan_stat[1] = 0; c->scan_stat[2] = 0; c->scan_stat[3] = 1; c->scan_stat[4] = 0;
-#ifdef FRISK_STAMPS
-    DevBuf<unsigned long long> d_stamps;
-    HIPC(c, d_stamps.reserve(4 * 16 * 12));
-    HIPC(c, hipMemsetAsync(d_stamps.p, 0, 4 * 16 * 12 * 8, c->stream));
-    P.stamps = d_stamps.p;
-#endif
 
     const bool k8 = (c->kmax == 8);
     // LDS budget: 160 KB per workgroup.  Long windows at K = 8 need a long orphan list; the shared prefix tables
@@ -1726,12 +1709,8 @@ static int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64
         // chunks of 16 consecutive windows where the tables slide and the genome-side values travel through the ring (one window
         // in 16 is counted - and gathered - afresh; measured on the bench shard: 8: 6.71 ms, 12: 6.65, 16: 6.61, 24: 6.79), of 8 otherwise
         const bool can_slide = 2 * int64_t(inc) <= int64_t(w) - (c->kmax - 1) && !tune_env("FRISK_NO_SLIDE");
-#ifndef FRISK8_CHUNK_LONG
-#define FRISK8_CHUNK_LONG 16
-#endif
-        // (a long scan can afford longer chunks - fewer windows counted and gathered afresh - while every workgroup still gets FRISK8_CHUNK_ROUNDS of them)
-        int64_t chunk_cap = can_slide ? 16 : 8;
-        if (can_slide && FRISK8_CHUNK_LONG > 16) chunk_cap = std::max<int64_t>(16, std::min<int64_t>(FRISK8_CHUNK_LONG, n / (int64_t(c->num_cu) * 3 * 64)));
+        // (chunks of 32 on long scans, FRISK8_CHUNK_LONG at c34d7fb: inside the noise, NOTES round 4)
+        const int64_t chunk_cap = can_slide ? 16 : 8;
         int64_t chunk8 = std::max<int64_t>(1, std::min<int64_t>(n / (int64_t(c->num_cu) * 3 * 8), chunk_cap));
         // A SHORT scan (fewer than 2 x 16 windows per workgroup: BASELINE's C3, a rank's share of a small genome) is dealt statically in
         // TWO rounds of the launch's workgroups: chunks of ceil(n / (2 x workgroups)) windows, tables sliding and the ring inside a chunk.
@@ -1927,25 +1906,6 @@ static int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64
     }
 #undef FRISK_LAUNCH
     HIPC(c, e);
-#ifdef FRISK_STAMPS
-    {
-        std::vector<unsigned long long> h(4 * 16 * 12);
-        HIPC(c, hipMemcpyAsync(h.data(), d_stamps.p, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipStreamSynchronize(c->stream));
-        static const char* names16[9] = {"stage1", "barrier1", "stage2", "stage3", "barrier3", "stage4", "blocksum", "cleanup+store", "endbarrier"};
-        static const char* names8[9] = {"stage1", "barrier1", "stage2a+b", "stage2b+b", "stage3+b", "stage4", "sums+b", "clear+store", "endbarrier"};
-        const char* const* names = narrow ? names8 : names16;
-        double acc[9] = {0}; int cnt = 0;
-        for (int b = 0; b < 4; ++b) for (int w = 4; w < 16; ++w) {
-            const unsigned long long* t = &h[(b * 16 + w) * 12];
-            if (!t[0] || !t[9]) continue;
-            for (int i = 0; i < 9; ++i) acc[i] += double(t[i + 1] - t[i]);
-            ++cnt;
-        }
-        if (cnt) { std::fprintf(stderr, "[stamps] windows %d:", cnt); for (int i = 0; i < 9; ++i) std::fprintf(stderr, " %s %.0f", names[i], acc[i] / cnt); std::fprintf(stderr, "\n"); }
-        d_stamps.release();
-    }
-#endif
     if (!rows_sent) {
         if (c->plan_maxwin <= 65535 && c->kmax <= 8 && n > 0) {     // the LDS kernels leave the rows' scalar tail to one thread per row
             finish_rows_kernel<<<grid_for(n, 256, 1 << 20), 256, 0, c->stream>>>(n, P.status, P.kld, P.gc, P.sw, P.sg);

@@ -39,35 +39,14 @@
 #include "scan_kernel.h"
 
 #define FRISK8_ORPH_CAP 24         // orphan entries kept in LDS (two per invalid run); a window with more goes to the 16-bit form
-#ifndef FRISK8_UNROLL1
 #define FRISK8_UNROLL1 2           // unroll factor of the stage-1 position loop
-#endif
-#ifndef FRISK8_SHORT_LANES
 #define FRISK8_SHORT_LANES 6        // stage 1: up to this many lanes of a wave with short words get a pass each (more: per position)
-#endif
-#ifndef FRISK8_PRIO
-#define FRISK8_PRIO 3               // wave priority (s_setprio) of every stage but the scoring loop; 0 = no priorities
-#endif
-#ifndef FRISK8_W7_READ
-#define FRISK8_W7_READ 0            // 4-bit form: 1 = the (K-1)-mer's four nibbles come from an LDS read of their own (round 2's form)
-#endif
-#ifndef FRISK8_PRE_SPLIT
-#define FRISK8_PRE_SPLIT 1          // shared prefix sums as two arrays - A[] read by one ds_read_b64, W[] by one ds_read_b32 - instead of
-#endif                              // interleaved 12-byte entries (a ds_read2_b32 and a ds_read_b32: half again as many LDS passes)
-#ifndef FRISK8_PLACE
-#define FRISK8_PLACE 1              // orphans are folded into the order-K table where it has room (stage 3): no orphan compares in the scoring loop
-#endif
-#ifndef FRISK8_RING
-#define FRISK8_RING 1               // genome-side values travel from window to window through a per-workgroup ring in global memory (below)
-#endif
-#ifndef FRISK8_PARK_LATE
-#define FRISK8_PARK_LATE 0          // 1: a parking wave stores behind its scoring loop instead of inside it (measured: +-0)
-#endif
-#ifndef FRISK8_RING_COLS
+#define FRISK8_PRIO 3               // wave priority (s_setprio) of every stage but the scoring loop
 #define FRISK8_RING_COLS 256        // ring geometry: ITS rows x 256 columns of doubles per workgroup (position p <-> row p % ITS, column p / ITS % 256):
-#endif                              // ITS x 256 = the most positions a window of this instantiation has - 40 KB per workgroup at 20 positions per lane
+                                    // ITS x 256 = the most positions a window of this instantiation has - 40 KB per workgroup at 20 positions per lane
                                     // (round 3 had 512 columns, 80 KB: the same time, twice the footprint beside 4 MB of L2 per XCD)
-#define FRISK8_RING_PAD 16          // doubles behind every workgroup's slice of the ring (see dummy_off)
+#define FRISK8_RING_PAD 16          // doubles behind every workgroup's slice of the ring, touched by nobody (the idle lanes of FRISK8_DEAL's
+                                    // parking waves stored there, at c34d7fb); part of the slice stride
 #define FRISK8_SLOTS 8             // misc counters per window (double-buffered by window parity)
 
 enum { M8_NPLACED = 1,             // misc slots (0, 2, 4, 5: M_UPA, M_UPG, M_NORPH, M_NVALID): orphans folded into the order-K table ...
@@ -84,7 +63,9 @@ struct Lds8 {
     static constexpr uint32_t small_bytes = 2736;                                  // orders kmin..KMAX-3 as u16 bins (sized for 1..5)
     static constexpr uint32_t orphans = small + small_bytes;                       // u16[FRISK8_ORPH_CAP]
     static constexpr uint32_t NL = 1u << (2 * (KMAX - 3));                         // entries of the shared prefix tables (level KMAX-3)
-    static constexpr uint32_t pre = (orphans + FRISK8_ORPH_CAP * 2 + 15) / 16 * 16;     // Pre8[NL]: the shared prefix sums, 12 bytes each
+    // the shared prefix sums, 12 bytes each, as two arrays: A (NL doubles, one ds_read_b64) and W behind it (NL words, one ds_read_b32)
+    // (interleaved 12-byte entries took a ds_read2_b32 and a ds_read_b32: half again as many LDS passes; FRISK8_PRE_SPLIT at c34d7fb)
+    static constexpr uint32_t pre = (orphans + FRISK8_ORPH_CAP * 2 + 15) / 16 * 16;
     // SIDE (below): the side table follows the prefix sums (whose weights carry the side count of the (K-3)-mer's 4-mer in their top bits)
     // (LDS is handed out in pieces of 1280 bytes on gfx950: three workgroups per CU get 42 of them each = 53 760 bytes)
     static constexpr uint32_t side = pre + NL * 12;                                // u8[256]: counts of the period-4 max-mers (SIDE)
@@ -116,13 +97,6 @@ __device__ inline double log_tab_n(double x, const double2* tab) {
     for (int d = DEG - 1; d >= 2; --d) p = __builtin_fma(r, p, (d & 1) ? 1.0 / d : -1.0 / d);
     return __builtin_fma(double(k), 0.69314718055994530942, e.y) + __builtin_fma(r * r, p, r);
 }
-
-// shared prefix sums of one (K-3)-mer, the orders kmin..K-3 of a max-mer's two sums (as scan_kernel.h's pre_i / pre_w): numerator
-// term and integer weight, interleaved so that ONE address serves both reads of a position
-struct __attribute__((packed, aligned(4))) Pre8 {
-    double A;
-    uint32_t W;
-};
 
 template <int CTRL>
 __device__ inline uint32_t dpp_addu(uint32_t x) {
@@ -168,13 +142,13 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     constexpr int NW = NT / 64;
     constexpr int SHW = BITS == 8 ? 2 : 3;               // code >> SHW = dword of the table
     constexpr uint32_t PERM = (32 / BITS) - 1;           // code & PERM = field inside the dword
-    static_assert(!SIDE || (KMAX == 8 && BITS == 4 && !DEBUG && NT == 256 && FRISK8_PRE_SPLIT), "the side table exists for the 4-bit form at K = 8");
+    static_assert(!SIDE || (KMAX == 8 && BITS == 4 && !DEBUG && NT == 256), "the side table exists for the 4-bit form at K = 8");
     using L = Lds8<KMAX, BITS, LOGN, NT, SIDE>;
     // the order-K table is cleared whole when that takes no more stores per thread than a lane has positions (measured: 64 KiB
     // for windows of 2000 bases is the one case where every position clearing its own dword is cheaper)
     constexpr bool CLEAR_ALL = L::t8_bytes / 16 / NT <= uint32_t(ITS);
     // K = 7, 8: thread t sums the table below ITS OWN (K-3)-mers (the 4-mer t / its four 5-mers), so that stage 2 runs inside stage 3: no
-    // barrier and no LDS round trip between the table sums and the prefix tables made from them
+    // barrier and no LDS round trip between the table sums and the prefix tables made from them (K = 7: the 64 counters below the 4-mer t itself)
     constexpr bool FUSED = (KMAX >= 7 && NT >= 256 && NT % 256 == 0);
     // Orphans - the (K-1)- and (K-2)-mers that are no prefix of a counted max-mer - need not be compared against every position's
     // code in the scoring loop: an orphan (K-1)-mer can be ADDED TO THE TABLE as a max-mer that does not occur in the window (a
@@ -184,12 +158,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     // that does not occur.  Stage 3 does this, the thread that owns the orphan's 4-mer (whose sums over that part of the table
     // follow in program order); where the table has no room the orphan stays on the list and the window takes the scoring loop
     // with compares.  The same counts either way, so the same bits.  (Debug builds dump every counter: they keep the list.)
-    constexpr bool PLACE = FRISK8_PLACE && FUSED && !DEBUG;
-#ifdef FRISK8_ROLLED
-    constexpr bool ROLLED_K = FRISK8_ROLLED != 0;
-#else
-    constexpr bool ROLLED_K = KMAX < 8 || NT > 256;      // the scoring loop is rolled (two groups per trip) - measured per K, see stage 4
-#endif                 // (K = 7: the 64 counters below the 4-mer t itself)
+    constexpr bool PLACE = FUSED && !DEBUG;
     __shared__ __attribute__((aligned(16))) unsigned char lds[L::total];
     const int tid0 = threadIdx.x;
     const int kmin0 = P.kmin;
@@ -198,8 +167,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     uint32_t* small32 = reinterpret_cast<uint32_t*>(lds + L::small);
     uint16_t* small16 = reinterpret_cast<uint16_t*>(lds + L::small);
     uint16_t* orph = reinterpret_cast<uint16_t*>(lds + L::orphans);
-    Pre8* pre = reinterpret_cast<Pre8*>(lds + L::pre);
-    double* preA = reinterpret_cast<double*>(lds + L::pre);                    // (FRISK8_PRE_SPLIT: NL doubles, then NL words)
+    double* preA = reinterpret_cast<double*>(lds + L::pre);                    // (NL doubles, then NL words)
     uint32_t* preW = reinterpret_cast<uint32_t*>(lds + L::pre + NL * 8);
     // SIDE.  A window of a real assembly that holds a max-mer 16+ times nearly always holds a SIMPLE one: a poly-A tail, a
     // (CA)n or (AAAT)n run.  Such a window wraps a 4-bit counter and had to be redone with 8-bit counters - two workgroups per
@@ -221,7 +189,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     const unsigned char* side8 = lds + L::side;
     auto put_pre = [&](uint32_t idx, double A, uint32_t W, uint32_t sd = 0u) __attribute__((always_inline)) {
         if constexpr (SIDE) { preA[idx] = A; preW[idx] = W | (sd << 23); }     // (W < 5120 (4 + 16 + ... + 4^5) < 2^23; the side count < 2^8)
-        else if (FRISK8_PRE_SPLIT) { preA[idx] = A; preW[idx] = W; } else { pre[idx].A = A; pre[idx].W = W; }
+        else { preA[idx] = A; preW[idx] = W; }
     };
     // (stage 1) one max-mer position more (SIGN = +1) or less (-1): the table's field, or the side counter of a period-4 max-mer
     auto bump = [&](uint32_t c16, auto sign_c) __attribute__((always_inline)) {
@@ -252,9 +220,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     if (P.in_list != nullptr && *P.in_count == 0u) return;
     // (the first scan of a batch queues all three bulk forms behind its sample; the sample's verdict, on the device, picks one)
     if (P.verdict != nullptr && *P.verdict != P.my_form) return;
-#if FRISK8_PRIO
     __builtin_amdgcn_s_setprio(FRISK8_PRIO);
-#endif
     clear_t8();
     clear_small();
     if (tid0 < 2 * FRISK8_SLOTS) misc_base[tid0] = 0;
@@ -329,21 +295,15 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     //  not by the gather: measured 8.80 ms without the ring, 9.06 with it, on the repeat-rich shape; at K = 6, 7 the table is 32 / 128 KB)
     //  ROLE & 2: a launch whose windows do not slide (increment above half a window, or too few windows for chunks): every window
     //  would gather everything and park it for nobody - such launches take the instantiation without the ring.)
-    constexpr bool RING = FRISK8_RING != 0 && KMAX == 8 && BITS == 4 && !(ROLE & 2);
+    constexpr bool RING = KMAX == 8 && BITS == 4 && !(ROLE & 2);
     // (one buffer: a copy of the genome table first, the workgroups' slices behind it - so that "from the table" and "from the
     //  ring" are two 32-bit offsets from one base, and the scoring loop's load is one instruction either way)
     char* const ring = RING ? reinterpret_cast<char*>(P.ig_ring) : nullptr;
-    // (a workgroup's slice: ITS x COLS doubles, then FRISK8_RING_PAD doubles that nobody reads - where the lanes of a parking wave that
-    //  gathered nothing send their store: an unconditional store with a selected address keeps the scoring loop one scheduling region,
-    //  a store under a per-lane condition put a branch behind every position and made the scan 2.6 x slower)
+    // (a workgroup's slice: ITS x COLS doubles, then FRISK8_RING_PAD doubles that nobody touches)
     const uint32_t slice_off = RING ? uint32_t((size_t(NK) + size_t(blockIdx.x) * (size_t(ITS) * FRISK8_RING_COLS + FRISK8_RING_PAD)) * 8) : 0u;
-    const uint32_t dummy_off = slice_off + uint32_t(ITS) * FRISK8_RING_COLS * 8u;
     bool slide_next = false;            // the table is left standing for the next window (which slides); false: it is cleared
     bool ring_next = false;             // ... and so is the ring: the window before this one went through the scoring loop (a window
                                         // that the N filter drops, or that is handed on, parks nothing - its successor gathers afresh)
-#ifdef FRISK_STAMPS
-    int stamp_win = -1;         // (diagnostic builds: STAMP of scan_kernel.h - wave 0 of the first workgroups, s_memtime per stage)
-#endif
 
     // candidate `cand` of the descriptor in `d`: first base, reported coordinates, length (crawlGenome L211-245)
     auto window_of = [&](int64_t cand, int64_t& st, int64_t& rep_start, int64_t& rep_stop, int& n, bool& jump) {
@@ -435,10 +395,6 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             int tid = tid0, kmin = kmin0;
             asm volatile("" : "+v"(tid), "+s"(kmin));
             asm volatile("" : "+s"(Pk));            // (kernel arguments used once per window: re-read from their segment, see Pk)
-#ifdef FRISK_STAMPS
-            ++stamp_win;
-#endif
-            STAMP(0)
             const int lane = tid & 63;
             int64_t st, rep_start, rep_stop;
             int n;
@@ -451,27 +407,20 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             // where the window's first base sits in the ring: row rb_r, column rb_q (uniform)
             const uint32_t ring_base = RING ? uint32_t(uint64_t(st) % uint64_t(ITS * FRISK8_RING_COLS)) : 0u;
             const uint32_t rb_q = ring_base / uint32_t(ITS), rb_r = ring_base - rb_q * uint32_t(ITS);
-            // WHICH positions a lane holds.  Block b = positions [b ITS, (b + 1) ITS) of the window; lane t holds block t.  FRISK8_DEAL = 1
-            // (round 4, measured and NOT taken) deals the blocks to the four waves in groups of sixteen - wave w holds the groups w,
-            // w + 4, w + 8, w + 12 - so that the entering range of a slid window (the lanes that gather from the genome table, a cache
-            // line per lane, and park) is shared by all four waves (9 / 16 / 16 / 10 lanes at w = 5000, inc = 1000) instead of sitting
-            // in wave 3 (57 lanes) with the other three waiting at the loop's barrier.  But then every wave runs the parking copy of
-            // the scoring loop: 6.30-6.35 ms per scan of the bench shard against 6.13-6.17 (stores behind the loop: 6.21-6.31), and
-            // with the store under a per-lane condition - a branch behind every position - 16.1 ms.
-#ifndef FRISK8_DEAL
-#define FRISK8_DEAL 0
-#endif
-            const int blk = (FRISK8_DEAL && NT == 256) ? ((((tid & 63) >> 4) * 4 + (tid >> 6)) * 16 + (tid & 15)) : tid;
+            // WHICH positions a lane holds.  Block b = positions [b ITS, (b + 1) ITS) of the window; lane t holds block t.  Dealing
+            // the blocks to the four waves in groups of sixteen instead (round 4, FRISK8_DEAL at c34d7fb: measured and NOT taken) - wave
+            // w holds the groups w, w + 4, w + 8, w + 12 - shares the entering range of a slid window (the lanes that gather from the
+            // genome table, a cache line per lane, and park) among all four waves (9 / 16 / 16 / 10 lanes at w = 5000, inc = 1000)
+            // instead of leaving it in wave 3 (57 lanes) with the other three waiting at the loop's barrier.  But then every wave runs
+            // the parking copy of the scoring loop: 6.30-6.35 ms per scan of the bench shard against 6.13-6.17 (stores behind the loop,
+            // FRISK8_PARK_LATE: 6.21-6.31), and with the store under a per-lane condition - a branch behind every position - 16.1 ms.
             // byte offset (from the buffer's base) of the ring's place for this lane's it-th position
             // ... split into what is the same for every lane (the row, and the slice: scalar arithmetic, and it becomes part of the load's
-            // scalar base) and the lane's column - one of two values per window, by whether the row index wrapped (`FRISK8_RING_SPLIT`;
-            // round 3 computed row, carry, column, mask, shift and sum on the vector unit for every position: four VALU instructions
-            // of the scoring loop's ~52 per position)
-#ifndef FRISK8_RING_SPLIT
-#define FRISK8_RING_SPLIT 1
-#endif
-            const uint32_t lane_col0 = RING ? (((rb_q + uint32_t(blk)) & (FRISK8_RING_COLS - 1u)) << 3) : 0u;
-            const uint32_t lane_col1 = RING ? (((rb_q + 1u + uint32_t(blk)) & (FRISK8_RING_COLS - 1u)) << 3) : 0u;
+            // scalar base) and the lane's column - one of two values per window, by whether the row index wrapped (round 3 computed
+            // row, carry, column, mask, shift and sum on the vector unit for every position: four VALU instructions of the scoring
+            // loop's ~52 per position; FRISK8_RING_SPLIT at c34d7fb)
+            const uint32_t lane_col0 = RING ? (((rb_q + uint32_t(tid)) & (FRISK8_RING_COLS - 1u)) << 3) : 0u;
+            const uint32_t lane_col1 = RING ? (((rb_q + 1u + uint32_t(tid)) & (FRISK8_RING_COLS - 1u)) << 3) : 0u;
             auto ring_uni = [&](int it) __attribute__((always_inline)) -> uint32_t {        // (uniform) slice + row
                 const uint32_t rr = rb_r + uint32_t(it);
                 const uint32_t cy = rr >= uint32_t(ITS) ? 1u : 0u;
@@ -480,16 +429,12 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             auto ring_lane = [&](int it) __attribute__((always_inline)) -> uint32_t {       // the lane's column, in bytes
                 return (rb_r + uint32_t(it) >= uint32_t(ITS)) ? lane_col1 : lane_col0;
             };
-            auto ring_mine = [&](int it) __attribute__((always_inline)) -> uint32_t {
-                if (FRISK8_RING_SPLIT) return ring_uni(it) + ring_lane(it);
-                const uint32_t rr = rb_r + uint32_t(it);                         // (uniform: the row, and whether it wraps into the next column)
-                const uint32_t cy = rr >= uint32_t(ITS) ? 1u : 0u;
-                return slice_off + ((((rr - cy * uint32_t(ITS)) * FRISK8_RING_COLS) + ((rb_q + cy + uint32_t(blk)) & (FRISK8_RING_COLS - 1u))) << 3);
-            };
+            // (the sum of the two, as a call of its own: written out in fetch() it moved one kernel's register allocation)
+            auto ring_mine = [&](int it) __attribute__((always_inline)) -> uint32_t { return ring_uni(it) + ring_lane(it); };
             const bool sliding = slide_next;
             // this lane gathers its positions' genome-side values from the table (and parks them in the ring): every lane of a
             // window counted afresh, the lanes that hold a position of the entering range in a window slid into
-            const bool lane_new = !sliding || !ring_next || blk * ITS + (ITS - 1) >= P.w - (K - 1) - P.inc;
+            const bool lane_new = !sliding || !ring_next || tid * ITS + (ITS - 1) >= P.w - (K - 1) - P.inc;
             ring_next = false;                                  // (true again where this window's scoring loop has run)
             slide_next = slide_pp > 0 && ci + 1 < ce && d.kind == 0 && !jump && cand + 1 < d.cand0 + d.ncand &&
                          st + int64_t(P.inc) + P.w <= d.size;
@@ -505,7 +450,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             parity ^= 1u;
 
             // ---- stage 1: one pass over the window's positions (a lane owns ITS consecutive ones) -----------
-            const int j0 = blk * ITS;
+            const int j0 = tid * ITS;
             const int64_t gl = g0 + (j0 < n ? j0 : 0);                       // clamped: loads are unconditional
             const int64_t wi = gl >> 4, mi = gl >> 5;
             const int shc = 32 - int(gl & 15) * 2, shm = 32 - int(gl & 31);
@@ -675,9 +620,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     if (nvalid) atomicAdd(&misc[M_NVALID], nvalid);
                 }
             }
-            STAMP(1)
             __syncthreads();
-            STAMP(2)
             if (tid < FRISK8_SLOTS) misc_other[tid] = 0;        // the previous window's counters: nobody reads them now
 
             // ---- stage 2: C_5[q] = D_5[q] + (sum of the 64 order-8 counters below q); grand total for the overflow check
@@ -710,7 +653,6 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                 if (lane == 0 && tot) atomicAdd(&misc[M8_TSUM], tot);
                 __syncthreads();
             }
-            STAMP(3)
             // The orders below follow inside a wave, no LDS round trip between the levels.  LVL >= 4 (K = 7, 8): as part of
             // stage 3, where thread t holds the 4-mer t anyway.  LVL = 3 (K = 6): here - one wave, lane l = the 3-mer l.
             if constexpr (LVL == 3) {
@@ -729,7 +671,6 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                 }
                 __syncthreads();
             }
-            STAMP(4)
 
             auto uni = [](uint32_t x) -> uint32_t { return __builtin_amdgcn_readfirstlane(x); };
             const uint32_t upAll = uni(misc[M_UPA]), upGC = uni(misc[M_UPG]);
@@ -821,7 +762,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     f.Ig = 1.0;
                     if (mode) {
                         f.roff = ring_mine(it);
-                        if (FRISK8_RING_SPLIT && mode == 1)      // every lane reads the ring: scalar base (slice + row) + the lane's column
+                        if (mode == 1)      // every lane reads the ring: scalar base (slice + row) + the lane's column
                             f.Ig = *reinterpret_cast<const double*>((ring + ring_uni(it)) + ring_lane(it));
                         else
                             f.Ig = *reinterpret_cast<const double*>(ring + ((mode == 2 && lane_new) ? (c16 << 3) : f.roff));
@@ -835,22 +776,12 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     f.w6 = *reinterpret_cast<const uint4*>(t8b + (c16 & ~15u));
                 } else {                // the sixteen nibbles of the 6-mer c >> 4 are the 8 bytes at 8 (c >> 4)
                     f.c8 = 0;
-#if FRISK8_W7_READ
-                    f.w7 = *reinterpret_cast<const uint16_t*>(t8b + ((c16 >> 2) << 1));        // the 7-mer's four nibbles, read on their own
-#else
                     f.w7 = 0;
-#endif
                     const uint2 x = *reinterpret_cast<const uint2*>(t8b + ((c16 >> 4) << 3));
                     f.w6 = make_uint4(x.x, x.y, 0u, 0u);
                 }
-                if (FRISK8_PRE_SPLIT) {
-                    f.W5 = *reinterpret_cast<const uint32_t*>(lds + L::pre + NL * 8 + ((c16 >> 6) << 2));
-                    f.A5 = *reinterpret_cast<const double*>(lds + L::pre + ((c16 >> 6) << 3));
-                } else {
-                    const Pre8* e = reinterpret_cast<const Pre8*>(lds + L::pre + __umul24(c16 >> 6, 12u));     // (one v_mul_u32_u24)
-                    f.W5 = e->W;
-                    f.A5 = e->A;
-                }
+                f.W5 = *reinterpret_cast<const uint32_t*>(lds + L::pre + NL * 8 + ((c16 >> 6) << 2));
+                f.A5 = *reinterpret_cast<const double*>(lds + L::pre + ((c16 >> 6) << 3));
                 return f;
             };
             // counts of the three top orders of the max-mer c16 as the order-K table holds them: without the orphans
@@ -861,13 +792,9 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     c7 = __builtin_amdgcn_sad_u8(f.w7, 0u, 0u);
                     c6 = __builtin_amdgcn_sad_u8(f.w6.x, 0u, __builtin_amdgcn_sad_u8(f.w6.y, 0u, __builtin_amdgcn_sad_u8(f.w6.z, 0u, __builtin_amdgcn_sad_u8(f.w6.w, 0u, 0u))));
                 } else {
-#if FRISK8_W7_READ
-                    const uint32_t w7 = f.w7;
-#else
                     // the 7-mer's four nibbles are 16 of the 64 bits already here: one 64-bit shift instead of an LDS read of its own
-                    // (the dot product's 0x1111 ignores what the shift leaves above them)
+                    // (round 2's form, FRISK8_W7_READ at c34d7fb; the dot product's 0x1111 ignores what the shift leaves above them)
                     const uint32_t w7 = uint32_t(((uint64_t(f.w6.y) << 32) | f.w6.x) >> ((c16 & 12u) << 2));
-#endif
                     // (SIDE: the period-4 max-mer below the code's (K-2)-mer / (K-1)-mer / the code itself, where there is one)
                     uint32_t s6 = 0u, s7 = 0u, s8 = 0u;
                     if constexpr (SIDE) {
@@ -1105,17 +1032,10 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                         } else {
                             auto lo = [](double x) -> uint32_t { return uint32_t(__double2loint(x)); };
                             auto hi = [](double x) -> uint32_t { return uint32_t(__double2hiint(x)); };
-                            if (FRISK8_PRE_SPLIT) {
-                                uint4* oa = reinterpret_cast<uint4*>(preA + 4 * q4);
-                                oa[0] = make_uint4(lo(A5[0]), hi(A5[0]), lo(A5[1]), hi(A5[1]));
-                                oa[1] = make_uint4(lo(A5[2]), hi(A5[2]), lo(A5[3]), hi(A5[3]));
-                                *reinterpret_cast<uint4*>(preW + 4 * q4) = make_uint4(W5[0], W5[1], W5[2], W5[3]);
-                            } else {
-                            uint4* out = reinterpret_cast<uint4*>(pre + 4 * q4);        // four entries = 48 bytes, 16-byte aligned
-                            out[0] = make_uint4(lo(A5[0]), hi(A5[0]), W5[0], lo(A5[1]));
-                            out[1] = make_uint4(hi(A5[1]), W5[1], lo(A5[2]), hi(A5[2]));
-                            out[2] = make_uint4(W5[2], lo(A5[3]), hi(A5[3]), W5[3]);
-                            }
+                            uint4* oa = reinterpret_cast<uint4*>(preA + 4 * q4);
+                            oa[0] = make_uint4(lo(A5[0]), hi(A5[0]), lo(A5[1]), hi(A5[1]));
+                            oa[1] = make_uint4(lo(A5[2]), hi(A5[2]), lo(A5[3]), hi(A5[3]));
+                            *reinterpret_cast<uint4*>(preW + 4 * q4) = make_uint4(W5[0], W5[1], W5[2], W5[3]);
                         }
                     }
                     }
@@ -1138,7 +1058,6 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                 }
             }
             __syncthreads();
-            STAMP(5)
             const uint32_t pmask_raw = PLACE ? uni(misc[M8_PMASK]) : 0u;
             const uint32_t placed = pmask_raw & 0x7FFFFFFFu;                        // entries of the orphan list that went into the table
             if constexpr (PLACE) {
@@ -1197,12 +1116,10 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             //      Sw = sum Iw/c8,  Sg = sum Ig/c8,  T = sum Iw ln(Iw/Ig)/c8  over POSITIONS (= sums over distinct max-mers)
             const double r6 = r_of(K - 2), r7 = r_of(K - 1), r8 = r_of(K);      // (named for K = 8: the three orders above the prefix)
             double sw = 0.0, sg = 0.0, stt = 0.0;
-#if FRISK8_PRIO
             // The long scoring loop yields issue slots to the short stages of the other workgroups' windows: those are chains of
             // dependent steps between barriers, where a lost slot delays four waves, while a scoring wave has work for every slot
             // it gets.  Measured +3..4 % (all short stages high, scoring low; raising only some of them: less).
             __builtin_amdgcn_s_setprio(0);
-#endif
             // (a << SH) + b in one instruction (the compiler's own choice for the weight below is two shifts, a shift-add and an add3)
             auto shl_add = [](uint32_t a, auto sh, uint32_t b) __attribute__((always_inline)) -> uint32_t {
                 uint32_t r;
@@ -1265,30 +1182,19 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             //   K = 8 (LDS allows 3 / 2 workgroups per CU): unrolled, groups of 2: 44.8 / 36.2; rolled, groups of 1: 43.2 / 35.6
             //   K = 6, 7 (tables of 4 / 16 KiB: registers bound the occupancy): unrolled at 3 per CU spills (26 / 24); rolled,
             //   groups of 1, needs 89..92 registers, so FOUR workgroups share a CU: 50.2 / 45.3 (16-bit form: 31.0 / 26.0)
-#ifdef FRISK8_S4_GROUP
-            constexpr int GR = FRISK8_S4_GROUP;
-#else
             constexpr int GR = (K == 8 && BITS == 4 && !SIDE) ? 2 : 1;       // (8-bit form at K = 8: groups of one are 2..3 % ahead; SIDE: registers)
-#endif
-#ifdef FRISK8_ROLLED
-            constexpr bool ROLLED = FRISK8_ROLLED != 0;
-#else
             constexpr bool ROLLED = K < 8 || NT > 256;
-#endif
             // ALLON: every lane of this wave starts a max-mer at every one of its positions (three waves in four of a window
             // without invalid bases) - no stand-in code to select, no weight to mask
             // (PARK: this wave has lanes that gather from the table - it parks what it used in the ring for the windows to come; a
             //  wave whose lanes all read the ring has nothing new to park, and its loop carries neither the select nor the store.
             //  Stores cost more than they look in this loop: loads and stores return in order on one counter, so every load behind a
-            //  store waits for the store's acknowledgement - measured 1.1 ms per scan with every wave parking)
+            //  store waits for the store's acknowledgement - measured 1.1 ms per scan with every wave parking; storing behind the
+            //  unrolled loop instead of inside it, FRISK8_PARK_LATE at c34d7fb: +-0)
             auto score_all = [&](auto allon_c, auto orph_c, auto park_c) __attribute__((always_inline)) {
                 constexpr bool ALLON = decltype(allon_c)::value;
                 constexpr bool PARK = RING && decltype(park_c)::value;
                 constexpr int FMODE = PARK ? 2 : 1;
-                // the unrolled loop parks behind itself: a store in front of a load holds that load's data back until the store is
-                // acknowledged (one in-order counter), and this wave - the one that gathers - is the one the others wait for
-                constexpr bool PARK_LATE = PARK && FRISK8_PARK_LATE && !(ROLLED_K && ITS % (2 * GR) == 0);
-                double parked[PARK_LATE ? ITS : 1];
                 constexpr int ORPH = decltype(orph_c)::value;           // the orphan list holds <= 2 entries (one (K-1)-mer at most) / <= 4 / any number: 2 / 4 / 0
                 auto on_at = [&](int it) -> bool { return ALLON || ((fm4 >> (31 - it)) & 1u); };
                 auto code4_at = [&](int it) -> uint32_t {      // the position's max-mer, or the stand-in where it starts none
@@ -1323,11 +1229,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     for (int k = 0; k < GR; ++k) {
                         if (!CHECK || g + k < ITS) {
                             // (the value this position used, into the ring for the windows to come: 1.0 where it starts no max-mer)
-                            if constexpr (PARK) {
-                                const double v = on_at(g + k) ? f[k].Ig : 1.0;
-                                if constexpr (PARK_LATE) parked[g + k] = v;      // (unrolled form: stored behind the loop)
-                                else *reinterpret_cast<double*>(ring + ((!FRISK8_DEAL || lane_new) ? f[k].roff : dummy_off)) = v;   // (DEAL: the lanes that gathered park; the others' values are there)
-                            }
+                            if constexpr (PARK) *reinterpret_cast<double*>(ring + f[k].roff) = on_at(g + k) ? f[k].Ig : 1.0;
                             score_one(f[k], c8[k], c7[k], c6[k], on_at(g + k) ? c8[k] : 0u, on_at(g + k));
                         }
                     }
@@ -1365,10 +1267,6 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     score_group(buf[cur], g, std::true_type{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if constexpr (PARK_LATE) {
-#pragma unroll
-                    for (int it = 0; it < ITS; ++it) *reinterpret_cast<double*>(ring + ((!FRISK8_DEAL || lane_new) ? ring_mine(it) : dummy_off)) = parked[it];
-                }
             };
             constexpr uint32_t ALL_MINE = uint32_t(0xFFFFFFFF00000000ull >> ITS);
             using orphX = std::integral_constant<int, -1>;                          // no orphan on the list: no compares at all
@@ -1393,14 +1291,10 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             }
 
             // workgroup totals in a fixed order: DPP butterfly per wave, then the NW partials in wave order
-#if FRISK8_PRIO
             __builtin_amdgcn_s_setprio(FRISK8_PRIO);
-#endif
-            STAMP(6)
             sw = wave_sum_exact(sw); sg = wave_sum_exact(sg); stt = wave_sum_exact(stt);
             if (lane == 0) { double* p = scratch + (tid >> 6) * 3; p[0] = sw; p[1] = sg; p[2] = stt; }
             __syncthreads();
-            STAMP(7)
             // behind the barrier: nobody reads the tables any more.  The whole order-K table in 16-byte stores (8 / 16 per thread at
             // K = 8) is cheaper than every position clearing its own dword (20 tests, extracts and masked 4-byte stores per lane)
             ring_next = true;
@@ -1422,9 +1316,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                 Pk->sg[row] = b;
                 Pk->kld[row] = c;                             // T; finish_rows_kernel turns (T, Sw, Sg) into the KLD
             }
-            STAMP(8)
             __syncthreads();
-            STAMP(9)
         }
     }
 }

@@ -74,7 +74,7 @@ struct ScanParams {
     uint32_t* dbg_counts;
     int64_t* dbg_meta;
     double* dbg_ivom;             // debug, kmax <= 6: row x 2 x 4^kmax - un-normalised window-side and genome-side IVOM per max-mer
-    unsigned long long* stamps;   // -DFRISK_STAMPS builds only: s_memtime at the stage boundaries of the first workgroups
+    unsigned long long* unused_stamps;  // always nullptr: kept so that the kernel-argument offsets of the fields below stay put
     // scan8_kernel.h (narrow order-8 counters): windows whose counters wrap are handed to the next wider form through
     // device-side lists of candidate indices
     const double* rc_tab;         // 1/c for c = 0..255 (entry 0 = 0): the weight of one of the c positions that share a max-mer
@@ -98,39 +98,6 @@ struct ScanParams {
 #define ROW_NO_MAXMER 8u
 
 #pragma clang fp contract(off)
-
-// Diagnostic builds only (-DFRISK_STAMPS): wave FRISK_STAMP_WAVE (0) of the first 4 workgroups records s_memtime at up to 12 points of its first
-// 16 windows; the launcher prints the per-stage cycle differences.  Never in the product library.
-#ifdef FRISK_STAMPS
-#ifndef FRISK_STAMP_WAVE
-#define FRISK_STAMP_WAVE 0
-#endif
-#define STAMP(i)                                                                                          \
-    if (tid == 64 * FRISK_STAMP_WAVE && blockIdx.x < 4 && stamp_win < 16)                                 \
-        P.stamps[(blockIdx.x * 16 + stamp_win) * 12 + (i)] = __builtin_amdgcn_s_memtime();
-#else
-#define STAMP(i)
-#endif
-
-#ifndef FRISK_ABL
-#define FRISK_ABL 0       // diagnostic builds (tools/ablate.py): drop one ingredient at a time; results wrong by design
-#endif
-
-// Diagnostic builds only (tools/ablate.py, -DFRISK_STOP=<n>): finish every window right after stage <n> with a
-// value that depends on the stage's results, to time the stages cumulatively.  Never in the product library.
-#ifdef FRISK_STOP
-#define STOP_AFTER(stage, value)                                                              \
-    if (FRISK_STOP == (stage)) {                                                              \
-        const double v_ = double(value);                                                      \
-        __syncthreads();                                                                      \
-        cleanup();                                                                            \
-        if (tid == 0) { P.status[row] = ROW_KEPT; P.kld[row] = v_; P.gc[row] = 0.5; }         \
-        __syncthreads();                                                                      \
-        continue;                                                                             \
-    }
-#else
-#define STOP_AFTER(stage, value)
-#endif
 
 // LDS carve-up (dynamic, all offsets multiples of 16 bytes)
 struct LdsLayout {
@@ -318,10 +285,6 @@ __device__ inline double div_exact(double n, double d) {
     double r = __builtin_amdgcn_rcp(d);
     double e = __builtin_fma(-d, r, 1.0);
     r = __builtin_fma(r, e, r);
-#ifdef FRISK_DIV_2NR
-    e = __builtin_fma(-d, r, 1.0);
-    r = __builtin_fma(r, e, r);
-#endif
     const double q = n * r;
     e = __builtin_fma(-d, q, n);
     return __builtin_fma(e, r, q);
@@ -426,9 +389,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
     d.cand0 = 0; d.ncand = 0; d.off = 0; d.size = 0; d.kind = 0; d.base0 = 0; d.j0 = 0;
     int dsi = -1;
     uint32_t parity = 0;
-#ifdef FRISK_STAMPS
-    int stamp_win = -1;
-#endif
 
     for (int64_t q = v; q < nchunks; q += G) {
         const int64_t cb = listed ? q : P.c0 + q * chunk;
@@ -447,9 +407,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                 d = P.descs[lo];
                 dsi = lo;
             }
-#ifdef FRISK_STAMPS
-            ++stamp_win;
-#endif
             const int64_t j = cand - d.cand0 + d.j0;           // window index inside the scaffold
             int64_t st;                // 0-based first base of the window inside the scaffold
             int64_t rep_start, rep_stop;   // coordinates as the reference reports them
@@ -472,7 +429,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
             }
             const int64_t g0 = d.off + (st - d.base0);            // resident position of the window's first base
             const int64_t row = cand - P.c0;
-            STAMP(0)
             uint32_t* misc = misc_base + parity * FRISK_MISC_SLOTS;         // this window's counters
             uint32_t* misc_other = misc_base + (parity ^ 1u) * FRISK_MISC_SLOTS;
             parity ^= 1u;
@@ -535,20 +491,12 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                     const int64_t gl = g0 + (j0 < n ? j0 : 0);               // clamped: loads are unconditional
                     const int64_t wi = gl >> 4, mi = gl >> 5;
                     const int shc = 32 - int(gl & 15) * 2, shm = 32 - int(gl & 31);
-#if defined(FRISK_ABL) && (FRISK_ABL & 32)      // diagnostic: no window loads at all (fake bases, all valid)
-                    const uint32_t w0 = uint32_t(wi) * 2654435761u, w1 = w0 ^ 0x9E3779B9u, w2 = w1 * 40503u;
-#else
                     const uint32_t w0 = P.codes[wi], w1 = P.codes[wi + 1], w2 = P.codes[wi + 2];
-#endif
                     const uint32_t hi = uint32_t(((uint64_t(w0) << 32) | w1) >> shc);
                     const uint32_t lo = uint32_t(((uint64_t(w1) << 32) | w2) >> shc);
                     const uint64_t acode = (uint64_t(hi) << 32) | lo;        // bases j0 .. j0+31, first base in the top bits
-#if defined(FRISK_ABL) && (FRISK_ABL & 32)
-                    const uint32_t ainv = 0u, alow = uint32_t(mi >> 40) + uint32_t(shm >> 8);
-#else
                     const uint32_t ainv = uint32_t(((uint64_t(P.inv[mi]) << 32) | P.inv[mi + 1]) >> shm);
                     const uint32_t alow = uint32_t(((uint64_t(P.low[mi]) << 32) | P.low[mi + 1]) >> shm);
-#endif
                     auto topbits = [](int k) -> uint32_t {                  // the k most significant bits (k clamped to 0..32)
                         k = k < 0 ? 0 : (k > 32 ? 32 : k);
                         return uint32_t(0xFFFFFFFF00000000ull >> k);
@@ -635,9 +583,7 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                     if (nvalid) atomicAdd(&misc[M_NVALID], nvalid);
                 }
             }
-            STAMP(1)
             __syncthreads();
-            STAMP(2)
             if (tid < FRISK_MISC_SLOTS) misc_other[tid] = 0;        // the previous window's counters: nobody reads them now
             auto code16_at = [&](int it) -> uint32_t {
                 if (ITS > 0) return c16v[it];
@@ -655,7 +601,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                     reinterpret_cast<uint4*>(small32)[i] = make_uint4(0, 0, 0, 0);
             };
             auto cleanup = [&]() { zero_own_bins(); clear_small(); };
-            STOP_AFTER(0, misc[M_NVALID])
 
             // ---- stage 2: marginalise the small tables: C_x[q] = D_x[q] + sum_b C_{x+1}[4q+b] --------------
             auto marg_level = [&](int x, int first, int step) {
@@ -718,10 +663,8 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                 }
             } else {
                 int x = ks - 1;
-#ifndef FRISK_MARG_WIDE
-#define FRISK_MARG_WIDE 3
-#endif
-                for (; x >= kmin && x > FRISK_MARG_WIDE; --x) { // wide levels: all waves, one barrier each
+                constexpr int MARG_WIDE = 3;                    // the highest level of <= 64 bins
+                for (; x >= kmin && x > MARG_WIDE; --x) {       // wide levels: all waves, one barrier each
                     marg_level(x, tid, NT);
                     __syncthreads();
                 }
@@ -736,7 +679,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                     __syncthreads();
                 }
             }
-            STAMP(3)
             // window-uniform values read back from LDS are moved to scalar registers: they stay live to the end of the
             // window and must not cost a vector register (nor depend on which lanes a later loop leaves active)
             auto uni = [](uint32_t v) -> uint32_t { return __builtin_amdgcn_readfirstlane(v); };
@@ -767,9 +709,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                 __syncthreads();
                 continue;
             }
-            STOP_AFTER(1, small16[tid & 3] + nvalid_top)
-
-            STOP_AFTER(2, small16[tid & 3] + nvalid_top)
 
             WinTables<K8> T;
             T.t8_16 = reinterpret_cast<const uint16_t*>(t8);
@@ -826,10 +765,7 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                     pre_w[c] = W;                   // < 65536 * 4^6
                 }
             }
-            STAMP(4)
             __syncthreads();
-            STAMP(5)
-            STOP_AFTER(3, lv ? pre_i[tid & 1023] : rtab[1])
 
             if (DEBUG && P.dbg_counts) {
                 uint32_t* out = P.dbg_counts + row * int64_t(P.nprof);
@@ -924,17 +860,11 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
             };
             // one max-mer: genome side gathered, window side from the tables, three exact additions
             auto score_one = [&](const auto& Tm, uint32_t code, bool rep, auto plain_c, auto lv_c) __attribute__((always_inline)) {
-#ifndef FRISK_ABL
-#define FRISK_ABL 0
-#endif
-                // (FRISK_ABL: diagnostic builds that drop one ingredient at a time - tools/ablate.py; results wrong by design)
-                const double Ig = (FRISK_ABL & 8) ? 1e-3 + 1e-9 * double(code) : P.ig[code];   // unconditional gather (code < 4^K always)
+                const double Ig = P.ig[code];                   // unconditional gather (code < 4^K always)
                 // Iw = A/W and Iw/Ig with ONE division: ratio = A / (W * Ig), Iw = ratio * Ig
                 double A;
-                double Wd;
-                if (FRISK_ABL & 16) { A = 1e-4 * double(code & 1023u); Wd = double(code | 1u); }
-                else Wd = window_ivom(Tm, code, plain_c, lv_c, A);
-                const double ratio = (FRISK_ABL & 2) ? A * (Wd * Ig) : div_exact(A, Wd * Ig);
+                const double Wd = window_ivom(Tm, code, plain_c, lv_c, A);
+                const double ratio = div_exact(A, Wd * Ig);
                 const double Iw = ratio * Ig;
                 if (DEBUG && P.dbg_ivom && rep) {       // IvomBuild's per-max-mer values before normalisation (L442-450)
                     double* o = P.dbg_ivom + (row * 2) * (int64_t(1) << (2 * kmax));
@@ -942,18 +872,10 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                     o[(int64_t(1) << (2 * kmax)) + code] = Ig;
                 }
                 // Iw ln(Iw/Ig): the log of the RATIO (|ln| ~ 1) keeps the absolute error of T at the 1e-16 level
-#ifdef FRISK_LOG_FDLIBM
-                const double t = Iw * log_pos(ratio);
-#else
-                const double t = (FRISK_ABL & 1) ? Iw * ratio : Iw * log_tab_pos(ratio, logtab);
-#endif
-                if (FRISK_ABL & 4) {
-                    accw.hi += only_rep(rep, Iw); accg.hi += only_rep(rep, Ig); acct.hi += only_rep(rep, t);
-                } else {
-                    exact_add(accw, only_rep(rep, Iw));
-                    exact_add(accg, only_rep(rep, Ig));
-                    exact_add(acct, only_rep(rep, t));
-                }
+                const double t = Iw * log_tab_pos(ratio, logtab);
+                exact_add(accw, only_rep(rep, Iw));
+                exact_add(accg, only_rep(rep, Ig));
+                exact_add(acct, only_rep(rep, t));
             };
             // window-uniform decisions resolved OUTSIDE the scoring loops: bound on the orphan list, shared prefix in use
             using orph1 = std::integral_constant<int, 1>;
@@ -978,27 +900,16 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                         const bool rep = (repmask >> it) & 1ull;
                         if (ITS == 0 && !rep) continue;
                         score_one(T, code16_at(it) >> kshift, rep, plain_c, lv_c);
-#ifndef FRISK_S4_GROUP
-#define FRISK_S4_GROUP 2
-#endif
-                        // interleave at most FRISK_S4_GROUP positions: more overlap needs more live registers than the
+                        // interleave at most S4_GROUP positions: more overlap needs more live registers than the
                         // 128 a 1024-thread workgroup leaves per lane, and the scheduler would spill
-                        if ((it % FRISK_S4_GROUP) == FRISK_S4_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+                        constexpr int S4_GROUP = 2;
+                        if ((it % S4_GROUP) == S4_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
                     }
                 });
-            STAMP(6)
             exact_end(accw); exact_end(accg); exact_end(acct);
-#ifdef FRISK_STOP
-            block_sum3<NW>(accw, accg, acct, scratch_base, tid);
-#else
             block_sum3<NW, true>(accw, accg, acct, scratch_base, tid);
-#endif
-            STAMP(7)
             zero_own_bins();                                // behind the barrier: nobody reads the max-mer table any more
             clear_small();                                  // all reads of the small tables are behind the barrier
-#ifdef FRISK_STOP
-            { const double Sw = exact_value(accw), Sg = exact_value(accg), Tt = exact_value(acct); STOP_AFTER(4, Sw + Sg + Tt) }
-#endif
             // the scalar tail of the row - two logarithms and a division, ~2 000 cycles of dependent instructions that every
             // other wave would wait for at the window's last barrier - is left to finish_rows_kernel (all rows in parallel)
             if (tid == 0) {
@@ -1007,9 +918,7 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void scan_kernel(const Sca
                 P.sw[row] = exact_value(accw);
                 P.sg[row] = exact_value(accg);
             }
-            STAMP(8)
             __syncthreads();
-            STAMP(9)
         }
     }
 }

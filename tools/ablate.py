@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Kernel experiments: build variants of libfrisk_hip.so with -DFRISK_ABL=<mask> (the ingredient mask scan_kernel.h tests; or other -D flags) and time
-the scan / profile kernels of each on one synthetic shard.  Results of ablated builds are WRONG by design; only
-the timings mean anything.  Usage (on the GPU box): python tools/ablate.py 0 1 2 4 8 15"""
+"""Kernel experiments: build variants of libfrisk_hip.so, one per argument - a comma-separated list of -D flags - and time
+the scan / profile kernels of each on one synthetic shard.  Usage (on the GPU box): python tools/ablate.py FRISK_TUNE NAME=VALUE,FRISK_TUNE ...
+(tools/exp/ab.sh runs it on the whole shard; tools/exp/width_sweep.sh sweeps FRISK_K8_BITS with a FRISK_TUNE build)."""
 import os
 import subprocess
 import sys
@@ -31,7 +31,7 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     scale = float(os.environ.get("ABLATE_SCALE", "0.25"))
     for spec in sys.argv[1:]:
-        defs = ["-DFRISK_ABL=" + spec, "-DFRISK_TUNE", "-DFRISK_K8_WIDTH=16"] if spec.isdigit() else ["-D" + d for d in spec.split(",")]
+        defs = ["-D" + d for d in spec.split(",")]
         lib = os.path.join(OUT, "lib_%s.so" % spec.replace(",", "_").replace("=", ""))
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC",
                         "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", lib,
@@ -39,10 +39,6 @@ def main():
         env = dict(os.environ, FRISK_HIP_LIB=lib)
         out = subprocess.run([sys.executable, "-c", CHILD % (ROOT, scale, CHILD_K, float(os.environ.get("ABLATE_LOWER", "0")), float(os.environ.get("ABLATE_REPEATS", "0")))], env=env, capture_output=True, text=True)
         print(spec, out.stdout.strip().splitlines()[-1] if out.stdout.strip() else out.stderr[-500:], flush=True)
-        for line in out.stderr.splitlines():
-            if line.startswith("[stamps]"):
-                print("   ", line, flush=True)
-                break
 
 
 if __name__ == "__main__":
