@@ -1971,8 +1971,17 @@ int frisk_scan_ivom(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_
     for (int64_t r = 0; r < n; ++r) {           // normalise over the window's present max-mers (L450-454), in index order
         const double* iw = raw.data() + size_t(r) * 2 * nk;
         const double* ig = iw + nk;
-        double sw = 0.0, sg = 0.0;
-        for (size_t k = 0; k < nk; ++k) { sw += iw[k]; sg += ig[k]; }
+        // compensated (Neumaier) sums: a plain running sum over a window's ~10^3 max-mers loses up to that many ulps of Sw, Sg,
+        // which shifts every normalised entry alike (measured: 87 ulps at K = 6); the scan kernels sum these exactly
+        double sw = 0.0, sg = 0.0, cw = 0.0, cg = 0.0;
+        auto add = [](double& s, double& comp, double v) {
+            const double t = s + v;
+            comp += std::fabs(s) >= std::fabs(v) ? (s - t) + v : (v - t) + s;
+            s = t;
+        };
+        for (size_t k = 0; k < nk; ++k) { add(sw, cw, iw[k]); add(sg, cg, ig[k]); }
+        sw += cw;
+        sg += cg;
         for (size_t k = 0; k < nk; ++k) {
             window_ivom[size_t(r) * nk + k] = iw[k] != 0.0 ? iw[k] / sw : 0.0;
             genome_ivom[size_t(r) * nk + k] = iw[k] != 0.0 ? ig[k] / sg : 0.0;

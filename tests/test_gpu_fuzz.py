@@ -8,36 +8,9 @@ from frisk_amd import _ffi
 from frisk_amd.engine import Engine
 from oracle import frisk_oracle_c as OC
 
+from fuzz_cases import random_case as _random_case
+
 pytestmark = pytest.mark.gpu
-
-
-def _random_case(rng, kmax_hi=8):
-    kmax = int(rng.integers(1, kmax_hi + 1))
-    kmin = int(rng.integers(1, kmax + 1))
-    w = int(rng.choice([37, 64, 100, 333, 512, 1000, 2048, 2049, 5000, 5121, 8192, 8193, 12000, 66000]))
-    inc = max(1, int(w * rng.choice([0.05, 0.2, 0.5, 0.9, 1.0, 1.6])))
-    seqs = []
-    for _ in range(int(rng.integers(1, 6))):
-        n = int(rng.choice([0, 5, w // 2, w, w + 1, 2 * w + 3, 3 * w, 7 * w + int(rng.integers(0, w))]))
-        p = rng.dirichlet([2, 2, 2, 2])
-        s = rng.choice(np.frombuffer(b"ATGC", dtype=np.uint8), size=n, p=p)
-        for _ in range(int(rng.integers(0, 6))):
-            if n == 0:
-                break
-            a = int(rng.integers(0, n))
-            ln = int(rng.choice([1, 2, 7, 8, 9, 40, w // 3 + 1]))
-            kind = rng.integers(0, 4)
-            if kind == 0:
-                s[a:a + ln] = ord("N")
-            elif kind == 1:
-                s[a:a + ln] |= 0x20                           # soft-masked
-            elif kind == 2:
-                s[a:a + ln] = rng.choice(np.frombuffer(b"RYKMnrx-*", dtype=np.uint8), size=len(s[a:a + ln]))
-            else:
-                s[a:a + ln] = s[a] if a < n else ord("A")      # a low-complexity run (big counts)
-        seqs.append(s.tobytes())
-    return dict(kmin=kmin, kmax=kmax, w=w, inc=inc, seqs=seqs, mask_host=bool(rng.integers(0, 2)),
-                scaffolds_all=bool(rng.integers(0, 2)), rip=bool(rng.integers(0, 2)) and kmin <= 2 <= kmax)
 
 
 @pytest.mark.parametrize("block", range(16))
