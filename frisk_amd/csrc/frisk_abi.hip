@@ -193,15 +193,26 @@ int grid_for(int64_t items, int per_block, int max_blocks) {
     return int(b);
 }
 
-// layout of a batch in padded coordinates (frisk_device.h): scaffold s at [off, off+len), then at least one PAD
+int settle_stream(frisk_ctx* c);
+
+// layout of a batch in padded coordinates (frisk_device.h): scaffold s at [off, off+len), then at least one PAD.  The arguments are
+// checked before B is touched: a refused load or stage leaves the batch in the slot as it was.
 int layout_batch(frisk_ctx* c, frisk_ctx::Batch& B, const int64_t* lens, int32_t n_seq) {
     if (n_seq < 0) return fail(c, FRISK_E_ARG, "n_seq < 0");
+    for (int32_t s = 0; s < n_seq; ++s)
+        if (lens[s] < 0) return fail(c, FRISK_E_ARG, "negative scaffold length");
+    // The loaders refill the RESIDENT slot on the compute stream: the pieces of a streamed upload into it may still be in flight on
+    // the copy stream, so the compute stream waits for the last one (on the device) before anything writes the slot.  The stage
+    // forms fill the other slot on the copy stream, which is ordered behind its own pieces already.
+    if (&B == &c->b()) {
+        const int rc = settle_stream(c);
+        if (rc) return rc;
+    }
     B.seq_off.assign(size_t(n_seq), 0);
     B.seq_len.assign(lens, lens + n_seq);
     B.seq_name.assign(size_t(n_seq), std::string());
     int64_t pos = 0;
     for (int32_t s = 0; s < n_seq; ++s) {
-        if (lens[s] < 0) return fail(c, FRISK_E_ARG, "negative scaffold length");
         B.seq_off[size_t(s)] = pos;
         pos += lens[s] + 1;                       // at least one PAD position after every scaffold
     }
@@ -212,7 +223,7 @@ int layout_batch(frisk_ctx* c, frisk_ctx::Batch& B, const int64_t* lens, int32_t
     B.width_hint = 0;
     B.tiled = false;
     B.tiles.clear(); B.g_name.clear(); B.g_len.clear();
-    B.streaming = false;        // (piece_end is kept: frisk_seq_stage_2bit looks at the slot's previous upload)
+    B.streaming = false;        // (piece_end is kept: frisk_seq_stage_2bit looks at the slot's previous upload; the resident slot was settled above)
     if (B.have_host2) {
         B.have_host2 = false;
         decltype(B.h_codes)().swap(B.h_codes);
@@ -1238,20 +1249,24 @@ int frisk_profile_reset(frisk_ctx* c) {
     return FRISK_OK;
 }
 
-static int profile_add_range(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1, bool first = true, bool last = true);
+static int profile_add_range(frisk_ctx* c, int mask_host, bool one_pass, int64_t p0, int64_t p1, bool first = true, bool last = true);
 
 int frisk_profile_add(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1) {
     if (!c) return FRISK_E_ARG;
+    // the flags split before any branch: every form below is handed --maskHost (bit 0) alone, the one-pass hook on its own
+    const bool one_pass = (mask_host & FRISK_PROFILE_ONE_PASS) != 0;
+    mask_host &= 1;
     if (!c->b().have_seq) return fail(c, FRISK_E_STATE, "frisk_profile_add: no resident sequence batch");
     if (c->b().tiled) {
         // a tiled batch: "the whole batch" means the positions this rank OWNS (every base of the genome is owned by exactly
         // one rank; the K-1 bases kept behind an owned range belong to the words that start inside it)
         if (!(p0 < 0 && p1 < 0)) return fail(c, FRISK_E_ARG, "frisk_profile_add: a tiled batch is profiled as a whole (-1, -1)");
+        c->profile_final = false;           // (as every add: also when this rank owns no position)
         const frisk_ctx::Batch& B = c->b();
         for (size_t t = 0; t < B.tiles.size(); ++t) {
             const frisk_ctx::Batch::Tile& T = B.tiles[t];
             if (T.own1 <= T.own0) continue;
-            int rc = profile_add_range(c, mask_host, B.seq_off[t] + (T.own0 - T.base0), B.seq_off[t] + (T.own1 - T.base0));
+            int rc = profile_add_range(c, mask_host, one_pass, B.seq_off[t] + (T.own0 - T.base0), B.seq_off[t] + (T.own1 - T.base0));
             if (rc) return rc;
         }
         return FRISK_OK;
@@ -1268,7 +1283,7 @@ int frisk_profile_add(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1) {
             HIPC(c, hipStreamWaitEvent(c->stream, SB.piece_ev[i], 0));
             const int64_t upto = i + 1 == np ? SB.padded_len : (SB.piece_end[i] - 1) * 32;
             if (upto > done || i + 1 == np || i == 0) {
-                int rc = profile_add_range(c, mask_host, done, std::max(done, upto), i == 0, i + 1 == np);
+                int rc = profile_add_range(c, mask_host, one_pass, done, std::max(done, upto), i == 0, i + 1 == np);
                 if (rc) return rc;
                 done = std::max(done, upto);
             }
@@ -1277,10 +1292,10 @@ int frisk_profile_add(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1) {
         return FRISK_OK;
     }
     if (int rs = settle_stream(c)) return rs;
-    return profile_add_range(c, mask_host, p0, p1);
+    return profile_add_range(c, mask_host, one_pass, p0, p1);
 }
 
-static int profile_add_range(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1, bool first, bool last) {
+static int profile_add_range(frisk_ctx* c, int mask_host, bool one_pass, int64_t p0, int64_t p1, bool first, bool last) {
     if (p0 < 0 && p1 < 0) { p0 = 0; p1 = c->b().padded_len; }
     if (p0 < 0 || p1 > c->b().padded_len || p0 > p1) return fail(c, FRISK_E_ARG, "position range outside the batch");
     HIPC(c, hipSetDevice(c->device));
@@ -1299,10 +1314,8 @@ static int profile_add_range(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1
     // K = 8, a long range (a whole resident genome): 16-bit counters, ONE walk over the sequence (profile_add16_kernel; a wrapped
     // counter sends its workgroup to the two-half form).  The walk halves, the flush doubles (65 536 fields per workgroup instead of
     // 32 768 bins): measured 2.42 -> 1.33 ms on the 3.29 Gb shape, 0.345 -> 0.55 ms on the 410 Mb shard (tools/exp/prof_ab.py) - so from
-    // 2^30 positions per launch on.  (mask_host bit 1 = FRISK_PROFILE_ONE_PASS forces it: the tests' way to the overflow path.)
-    const bool one_pass = c->kmax == 8 && ((mask_host & 2) || p1 - p0 >= (int64_t(1) << 30));
-    mask_host &= 1;
-    if (one_pass) {
+    // 2^30 positions per launch on.  (one_pass = FRISK_PROFILE_ONE_PASS forces it: the tests' way to the overflow path.)
+    if (c->kmax == 8 && (one_pass || p1 - p0 >= (int64_t(1) << 30))) {
         const int64_t span16 = p1 - p0;
         const int64_t nwords16 = span16 > 0 ? ((p1 + 31) >> 5) - (p0 >> 5) : 0;
         int64_t nch = std::min<int64_t>(std::max<int64_t>(1, span16 / 65536), int64_t(c->num_cu));

@@ -5,6 +5,7 @@ the HIP kernels.  torch is used only by `profile_allreduce` (RCCL through torch.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -104,6 +105,7 @@ class Engine:
         self.seq_lens = []
         self.shard_index = None     # the seek index the last load_fasta_shard used (None: it parsed the file)
         self._pinned = {}           # name -> (address, nbytes): page-locked result buffers, reused across scans
+        self._owned = {}            # address -> finaliser: page-locked buffers that belong to the arrays handed out (_owned_array)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -111,6 +113,8 @@ class Engine:
             for addr, _ in self._pinned.values():
                 self._lib.frisk_host_free(self._ctx, C.c_void_p(addr))
             self._pinned = {}
+            for fin in list(self._owned.values()):
+                fin()
             self._lib.frisk_destroy(self._ctx)
             self._ctx = C.c_void_p()
 
@@ -129,6 +133,26 @@ class Engine:
             self._pinned[name] = (addr, cap)
         buf = (C.c_char * need).from_address(addr)
         return np.frombuffer(buf, dtype=dtype, count=max(int(n), 1))
+
+    def _owned_array(self, n, dtype):
+        """numpy array in a page-locked buffer of its own: freed when the last array that views it goes (or at close()), never
+        handed to another call - what pack_2bit / export_2bit / export_packed return, which a streamed upload may still read."""
+        dtype = np.dtype(dtype)
+        nbytes = max(int(n), 1) * dtype.itemsize
+        addr = self._lib.frisk_host_alloc(self._ctx, nbytes)
+        if not addr:
+            raise MemoryError("frisk_host_alloc(%d) failed" % nbytes)
+        buf = (C.c_char * nbytes).from_address(addr)
+        fin = weakref.finalize(buf, Engine._free_owned, weakref.ref(self), addr)
+        fin.atexit = False
+        self._owned[addr] = fin
+        return np.frombuffer(buf, dtype=dtype, count=max(int(n), 1))
+
+    @staticmethod
+    def _free_owned(engine_ref, addr):
+        eng = engine_ref()
+        if eng is not None and eng._owned.pop(addr, None) is not None and getattr(eng, "_ctx", None):
+            eng._lib.frisk_host_free(eng._ctx, C.c_void_p(addr))
 
     def __del__(self):
         try:
@@ -196,23 +220,24 @@ class Engine:
     def pack_2bit(self, seqs, pinned=True):
         """ASCII scaffolds -> the 0.25 B/base upload form, on the host (library threads): (codes, inv_runs, low_runs, lens).
         codes: uint32[2 P / 32] (page-locked when pinned=True: its upload is then asynchronous); inv_runs / low_runs: int64[n, 2]
-        half-open runs of padded positions (letters other than ACGTacgt / lowercase acgt)."""
+        half-open runs of padded positions (letters other than ACGTacgt / lowercase acgt).  Page-locked arrays belong to the
+        caller as ordinary ones do: no later call writes them (valid until close())."""
         arrs = [self._as_u8(s) for s in seqs]
         n = len(arrs)
         ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
         lens = [int(a.size) for a in arrs]
         clens = (C.c_int64 * max(n, 1))(*lens)
         P = int(self._lib.frisk_padded_len_of(clens, n))
-        codes = self.host_array("codes2", 2 * P // 32, np.uint32) if pinned else np.empty(2 * P // 32, np.uint32)
+        codes = self._owned_array(2 * P // 32, np.uint32) if pinned else np.empty(2 * P // 32, np.uint32)
         pi, pl, ni, nl = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
         self._check(self._lib.frisk_pack_2bit(ptrs, clens, n, _ptr(codes), C.byref(pi), C.byref(ni), C.byref(pl), C.byref(nl)))
         return (codes,) + self._take_runs(pi, ni, pl, nl, pinned) + (lens,)
 
     def _take_runs(self, pi, ni, pl, nl, pinned):
         out = []
-        for tag, ptr, cnt in (("inv_runs", pi, ni), ("low_runs", pl, nl)):
+        for ptr, cnt in ((pi, ni), (pl, nl)):
             k = int(cnt.value)
-            dst = self.host_array(tag, max(2 * k, 2), np.int64)[:2 * k] if pinned else np.empty(2 * k, np.int64)
+            dst = self._owned_array(max(2 * k, 2), np.int64)[:2 * k] if pinned else np.empty(2 * k, np.int64)
             if k:
                 dst[:] = np.frombuffer((C.c_int64 * (2 * k)).from_address(ptr.value), dtype=np.int64)
             self._lib.frisk_free(ptr)
@@ -241,9 +266,9 @@ class Engine:
         self._staged = (keep, lens)
 
     def export_2bit(self, pinned=False):
-        """(codes, inv_runs, low_runs) of the resident batch in the 0.25 B/base form."""
+        """(codes, inv_runs, low_runs) of the resident batch in the 0.25 B/base form (pinned=True: page-locked, as pack_2bit)."""
         w32 = self.padded_len // 32
-        codes = self.host_array("codes2", 2 * w32, np.uint32) if pinned else np.empty(2 * w32, np.uint32)
+        codes = self._owned_array(2 * w32, np.uint32) if pinned else np.empty(2 * w32, np.uint32)
         pi, pl, ni, nl = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
         self._check(self._lib.frisk_seq_export_2bit(self._ctx, _ptr(codes), C.byref(pi), C.byref(ni), C.byref(pl), C.byref(nl)))
         return (codes,) + self._take_runs(pi, ni, pl, nl, pinned)
@@ -257,10 +282,11 @@ class Engine:
             self._check(self._lib.frisk_seq_set_names(self._ctx, arr, len(names)))
 
     def export_packed(self, pinned=False):
-        """(codes, inv, low) of the resident batch as uint32 arrays (2P/32, P/32, P/32 words; P = padded_len)."""
+        """(codes, inv, low) of the resident batch as uint32 arrays (2P/32, P/32, P/32 words; P = padded_len; pinned=True:
+        page-locked, as pack_2bit)."""
         w32 = self.padded_len // 32
-        new = (lambda nm, n: self.host_array(nm, n, np.uint32)) if pinned else (lambda nm, n: np.empty(n, np.uint32))
-        codes, inv, low = new("codes", 2 * w32), new("inv", w32), new("low", w32)
+        new = (lambda n: self._owned_array(n, np.uint32)) if pinned else (lambda n: np.empty(n, np.uint32))
+        codes, inv, low = new(2 * w32), new(w32), new(w32)
         self._check(self._lib.frisk_seq_export_packed(self._ctx, _ptr(codes), _ptr(inv), _ptr(low)))
         return codes, inv, low
 

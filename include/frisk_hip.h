@@ -75,7 +75,8 @@ int64_t frisk_profile_len(const frisk_ctx* ctx);      /* sum_{x=kmin..kmax} 4^x 
  * Replaces the hand-off of scaffold strings from iterFasta (L139-164) to the counters
  * (L297, L203).  Uploads n_seq scaffolds (ASCII, any case, any IUPAC letter), packs them on
  * the device to 2 bits/base + validity and soft-mask bitmaps, and keeps them resident until the
- * next load.  Empty scaffolds (len 0) are allowed. */
+ * next load.  Empty scaffolds (len 0) are allowed.  A refused load (FRISK_E_ARG: n_seq < 0, a negative length) changes nothing:
+ * the resident batch, its lengths and names stay as they were.  The same holds for frisk_seq_synth / frisk_seq_synth2. */
 int frisk_seq_load(frisk_ctx* ctx, const uint8_t* const* seqs, const int64_t* lens, int32_t n_seq);
 
 /* Double-buffered residency - the "streamed to HBM" of the north star.  frisk_seq_stage uploads and packs the NEXT batch on
@@ -99,7 +100,7 @@ int frisk_seq_stage_packed(frisk_ctx* ctx, const uint32_t* codes, const uint32_t
  * The codes cross PCIe in pieces of piece_bases positions (0: the library's default, 256 Mbases = 64 MB) with an event behind
  * each: frisk_seq_commit does not wait for them, and frisk_profile_add(-1, -1) on the committed batch counts piece i while
  * piece i + 1 is on its way, so that of phase A only the last piece's kernel follows the upload.  Any other use of the batch
- * waits (on the device) for the last piece.  Replaces, with frisk_pack_2bit, the hand-off of scaffold strings from iterFasta
+ * waits (on the device) for the last piece - a load that replaces the batch in its slot included.  Replaces, with frisk_pack_2bit, the hand-off of scaffold strings from iterFasta
  * (L139-164) to computeKmers (L297) and crawlGenome (L203).  Caller keeps the arrays alive as for frisk_seq_stage. */
 int frisk_seq_stage_2bit(frisk_ctx* ctx, const uint32_t* codes, const int64_t* inv_runs, int64_t n_inv, const int64_t* low_runs,
                          int64_t n_low, const int64_t* lens, int32_t n_seq, int64_t piece_bases);
@@ -184,7 +185,8 @@ int frisk_profile_reset(frisk_ctx* ctx);
 /* Count the k-mers that START in padded positions [pos_begin,pos_end) of the resident batch;
  * pos_begin = pos_end = -1 means the whole batch.  mask_host: bit 0 = --maskHost (L336-337); bit 1 = FRISK_PROFILE_ONE_PASS, a test
  * hook: at kmax = 8 take the one-pass form with 16-bit LDS counters (what ranges of 2^30+ positions take by themselves; a wrapped
- * counter falls back to the two-pass form) whatever the size.  Same counts either way. */
+ * counter falls back to the two-pass form) whatever the size; at other kmax it changes nothing.  Same counts either way: bit 1 never
+ * masks, on any path (kmax > 8, a streamed batch counted piece by piece, a tiled batch). */
 #define FRISK_PROFILE_ONE_PASS 2
 int frisk_profile_add(frisk_ctx* ctx, int mask_host, int64_t pos_begin, int64_t pos_end);
 int64_t frisk_seq_padded_len(const frisk_ctx* ctx);
