@@ -85,6 +85,10 @@ SYMBOLS = [
     ("frisk_tsne_get", C.c_int, [_P, _P, _P, _P]),
     ("frisk_tsne_set", C.c_int, [_P, _P, _P, _P]),
     ("frisk_tsne_destroy", None, [_P]),
+    ("frisk_mds_create", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_P)]),
+    ("frisk_mds_dissimilarities", C.c_int, [_P, _P]),
+    ("frisk_mds_run", C.c_int, [_P, _P, C.c_int32, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32), _P]),
+    ("frisk_mds_destroy", None, [_P]),
     ("frisk_host_alloc", C.c_void_p, [_P, C.c_int64]),
     ("frisk_host_free", None, [_P, _P]),
     ("frisk_last_kernel_ms", C.c_double, [_P, C.c_int]),

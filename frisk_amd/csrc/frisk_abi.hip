@@ -31,6 +31,7 @@
 #include "hmm_host.h"
 #include "proj_kernels.h"
 #include "tsne_kernels.h"
+#include "mds_kernels.h"
 
 #define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
 #define FRISK_SIDE_SHARE 0.06       // 4-bit bulk takes the side-table form when the plain form would hand on more than this share of the sample
@@ -2170,6 +2171,55 @@ int frisk_tsne_set(frisk_tsne* h, const double* Y, const double* iY, const doubl
 }
 
 void frisk_tsne_destroy(frisk_tsne* h) {
+    if (!h) return;
+    frisk_proj::OnDevice on(h->s.device);
+    delete h;
+}
+
+// ---- metric MDS (mds_kernels.h): a handle holding the dissimilarities on its device between runs
+struct frisk_mds {
+    frisk_mds_impl::State s;
+};
+
+int frisk_mds_create(int device, const double* X, int64_t n, int64_t f, int32_t dims, frisk_mds** out) {
+    if (!out) return FRISK_E_ARG;
+    *out = nullptr;
+    if (!X || n < 2 || n > frisk_mds_impl::MAX_N || f < 1 || dims < 1 || dims > frisk_mds_impl::MAX_D || !all_finite(X, n * f))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    frisk_mds* h = new (std::nothrow) frisk_mds;
+    if (!h) return FRISK_E_HIP;
+    h->s.device = device;
+    h->s.n = n;
+    h->s.f = f;
+    h->s.d = dims;
+    if (h->s.create(X)) {
+        delete h;
+        return FRISK_E_HIP;
+    }
+    *out = h;
+    return FRISK_OK;
+}
+
+int frisk_mds_dissimilarities(frisk_mds* h, double* D_out) {
+    if (!h || !D_out) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    const size_t bytes = size_t(h->s.n) * size_t(h->s.n) * sizeof(double);
+    return hipMemcpy(D_out, h->s.D, bytes, hipMemcpyDeviceToHost) == hipSuccess ? FRISK_OK : FRISK_E_HIP;
+}
+
+int frisk_mds_run(frisk_mds* h, const double* Y0, int32_t max_iter, double eps, double* Y_out, double* stress_out,
+                  int32_t* n_iter_out, double* stress_trace_out) {
+    if (!h || !Y0 || !Y_out || max_iter < 1 || !(eps >= 0.0) || !std::isfinite(eps) || !all_finite(Y0, h->s.n * h->s.d))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.run(Y0, max_iter, eps, Y_out, stress_out, n_iter_out, stress_trace_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+void frisk_mds_destroy(frisk_mds* h) {
     if (!h) return;
     frisk_proj::OnDevice on(h->s.device);
     delete h;

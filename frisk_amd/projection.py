@@ -1,7 +1,8 @@
 """Symmetric k-mer proportions of anomalous windows, and their projection and clustering:
 PCA, DBSCAN and k-means as the reference runs them through sklearn (L1597-1665), on the GPU (frisk_proj_* / frisk_dbscan /
 frisk_kmeans, csrc/proj_kernels.h), and the reference's own exact t-SNE, PY-TSNE (frisk/tsne.py, L1622-1623), on the GPU
-(frisk_tsne_*, csrc/tsne_kernels.h).  sklearn's t-SNE, IncrementalPCA, NMF, MDS and spectral clustering are not built.
+(frisk_tsne_*, csrc/tsne_kernels.h), and sklearn's metric MDS (L1624-1627) on the GPU (frisk_mds_*, csrc/mds_kernels.h).
+sklearn's t-SNE, IncrementalPCA, NMF and spectral clustering are not built.
 
 Reference (frisk/__init__.py): computeKmers(sym=True, pcaMode=True) L280-367 counts every valid word AND its
 reverse complement for orders pcaMin..pcaMax; scrubMirrors L797-811 keeps one key of each reverse-complement pair
@@ -77,6 +78,8 @@ def symmetricCounts(labelled_seqs, pcaMin, pcaMax, device=0):
 # ------------------------------------------------------------------------------------------------ projection / clustering
 DBSCAN_MIN_SAMPLES = 50         # DBSCAN(eps=args.epsDBSCAN, min_samples=50) (L1639)
 KMEANS_N_INIT, KMEANS_MAX_ITER, KMEANS_TOL = 20, 500, 1e-4      # KMeans(n_init=20, max_iter=500, tol=0.0001) (L1647-1649)
+MDS_N_INIT, MDS_MAX_ITER, MDS_EPS = 5, 500, 1e-3        # MDS(metric=True, n_init=5, max_iter=500, eps=0.001, n_jobs=1) (L1624-1627)
+MDS_MAX_N = 50000                   # the dense n x n dissimilarities: 20 GB at the cap
 
 
 def _ptr(a):
@@ -317,3 +320,79 @@ def tsne(X, dims=2, perplexity=20.0, seed=0, initial_dims=50, device=0, log=None
             log(10 * (k + 1), c)
     return TSNEResult(Y, cost, beta, tries, {"pca_ms": 1e3 * (t1 - t0), "affinities_ms": 1e3 * (t2 - t1),
                                              "iterations_ms": 1e3 * (t3 - t2)})
+
+
+# ------------------------------------------------------------------------------------------------ MDS
+class MDS:
+    """Metric MDS on the GPU (frisk_mds_*): the dissimilarities of X (n x f, any f >= 1) stay on the device, and each run() is one
+    SMACOF start against them.  Use as a context manager (or call close())."""
+
+    def __init__(self, X, dims=2, device=0):
+        X = _f64(X, 2)
+        self.n, self.f = X.shape
+        self.dims = int(dims)
+        self._h = C.c_void_p()
+        _call("frisk_mds_create", device, _ptr(X), self.n, self.f, self.dims, C.byref(self._h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._h:
+            _ffi.lib().frisk_mds_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def dissimilarities(self):
+        """The n x n D (direct-difference Euclidean distances of the rows of X)."""
+        D = np.empty((self.n, self.n))
+        _call("frisk_mds_dissimilarities", self._h, _ptr(D))
+        return D
+
+    def run(self, Y0, max_iter=MDS_MAX_ITER, eps=MDS_EPS):
+        """sklearn's _smacof_single(D, metric=True, init=Y0, max_iter, eps): (Y, raw stress, iterations, stress after each
+        iteration)."""
+        Y0 = _f64(Y0, 2)
+        if Y0.shape != (self.n, self.dims):
+            raise ValueError("expected a start of shape %s, got %s" % ((self.n, self.dims), Y0.shape))
+        Y, trace = np.empty_like(Y0), np.empty(max(1, int(max_iter)))
+        stress, iters = C.c_double(), C.c_int32()
+        _call("frisk_mds_run", self._h, _ptr(Y0), int(max_iter), float(eps), _ptr(Y), C.byref(stress), C.byref(iters),
+              _ptr(trace))
+        return Y, stress.value, iters.value, trace[:iters.value].copy()
+
+
+class MDSResult:
+    """Y (n x dims) of the best start, its raw stress and iterations, best_start (0-based), the stresses and n_iters of every
+    start; timings in ms (dissimilarities / smacof)."""
+
+    def __init__(self, Y, stress, n_iter, best_start, stresses, n_iters, timings):
+        self.Y, self.stress, self.n_iter, self.best_start = Y, stress, n_iter, best_start
+        self.stresses, self.n_iters, self.timings = stresses, n_iters, timings
+
+
+def mds(X, dims=2, seed=0, n_init=MDS_N_INIT, max_iter=MDS_MAX_ITER, eps=MDS_EPS, device=0):
+    """sklearn's MDS(n_components=dims, metric=True, n_init, max_iter, eps, n_jobs=1, dissimilarity='euclidean',
+    random_state=seed).fit_transform(X) (L1624-1627): D on the GPU from direct differences, then n_init SMACOF runs on the GPU
+    from starts drawn in turn from one RandomState(seed) (uniform on [0, 1)); the run of lowest raw stress is kept (the earliest
+    on a tie)."""
+    X = _f64(X, 2)
+    n = X.shape[0]
+    if not 2 <= n <= MDS_MAX_N:
+        raise ValueError("MDS needs between 2 and %d samples, got %d" % (MDS_MAX_N, n))
+    rs = np.random.RandomState(seed)
+    t0 = time.perf_counter()
+    with MDS(X, dims, device) as h:
+        t1 = time.perf_counter()
+        best, stresses, n_iters = None, [], []
+        for k in range(n_init):
+            Y, stress, iters, _ = h.run(rs.uniform(size=n * dims).reshape(n, dims), max_iter, eps)
+            stresses.append(stress)
+            n_iters.append(iters)
+            if best is None or stress < best[1]:
+                best = (Y, stress, iters, k)
+        t2 = time.perf_counter()
+    return MDSResult(best[0], best[1], best[2], best[3], stresses, n_iters,
+                     {"dissimilarities_ms": 1e3 * (t1 - t0), "smacof_ms": 1e3 * (t2 - t1)})

@@ -318,6 +318,27 @@ int  frisk_tsne_get(frisk_tsne* h, double* Y, double* iY, double* gains);
 int  frisk_tsne_set(frisk_tsne* h, const double* Y, const double* iY, const double* gains);
 void frisk_tsne_destroy(frisk_tsne* h);
 
+/* Metric MDS of the reference's --runProjection MDS (sklearn.manifold.MDS(metric=True, dissimilarity='euclidean'): the SMACOF
+ * algorithm of sklearn's _smacof_single), FP64 on `device`.  The handle keeps the n x n dissimilarities on the device, so a caller
+ * can run several starts, or step the algorithm, against one D; every result is bit-identical from run to run.
+ * frisk_mds_create: X[n][f] (the raw k-mer proportions), dims output columns; computes D_ij = sqrt(sum_k (x_ik - x_jk)^2) by
+ *   direct differences (exactly symmetric, diagonal exactly 0).  FRISK_E_ARG, with nothing allocated, unless 2 <= n <= 50 000,
+ *   f >= 1, 1 <= dims <= 64 and X finite.  Device memory: 8 n^2 bytes for D plus O(n (f + dims)).
+ * frisk_mds_dissimilarities: D_out[n][n] = D.
+ * frisk_mds_run: SMACOF from Y0[n][dims]: each step sets configuration distances that are exactly 0 to 1e-5, X <- (1 / n) B X
+ *   with B = -D / dist plus its row sums on the diagonal (computed as sum_j D_ij / dist_ij (x_i - x_j)), then the raw stress
+ *   sum over all i, j of (dist_ij - D_ij)^2 / 2 of the new X; from the second step on it stops when
+ *   (previous stress - stress) / (sum over all i, j of dist_ij^2 / 2) < eps, evaluated on the host in double, or after max_iter
+ *   steps.  Y_out[n][dims] the final X, stress_out its raw stress, n_iter_out the steps run (both nullable); stress_trace_out
+ *   (nullable, room for max_iter values) the stress after each step.  With eps = 0 the run stops early only if the stress
+ *   rises, so run(Y_t, 1, 0) is one step.  FRISK_E_ARG for non-finite Y0, max_iter < 1, or eps < 0 or not finite. */
+typedef struct frisk_mds frisk_mds;
+int  frisk_mds_create(int device, const double* X, int64_t n, int64_t f, int32_t dims, frisk_mds** out);
+int  frisk_mds_dissimilarities(frisk_mds* h, double* D_out);
+int  frisk_mds_run(frisk_mds* h, const double* Y0, int32_t max_iter, double eps, double* Y_out, double* stress_out,
+                   int32_t* n_iter_out, double* stress_trace_out);
+void frisk_mds_destroy(frisk_mds* h);
+
 /* Page-locked host memory for result buffers: D2H copies into it are asynchronous and run at PCIe rate
  * (pageable buffers work too, at a fraction of it).  Free with frisk_host_free before frisk_destroy. */
 void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);

@@ -7,12 +7,16 @@
   numpy / sklearn on the host's CPUs for the same work (null where sklearn is absent);
   PY-TSNE (exact t-SNE, d = 2, perplexity 20) at n = 5 000, 20 000 and 50 000 windows of F = 2 772 reduced to 50 columns:
   PCA-step, affinity and per-iteration ms, the 1000-iteration total, and the numpy restatement's ms per iteration on the host
-  (tests/tsne_oracle.py, 20 iterations at n = 5 000).
+  (tests/tsne_oracle.py, 20 iterations at n = 5 000);
+  MDS (--mds-only, metric SMACOF, d = 2) at n = 5 000, 20 000 and 50 000 windows of F = 2 772: dissimilarity ms (the handle's
+  create), ms per SMACOF step, iterations per start and the whole 5-start mds() ms; sklearn's MDS on the host at n = 2 000 and
+  5 000 (--no-gpu: only those); written to --out as well as printed.
 
 Every GPU time is a host clock around one call, which ends in a device-to-host copy (so it includes the host-to-device copy of the
 input); each shape is run once untimed first.  --small: tiny sizes, for a profiler run.
 
     python tools/proj_timing.py [--small] [--no-cpu] [--tsne-only]
+    python tools/proj_timing.py --mds-only [--ns 5000 20000] [--no-cpu | --no-gpu] [--out profiles/proj/mds_timing.json]
 """
 import argparse
 import json
@@ -49,7 +53,18 @@ def main():
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--tsne-only", action="store_true", help="only the PY-TSNE legs")
+    ap.add_argument("--mds-only", action="store_true", help="only the MDS legs")
+    ap.add_argument("--no-gpu", action="store_true", help="with --mds-only: only sklearn on the host")
+    ap.add_argument("--ns", type=int, nargs="+", default=None, help="with --mds-only: the GPU sizes")
+    ap.add_argument("--out", default=None, help="with --mds-only: also write the JSON here")
     opts = ap.parse_args()
+    if opts.mds_only:
+        doc = json.dumps({"tool": "proj_timing", "mds": mds_legs(opts)})
+        print(doc)
+        if opts.out:
+            with open(opts.out, "w") as fh:
+                fh.write(doc + "\n")
+        return
     if opts.tsne_only:
         print(json.dumps({"tool": "proj_timing", "tsne": tsne_legs(opts)}))
         return
@@ -130,6 +145,37 @@ def tsne_legs(opts):
             st = TO.step(Y, iY, gains, q, t)
             Y, iY, gains = st.Y, st.iY, st.gains
         out["numpy_oracle_ms_per_iteration_%d" % n] = 1e3 * (time.perf_counter() - t0) / 20
+    return out
+
+
+def mds_legs(opts):
+    F = 2772
+    out = {"F": F, "d": 2, "n_init": 5, "max_iter": 500, "eps": 1e-3}
+    if not opts.no_gpu:
+        from frisk_amd import projection as P
+        P.mds(_proportions(300, F, 1), 2)           # first launches
+        for n in opts.ns or ((1000,) if opts.small else (5000, 20000, 50000)):
+            X = _proportions(n, F, n)
+            Y0 = np.random.RandomState(0).uniform(size=(n, 2))
+            t0 = time.perf_counter()
+            with P.MDS(X, 2) as h:
+                t1 = time.perf_counter()
+                h.run(Y0, 1, 0.0)                   # 2 passes
+                t2 = time.perf_counter()
+                h.run(Y0, 21, 0.0)                  # 22 passes
+                t3 = time.perf_counter()
+            r = P.mds(X, 2)
+            out[str(n)] = {"dissimilarities_ms": 1e3 * (t1 - t0), "ms_per_step": 1e3 * ((t3 - t2) - (t2 - t1)) / 20,
+                           "n_iters": r.n_iters, "best_start": r.best_start, "stress": r.stress, "mds_ms": sum(r.timings.values()),
+                           "mds_timings": r.timings, "D_floor_ms_per_step": 8.0 * n * n / 6.3e12 * 1e3}
+    if not opts.no_cpu:
+        from sklearn.manifold import MDS
+        for n in ((500,) if opts.small else (2000, 5000)):
+            X = _proportions(n, F, n)
+            m = MDS(n_components=2, metric=True, n_init=5, max_iter=500, eps=1e-3, n_jobs=1, random_state=0,
+                    dissimilarity="euclidean", normalized_stress=False)
+            ms, _ = _ms(m.fit_transform, X)
+            out["sklearn_%d" % n] = {"ms": ms, "n_iter": int(m.n_iter_), "threads": os.cpu_count()}
     return out
 
 
