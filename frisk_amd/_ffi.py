@@ -89,6 +89,14 @@ SYMBOLS = [
     ("frisk_mds_dissimilarities", C.c_int, [_P, _P]),
     ("frisk_mds_run", C.c_int, [_P, _P, C.c_int32, C.c_double, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32), _P]),
     ("frisk_mds_destroy", None, [_P]),
+    ("frisk_ipca_create", C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(_P)]),
+    ("frisk_ipca_gram", C.c_int, [_P, _P, C.c_int64, _P]),
+    ("frisk_ipca_commit", C.c_int, [_P, _P, _P]),
+    ("frisk_ipca_get", C.c_int, [_P, _I64P, _P, _P, _P, _P]),
+    ("frisk_ipca_set", C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    ("frisk_ipca_transform", C.c_int, [_P, _P, C.c_int64, _P]),
+    ("frisk_ipca_last_ms", C.c_double, [_P, C.c_int]),
+    ("frisk_ipca_destroy", None, [_P]),
     ("frisk_host_alloc", C.c_void_p, [_P, C.c_int64]),
     ("frisk_host_free", None, [_P, _P]),
     ("frisk_last_kernel_ms", C.c_double, [_P, C.c_int]),

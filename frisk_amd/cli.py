@@ -6,10 +6,10 @@ caches, GFF3) and the same row echo on stdout.  Phase A and phase B run through 
 (frisk_amd.hotpath); thresholds, merging and GFF3 writing are host numpy (frisk_amd.postprocess).
 
 --hmmKLD runs frisk_amd.hmm (own 2-state Gaussian HMM; hmmlearn is absent and seeds randomly - parity unpinned).
---runProjection PCA, PY-TSNE (the reference's exact t-SNE, Y0 seeded by --seed, 0 when not given) or MDS (sklearn's metric MDS,
-its starts seeded the same way) with --cluster DBSCAN / KMEANS runs frisk_amd.projection on the GPU and writes the
-cluster-labelled GFF3.
-Out of scope here: the other projections (SKL-TSNE, IncrementalPCA, NMF) and SPECTRAL clustering,
+--runProjection PCA, PY-TSNE (the reference's exact t-SNE, Y0 seeded by --seed, 0 when not given), MDS (sklearn's metric MDS,
+its starts seeded the same way) or IncrementalPCA (sklearn's, in batches of 5 F rows) with --cluster DBSCAN / KMEANS runs
+frisk_amd.projection on the GPU and writes the cluster-labelled GFF3.
+Out of scope here: the other projections (SKL-TSNE, NMF) and SPECTRAL clustering,
 --graphics (seaborn/matplotlib), --gffIn intersections (bedtools).
 Those options are accepted, as in the reference, and reported as unavailable if used.
 
@@ -69,7 +69,8 @@ def build_parser():
     p.add_argument("--peakCRI", type=float, default=1.0)
     p.add_argument("--minPI", type=float, default=1.0)
     p.add_argument("--maxSI", type=float, default=1.0)
-    # projection / clustering (PCA, PY-TSNE, MDS, DBSCAN and KMEANS built; the other methods accepted, not available in this build)
+    # projection / clustering (PCA, PY-TSNE, MDS, IncrementalPCA, DBSCAN and KMEANS built; the other methods accepted, not available
+    # in this build)
     p.add_argument("--runProjection", default=None, choices=[None, "PCA", "PY-TSNE", "SKL-TSNE", "IncrementalPCA", "NMF", "MDS"])
     p.add_argument("--projectionDims", type=int, default=2)
     p.add_argument("--dimReduce", default="windows", choices=["features", "windows"])
@@ -92,13 +93,13 @@ def build_parser():
     return p
 
 
-PROJECTIONS = ("PCA", "PY-TSNE", "MDS")     # --runProjection methods built here (frisk_amd.projection)
+PROJECTIONS = ("PCA", "PY-TSNE", "MDS", "IncrementalPCA")     # --runProjection methods built here (frisk_amd.projection)
 CLUSTERINGS = ("DBSCAN", "KMEANS")      # --cluster methods built here
 
 
 def unavailable(args):
     """(option, reason) of every given option this build accepts but does not run.  --cluster runs only as DBSCAN or KMEANS
-    after --runProjection PCA, PY-TSNE or MDS (the reference clusters the projection, L1635-1655)."""
+    after --runProjection PCA, PY-TSNE, MDS or IncrementalPCA (the reference clusters the projection, L1635-1655)."""
     clustering = args.runProjection in PROJECTIONS and args.cluster in CLUSTERINGS
     out = []
     for opt, why in (("cluster", "sklearn clustering is out of scope"),
@@ -228,8 +229,8 @@ def _seed(args):
 
 
 def _project(args, anomCounts, device, clock):
-    """--runProjection PCA (L1612-1613), PY-TSNE (L1622-1623) or MDS (L1624-1627) on the anomalies' k-mer proportions, then --cluster DBSCAN /
-    KMEANS on the projection (L1635-1655).  Returns the cluster labels (None without a clustering this build runs)."""
+    """--runProjection PCA (L1612-1613), PY-TSNE (L1622-1623), MDS (L1624-1627) or IncrementalPCA (L1629-1631) on the anomalies' k-mer
+    proportions, then --cluster DBSCAN / KMEANS on the projection (L1635-1655).  Returns the cluster labels (None without a clustering this build runs)."""
     from . import projection as P
     if args.runProjection == "PY-TSNE":
         n = anomCounts.shape[0]
@@ -248,6 +249,12 @@ def _project(args, anomCounts, device, clock):
         log.info("MDS of %s x %s k-mer proportions: stress %s (start %s of %s, %s iterations); dissimilarities %.1f ms, "
                  "SMACOF %.1f ms", n, anomCounts.shape[1], res.stress, res.best_start + 1, len(res.stresses), res.n_iter,
                  res.timings["dissimilarities_ms"], res.timings["smacof_ms"])
+    elif args.runProjection == "IncrementalPCA":
+        res = P.incremental_pca(anomCounts, args.projectionDims, device=device)
+        log.info("IncrementalPCA of %s x %s k-mer proportions in %s batches: explained variance %s; statistics + Gram %.1f ms, "
+                 "eigh %.1f ms, transform %.1f ms", anomCounts.shape[0], anomCounts.shape[1], len(res.batch_sizes),
+                 res.explained_variance_.tolist(), res.timings["stats_gram_ms"], res.timings["eigh_ms"],
+                 res.timings["transform_ms"])
     else:
         res = P.pca(anomCounts, args.projectionDims, device=device)
         log.info("PCA of %s x %s k-mer proportions: explained variance %s; covariance %.1f ms, eigh %.1f ms, transform %.1f ms",

@@ -32,6 +32,7 @@
 #include "proj_kernels.h"
 #include "tsne_kernels.h"
 #include "mds_kernels.h"
+#include "ipca_kernels.h"
 
 #define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
 #define FRISK_SIDE_SHARE 0.06       // 4-bit bulk takes the side-table form when the plain form would hand on more than this share of the sample
@@ -2220,6 +2221,86 @@ int frisk_mds_run(frisk_mds* h, const double* Y0, int32_t max_iter, double eps, 
 }
 
 void frisk_mds_destroy(frisk_mds* h) {
+    if (!h) return;
+    frisk_proj::OnDevice on(h->s.device);
+    delete h;
+}
+
+// ---- incremental PCA (ipca_kernels.h): a handle holding the fit (rows seen, mean, variance, S, V) on its device between batches
+struct frisk_ipca {
+    frisk_ipca_impl::State s;
+};
+
+int frisk_ipca_create(int device, int64_t f, int32_t d, frisk_ipca** out) {
+    if (!out) return FRISK_E_ARG;
+    *out = nullptr;
+    if (f < 1 || d < 1 || d > f) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    frisk_ipca* h = new (std::nothrow) frisk_ipca;
+    if (!h) return FRISK_E_HIP;
+    h->s.device = device;
+    h->s.f = f;
+    h->s.d = d;
+    if (h->s.create()) {
+        delete h;
+        return FRISK_E_HIP;
+    }
+    *out = h;
+    return FRISK_OK;
+}
+
+int frisk_ipca_gram(frisk_ipca* h, const double* X, int64_t b, double* G_out) {
+    if (!h || !X || !G_out || b < 1 || (h->s.seen == 0 && b < h->s.d) || !all_finite(X, b * h->s.f)) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.gram(X, b, G_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_ipca_commit(frisk_ipca* h, const double* S, const double* Vt) {
+    if (!h || !S || !Vt || !all_finite(S, h->s.d) || !all_finite(Vt, int64_t(h->s.d) * h->s.f)) return FRISK_E_ARG;
+    if (!h->s.pending_b) return FRISK_E_STATE;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.commit(S, Vt) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_ipca_get(frisk_ipca* h, int64_t* n_seen, double* mean, double* var, double* S, double* Vt) {
+    if (!h) return FRISK_E_ARG;
+    if (n_seen) *n_seen = h->s.seen;
+    if (!mean && !var && !S && !Vt) return FRISK_OK;
+    if (!h->s.fitted) return FRISK_E_STATE;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    const size_t fb = size_t(h->s.f) * sizeof(double), db = size_t(h->s.d) * sizeof(double);
+    if (mean && hipMemcpy(mean, h->s.mean, fb, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    if (var && hipMemcpy(var, h->s.var, fb, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    if (S && hipMemcpy(S, h->s.S, db, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    if (Vt && hipMemcpy(Vt, h->s.Vt, size_t(h->s.d) * fb, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
+    return FRISK_OK;
+}
+
+int frisk_ipca_set(frisk_ipca* h, int64_t n_seen, const double* mean, const double* var, const double* S, const double* Vt) {
+    if (!h || n_seen < 0) return FRISK_E_ARG;
+    if (n_seen > 0 && (!mean || !var || !S || !Vt || !all_finite(mean, h->s.f) || !all_finite(var, h->s.f) ||
+                       !all_finite(S, h->s.d) || !all_finite(Vt, int64_t(h->s.d) * h->s.f)))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.set(n_seen, mean, var, S, Vt) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_ipca_transform(frisk_ipca* h, const double* X, int64_t n, double* Y_out) {
+    if (!h || !X || !Y_out || n < 1 || !all_finite(X, n * h->s.f)) return FRISK_E_ARG;
+    if (!h->s.fitted) return FRISK_E_STATE;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.transform(X, n, Y_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+double frisk_ipca_last_ms(const frisk_ipca* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
+
+void frisk_ipca_destroy(frisk_ipca* h) {
     if (!h) return;
     frisk_proj::OnDevice on(h->s.device);
     delete h;

@@ -1,8 +1,9 @@
 """Symmetric k-mer proportions of anomalous windows, and their projection and clustering:
 PCA, DBSCAN and k-means as the reference runs them through sklearn (L1597-1665), on the GPU (frisk_proj_* / frisk_dbscan /
 frisk_kmeans, csrc/proj_kernels.h), and the reference's own exact t-SNE, PY-TSNE (frisk/tsne.py, L1622-1623), on the GPU
-(frisk_tsne_*, csrc/tsne_kernels.h), and sklearn's metric MDS (L1624-1627) on the GPU (frisk_mds_*, csrc/mds_kernels.h).
-sklearn's t-SNE, IncrementalPCA, NMF and spectral clustering are not built.
+(frisk_tsne_*, csrc/tsne_kernels.h), sklearn's metric MDS (L1624-1627) on the GPU (frisk_mds_*, csrc/mds_kernels.h) and sklearn's
+IncrementalPCA (L1629-1631) on the GPU, batch by batch with the fit resident on the device (frisk_ipca_*, csrc/ipca_kernels.h).
+sklearn's t-SNE, NMF and spectral clustering are not built.
 
 Reference (frisk/__init__.py): computeKmers(sym=True, pcaMode=True) L280-367 counts every valid word AND its
 reverse complement for orders pcaMin..pcaMax; scrubMirrors L797-811 keeps one key of each reverse-complement pair
@@ -396,3 +397,173 @@ def mds(X, dims=2, seed=0, n_init=MDS_N_INIT, max_iter=MDS_MAX_ITER, eps=MDS_EPS
         t2 = time.perf_counter()
     return MDSResult(best[0], best[1], best[2], best[3], stresses, n_iters,
                      {"dissimilarities_ms": 1e3 * (t1 - t0), "smacof_ms": 1e3 * (t2 - t1)})
+
+
+# ------------------------------------------------------------------------------------------------ IncrementalPCA
+def gen_batches(n, batch_size, min_batch_size=0):
+    """sklearn.utils.gen_batches as (start, stop) pairs: full batches of batch_size rows; a tail shorter than min_batch_size
+    rows is merged into the batch before it."""
+    out, start = [], 0
+    for _ in range(int(n // batch_size)):
+        end = start + batch_size
+        if end + min_batch_size > n:
+            continue
+        out.append((start, end))
+        start = end
+    if start < n:
+        out.append((start, n))
+    return out
+
+
+class IncrementalPCA:
+    """sklearn's IncrementalPCA(n_components=dims, whiten=False) on the GPU (frisk_ipca_*): the fit (rows seen, mean, variance,
+    singular values, components) stays on the device between partial_fit calls, so X is only ever needed one batch at a time.
+    Per batch the device computes sklearn's mean / variance update and the Gram matrix G = AT A of sklearn's stacked matrix A;
+    the right singular vectors of A are the eigenvectors of G (one f x f torch.linalg.eigh on the same device, as pca()), the
+    top `dims` in descending order with sklearn's sign rule.  Because only `dims` components survive each batch, a fit of more
+    than one batch is not the PCA of X.  Use as a context manager (or call close())."""
+
+    def __init__(self, f, dims, device=0):
+        self.f, self.dims, self.device = int(f), int(dims), device
+        if not 1 <= self.dims <= self.f:
+            raise ValueError("n_components=%r invalid for n_features=%d, need more rows than columns for IncrementalPCA processing"
+                             % (dims, f))
+        self._h = C.c_void_p()
+        _call("frisk_ipca_create", device, self.f, self.dims, C.byref(self._h))
+        self.n_samples_seen_ = 0
+        self.explained_variance_ = self.explained_variance_ratio_ = self.noise_variance_ = None
+        self.timings = {"stats_ms": 0.0, "gram_ms": 0.0, "eigh_ms": 0.0}       # of the last partial_fit
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._h:
+            _ffi.lib().frisk_ipca_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def state(self):
+        """(n_samples_seen_, mean_, var_, singular_values_, components_) of the fit on the device; the arrays are None before
+        the first batch."""
+        seen = C.c_int64()
+        _call("frisk_ipca_get", self._h, C.byref(seen), None, None, None, None)
+        if seen.value == 0:
+            return 0, None, None, None, None
+        mean, var, S, Vt = np.empty(self.f), np.empty(self.f), np.empty(self.dims), np.empty((self.dims, self.f))
+        _call("frisk_ipca_get", self._h, None, _ptr(mean), _ptr(var), _ptr(S), _ptr(Vt))
+        return seen.value, mean, var, S, Vt
+
+    def set_state(self, n_samples_seen, mean=None, var=None, singular_values=None, components=None):
+        """Replace the fit on the device (n_samples_seen = 0: unfitted).  The derived attributes (explained_variance_, ...) are
+        those of a batch and are cleared."""
+        n = int(n_samples_seen)
+        if n < 0:
+            raise ValueError("n_samples_seen must be >= 0")
+        if n == 0:
+            _call("frisk_ipca_set", self._h, 0, None, None, None, None)
+        else:
+            mean, var, S, Vt = _f64(mean, 1), _f64(var, 1), _f64(singular_values, 1), _f64(components, 2)
+            if mean.shape != (self.f,) or var.shape != (self.f,) or S.shape != (self.dims,) or Vt.shape != (self.dims, self.f):
+                raise ValueError("state arrays do not have the shapes of f = %d, dims = %d" % (self.f, self.dims))
+            _call("frisk_ipca_set", self._h, n, _ptr(mean), _ptr(var), _ptr(S), _ptr(Vt))
+        self.n_samples_seen_ = n
+        self.explained_variance_ = self.explained_variance_ratio_ = self.noise_variance_ = None
+
+    mean_ = property(lambda self: self.state()[1])
+    var_ = property(lambda self: self.state()[2])
+    singular_values_ = property(lambda self: self.state()[3])
+    components_ = property(lambda self: self.state()[4])
+
+    def partial_fit(self, X):
+        import torch
+        X = _f64(X, 2)
+        b, f = X.shape
+        d = self.dims
+        if f != self.f:
+            raise ValueError("X has %d features, the fit %d" % (f, self.f))
+        first = self.n_samples_seen_ == 0
+        if first and d > b:
+            raise ValueError("n_components=%d must be less or equal to the batch number of samples %d for the first partial_fit "
+                             "call." % (d, b))
+        if b < 1:
+            raise ValueError("an empty batch")
+        G = np.empty((f, f))
+        _call("frisk_ipca_gram", self._h, _ptr(X), b, _ptr(G))
+        t0 = time.perf_counter()
+        tw, tv = torch.linalg.eigh(torch.from_numpy(G).to(torch.device("cuda", self.device)))
+        w, v = tw.cpu().numpy(), tv.cpu().numpy()
+        t1 = time.perf_counter()
+        order = np.argsort(w, kind="stable")[::-1][:d]
+        comps = v[:, order].T.copy()
+        big = np.argmax(np.abs(comps), axis=1)
+        comps *= np.sign(comps[np.arange(d), big])[:, None]
+        lam = np.maximum(w[order], 0.0)
+        S = np.sqrt(lam)
+        _call("frisk_ipca_commit", self._h, _ptr(S), _ptr(comps))
+        total = self.n_samples_seen_ + b
+        var = self.state()[2]
+        n_values = min(b if first else d + b + 1, f)            # singular values of A
+        trace = float(np.cumsum(np.diagonal(G))[-1])            # sum of all of them squared, in index order
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.explained_variance_ = S ** 2 / (total - 1)
+            self.explained_variance_ratio_ = S ** 2 / np.sum(var * total)
+            if d in (b, f):
+                self.noise_variance_ = 0.0
+            else:
+                self.noise_variance_ = max(trace - float(np.cumsum(lam)[-1]), 0.0) / (total - 1) / (n_values - d)
+        self.n_samples_seen_ = total
+        ms = _ffi.lib().frisk_ipca_last_ms
+        self.timings = {"upload_ms": ms(self._h, 0), "stats_ms": ms(self._h, 1), "gram_ms": ms(self._h, 2),
+                        "eigh_ms": 1e3 * (t1 - t0)}
+        return self
+
+    def transform(self, X):
+        """(X - mean_) components_.T on the GPU, any number of rows."""
+        X = _f64(X, 2)
+        if X.shape[1] != self.f:
+            raise ValueError("X has %d features, the fit %d" % (X.shape[1], self.f))
+        Y = np.empty((X.shape[0], self.dims))
+        if X.shape[0]:
+            _call("frisk_ipca_transform", self._h, _ptr(X), X.shape[0], _ptr(Y))
+        return Y
+
+
+class IncrementalPCAResult:
+    """Y (n x dims) and the fit under sklearn's names (components_ dims x f, singular_values_, mean_, var_, n_samples_seen_,
+    explained_variance_, explained_variance_ratio_, noise_variance_), batch_sizes, timings in ms (statistics + Gram with the
+    batch traffic / eigh / transform; kernels: the device time of statistics + stack and of the Gram kernels alone)."""
+
+    def __init__(self, Y, fit, batch_sizes, timings):
+        self.Y, self.batch_sizes, self.timings = Y, batch_sizes, timings
+        self.n_samples_seen_, self.mean_, self.var_, self.singular_values_, self.components_ = fit.state()
+        self.explained_variance_, self.explained_variance_ratio_ = fit.explained_variance_, fit.explained_variance_ratio_
+        self.noise_variance_ = fit.noise_variance_
+
+
+def incremental_pca(X, dims, batch_size=None, device=0):
+    """sklearn's IncrementalPCA(n_components=dims, batch_size=batch_size).fit(X).transform(X) (L1629-1631): batches of
+    batch_size rows (None: 5 * n_features), a tail shorter than dims rows merged into the batch before it."""
+    X = _f64(X, 2)
+    n, f = X.shape
+    size = 5 * f if batch_size is None else int(batch_size)
+    if size < 1:
+        raise ValueError("batch_size must be >= 1")
+    if n < 1:
+        raise ValueError("IncrementalPCA needs at least 1 sample")
+    batches = gen_batches(n, size, dims)
+    t = {"stats_gram_ms": 0.0, "eigh_ms": 0.0, "transform_ms": 0.0, "stats_kernels_ms": 0.0, "gram_kernels_ms": 0.0}
+    with IncrementalPCA(f, dims, device) as fit:
+        for lo, hi in batches:
+            t0 = time.perf_counter()
+            fit.partial_fit(X[lo:hi])
+            t["stats_gram_ms"] += 1e3 * (time.perf_counter() - t0) - fit.timings["eigh_ms"]
+            t["eigh_ms"] += fit.timings["eigh_ms"]
+            t["stats_kernels_ms"] += fit.timings["stats_ms"]
+            t["gram_kernels_ms"] += fit.timings["gram_ms"]
+        t0 = time.perf_counter()
+        Y = fit.transform(X)
+        t["transform_ms"] = 1e3 * (time.perf_counter() - t0)
+        return IncrementalPCAResult(Y, fit, [hi - lo for lo, hi in batches], t)

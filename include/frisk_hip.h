@@ -339,6 +339,35 @@ int  frisk_mds_run(frisk_mds* h, const double* Y0, int32_t max_iter, double eps,
                    int32_t* n_iter_out, double* stress_trace_out);
 void frisk_mds_destroy(frisk_mds* h);
 
+/* Incremental PCA of the reference's --runProjection IncrementalPCA (sklearn.decomposition.IncrementalPCA(n_components=d,
+ * whiten=False, batch_size=None)), FP64 on `device`.  The handle keeps the fit on the device between batches: the rows seen, the
+ * column mean and variance (sklearn's _incremental_mean_and_var, operation for operation), the singular values S[d] and the
+ * components Vt[d][f].  One batch is two calls, with the eigendecomposition of the Gram matrix between them left to the caller:
+ * frisk_ipca_create: f features, d components.  FRISK_E_ARG unless f >= 1 and 1 <= d <= f.
+ * frisk_ipca_gram: X[b][f], one batch.  Computes the batch's mean / variance update and G_out[f][f] = AT A (exactly symmetric),
+ *   where A is the batch minus the new mean (first batch) or the stack of the d rows S_i Vt_i, the batch minus its own mean
+ *   and the row sqrt(seen / (seen + b) * b) (old mean - batch mean).  The eigenvectors of G are the right singular vectors of A,
+ *   its eigenvalues their squared singular values.  The fit itself does not change.  FRISK_E_ARG for b < 1, a first batch with
+ *   b < d, or a non-finite X.
+ * frisk_ipca_commit: S[d], Vt[d][f] of the batch last given to frisk_ipca_gram become the fit, with that batch's mean, variance
+ *   and row count.  FRISK_E_STATE without such a batch.
+ * frisk_ipca_get: n_seen, mean[f], var[f], S[d], Vt[d][f] of the fit (each nullable; FRISK_E_STATE for an array before the
+ *   first commit).  frisk_ipca_set replaces the fit (n_seen = 0: back to the unfitted state, the arrays are not read) and
+ *   drops a batch not yet committed.
+ * frisk_ipca_transform: Y_out[n][d] = (X - mean) V for any n >= 1, rows fed to the device in pieces; FRISK_E_STATE before the
+ *   first commit.
+ * frisk_ipca_last_ms: device time of the last frisk_ipca_gram in ms: which = 0 upload, 1 statistics + stack, 2 Gram; else -1.
+ * Every result is bit-identical from run to run. */
+typedef struct frisk_ipca frisk_ipca;
+int  frisk_ipca_create(int device, int64_t f, int32_t d, frisk_ipca** out);
+int  frisk_ipca_gram(frisk_ipca* h, const double* X, int64_t b, double* G_out);
+int  frisk_ipca_commit(frisk_ipca* h, const double* S, const double* Vt);
+int  frisk_ipca_get(frisk_ipca* h, int64_t* n_seen, double* mean, double* var, double* S, double* Vt);
+int  frisk_ipca_set(frisk_ipca* h, int64_t n_seen, const double* mean, const double* var, const double* S, const double* Vt);
+int  frisk_ipca_transform(frisk_ipca* h, const double* X, int64_t n, double* Y_out);
+double frisk_ipca_last_ms(const frisk_ipca* h, int which);
+void frisk_ipca_destroy(frisk_ipca* h);
+
 /* Page-locked host memory for result buffers: D2H copies into it are asynchronous and run at PCIe rate
  * (pageable buffers work too, at a fraction of it).  Free with frisk_host_free before frisk_destroy. */
 void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);

@@ -186,13 +186,14 @@ def coincident_case():
             "X": {"call": "RandomState(77).rand(12, 5)", "sha256": sha(X)}}
 
 
-def anomalies(ns):
-    """The fixture's anomalous windows and their symmetric k-mer proportions, as make_golden_projection.end_to_end computes them."""
+def anomalies(ns, pmax=3):
+    """The fixture's anomalous windows and their symmetric k-mer proportions (orders 1..pmax), as
+    make_golden_projection.end_to_end computes them."""
     import pandas as pd
     import shutil
     import tempfile
     fa = os.path.join(INP, MGP.FASTA)
-    m, k, w, inc, pmin, pmax = 1, 4, 200, 100, 1, 3
+    m, k, w, inc, pmin = 1, 4, 200, 100, 1
     tmp = tempfile.mkdtemp(prefix="frisk_gold_")
     a = MG.Args(fa, m=m, k=k, w=w, i=inc, tempDir=tmp)
     blank = ns["rangeMaps"](m, k)

@@ -10,13 +10,18 @@
   (tests/tsne_oracle.py, 20 iterations at n = 5 000);
   MDS (--mds-only, metric SMACOF, d = 2) at n = 5 000, 20 000 and 50 000 windows of F = 2 772: dissimilarity ms (the handle's
   create), ms per SMACOF step, iterations per start and the whole 5-start mds() ms; sklearn's MDS on the host at n = 2 000 and
-  5 000 (--no-gpu: only those); written to --out as well as printed.
+  5 000 (--no-gpu: only those); written to --out as well as printed;
+  IncrementalPCA (--ipca-only, d = 2, batches of 5 F = 13 860 rows) at n = 30 000 and 100 000 windows of F = 2 772: the whole
+  incremental_pca() call and its split (statistics + Gram with the batch's copies, eigh, transform; device events around the
+  statistics + stack kernels and around the Gram kernels), pca() on the same X, and sklearn's IncrementalPCA on the host at the
+  --ipca-cpu-ns sizes; written to --out as well as printed.
 
 Every GPU time is a host clock around one call, which ends in a device-to-host copy (so it includes the host-to-device copy of the
 input); each shape is run once untimed first.  --small: tiny sizes, for a profiler run.
 
     python tools/proj_timing.py [--small] [--no-cpu] [--tsne-only]
     python tools/proj_timing.py --mds-only [--ns 5000 20000] [--no-cpu | --no-gpu] [--out profiles/proj/mds_timing.json]
+    python tools/proj_timing.py --ipca-only [--ns 30000 100000] [--ipca-cpu-ns 30000] [--no-cpu] [--out profiles/proj/ipca_timing.json]
 """
 import argparse
 import json
@@ -54,12 +59,21 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--tsne-only", action="store_true", help="only the PY-TSNE legs")
     ap.add_argument("--mds-only", action="store_true", help="only the MDS legs")
+    ap.add_argument("--ipca-only", action="store_true", help="only the IncrementalPCA legs")
+    ap.add_argument("--ipca-cpu-ns", type=int, nargs="+", default=None, help="with --ipca-only: the sizes of sklearn's runs on the host")
     ap.add_argument("--no-gpu", action="store_true", help="with --mds-only: only sklearn on the host")
     ap.add_argument("--ns", type=int, nargs="+", default=None, help="with --mds-only: the GPU sizes")
     ap.add_argument("--out", default=None, help="with --mds-only: also write the JSON here")
     opts = ap.parse_args()
     if opts.mds_only:
         doc = json.dumps({"tool": "proj_timing", "mds": mds_legs(opts)})
+        print(doc)
+        if opts.out:
+            with open(opts.out, "w") as fh:
+                fh.write(doc + "\n")
+        return
+    if opts.ipca_only:
+        doc = json.dumps({"tool": "proj_timing", "ipca": ipca_legs(opts)})
         print(doc)
         if opts.out:
             with open(opts.out, "w") as fh:
@@ -176,6 +190,42 @@ def mds_legs(opts):
                     dissimilarity="euclidean", normalized_stress=False)
             ms, _ = _ms(m.fit_transform, X)
             out["sklearn_%d" % n] = {"ms": ms, "n_iter": int(m.n_iter_), "threads": os.cpu_count()}
+    return out
+
+
+def _blobs(n, f, seed):
+    """Three blobs of proportions (a PCA of structureless rows has no leading components to time a projection on)."""
+    rs = np.random.RandomState(seed)
+    centres = rs.dirichlet(np.full(f, 2.0), size=3)
+    X = rs.standard_gamma(centres[rs.randint(0, 3, n)] * 200.0 + 1e-3)
+    return X / X.sum(axis=1, keepdims=True)
+
+
+def ipca_legs(opts):
+    from frisk_amd import projection as P
+    F, d = 2772, 2
+    out = {"F": F, "d": d, "batch_size": 5 * F}
+    ns = opts.ns or ((3000,) if opts.small else (30000, 100000))
+    P.incremental_pca(_blobs(300, F, 1), d)         # first launches
+    for n in ns:
+        X = _blobs(n, F, n)
+        P.incremental_pca(X[:min(n, 2 * 5 * F + 7)], d)             # warm-up of the batch shapes
+        ms, r = _ms(P.incremental_pca, X, d)
+        t = r.timings
+        P.pca(X, d)
+        pms, pr = _ms(P.pca, X, d)
+        out[str(n)] = {"batches": r.batch_sizes, "incremental_pca_ms": ms, "stats_gram_ms": t["stats_gram_ms"], "eigh_ms": t["eigh_ms"],
+                       "transform_ms": t["transform_ms"], "stats_stack_kernels_ms": t["stats_kernels_ms"],
+                       "gram_kernels_ms": t["gram_kernels_ms"], "eigh_share": t["eigh_ms"] / ms,
+                       "gram_kernels_fp64_tflops": 2.0 * n * F * F / (t["gram_kernels_ms"] * 1e-3) / 1e12,
+                       "explained_variance": r.explained_variance_.tolist(), "pca_ms": pms, "pca_timings": pr.timings}
+    if not opts.no_cpu:
+        from sklearn.decomposition import IncrementalPCA
+        for n in opts.ipca_cpu_ns or ns:
+            X = _blobs(n, F, n)
+            m = IncrementalPCA(n_components=d, whiten=False, copy=True, batch_size=None)
+            ms, _ = _ms(lambda: m.fit(X).transform(X))
+            out["sklearn_%d" % n] = {"ms": ms, "threads": os.environ.get("OMP_NUM_THREADS") or os.cpu_count()}
     return out
 
 
