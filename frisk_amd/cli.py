@@ -9,6 +9,11 @@ caches, GFF3) and the same row echo on stdout.  Phase A and phase B run through 
 --runProjection PCA, PY-TSNE (the reference's exact t-SNE, Y0 seeded by --seed, 0 when not given), MDS (sklearn's metric MDS,
 its starts seeded the same way) or IncrementalPCA (sklearn's, in batches of 5 F rows) with --cluster DBSCAN / KMEANS runs
 frisk_amd.projection on the GPU and writes the cluster-labelled GFF3.
+--updateHMM (with --updateWin / --updateInc; the reference advertises them as a future function and never wired them) scans the
+query again with the fine window, segments that track with the device HMM (csrc/hmm_kernels.h), writes it to
+updateWin_<w>_inc_<i>_<hmmOutfile>, and - with --gffOutfile - writes the anomalies with every boundary moved to the nearest
+boundary of the fine track (the reference's unused updateHMM, L737-755) to HMMupdated_<gffOutfile>.  No other output changes.
+Skipped with a warning in a sharded job, under --exitAfter, and where the fine scan meets the reference's ZeroDivisionError.
 Out of scope here: the other projections (SKL-TSNE, NMF) and SPECTRAL clustering,
 --graphics (seaborn/matplotlib), --gffIn intersections (bedtools).
 Those options are accepted, as in the reference, and reported as unavailable if used.
@@ -86,9 +91,10 @@ def build_parser():
     p.add_argument("--kClusters", type=int, default=2)
     p.add_argument("--seed", default=None)
     p.add_argument("--chrmlist", default=None, nargs="+")
-    p.add_argument("--updateHMM", action="store_true", default=False)
-    p.add_argument("--updateWin", type=int, default=1000)
-    p.add_argument("--updateInc", type=int, default=500)
+    p.add_argument("--updateHMM", action="store_true", default=False,
+                   help="refine anomaly boundaries to the nearest boundary of a fine-scale HMM track (second scan)")
+    p.add_argument("--updateWin", type=int, default=1000, help="window length of the fine scan")
+    p.add_argument("--updateInc", type=int, default=500, help="increment of the fine scan")
     p.add_argument("--findSelf", action="store_true", default=False, help="report windows BELOW the threshold instead")
     return p
 
@@ -223,6 +229,33 @@ class _Clock:
             sys.stderr.write(json.dumps({"frisk_timing": dict(self.parts), "total_s": total}) + "\n")
 
 
+FINE_HMM_NATIVE = "gpu"         # GaussianHMM2(native=...) of the fine track: the device model
+
+
+def _fine_model(device):
+    from .hmm import GaussianHMM2
+    return GaussianHMM2(native=FINE_HMM_NATIVE, device=device)
+
+
+def fineTrackName(args):
+    return "updateWin_%s_inc_%s_%s" % (args.updateWin, args.updateInc, args.hmmOutfile)
+
+
+def _fine_scan(args, hp, querySeq, clock):
+    """--updateHMM, step 1: the query again with w = --updateWin, inc = --updateInc, same profile, same --scaffoldsAll (no RIP
+    columns: nothing reads them).  The table is neither echoed, written nor cached.  None where the reference's scan would die."""
+    fine = argparse.Namespace(**vars(args))
+    fine.windowlen, fine.increment, fine.RIP = args.updateWin, args.updateInc, False
+    try:
+        table, _res = hp.scanTable(fine, querySeq)
+    except ZeroDivisionError:
+        log.warning("--updateHMM skipped: the fine scan (-w %s -i %s) meets a window whose max-mer prefix has zero weight in the "
+                    "host profile (the reference's ZeroDivisionError).", args.updateWin, args.updateInc)
+        table = None
+    clock.lap("fine scan (--updateHMM)")
+    return table
+
+
 def _seed(args):
     # the reference passes random_state=None and leaves numpy unseeded (not reproducible); --seed, 0 when not given, seeds here
     return int(args.seed) if args.seed is not None else 0
@@ -310,6 +343,12 @@ def _main(argv=None):
     clustering = projection and args.cluster in CLUSTERINGS
     for opt, why in unavailable(args):
         log.warning("--%s is not available in this build: %s", opt, why)
+    update = bool(args.updateHMM)
+    if update and (sharded or args.exitAfter):
+        log.warning("--updateHMM skipped: %s.", "a sharded job keeps tiles cut for the main window and increment" if sharded
+                    else "--exitAfter %s stops before the features" % args.exitAfter)
+        update = False
+    fine_table = None
 
     from .hotpath import HotPath
     from . import distributed as D
@@ -441,6 +480,8 @@ def _main(argv=None):
                 clock.lap("score table text + window pickle started" if zero is None else "score table text")
             if zero is not None:
                 raise zero
+        if update:              # before the HotPath is closed; loads the sequence where both caches were hit (the profile is set)
+            fine_table = _fine_scan(args, hp, querySeq, clock)
     except BaseException:
         for th in out_threads:
             th.join()
@@ -475,6 +516,18 @@ def _main(argv=None):
             log.info("HMM segmentation: %s state features (fit: %s EM rounds, log-likelihood %s)", len(intervals),
                      getattr(_model, "n_iter_", "?"), getattr(_model, "loglik_", "?"))
             clock.lap("HMM segmentation + GFF")
+        fine_intervals = None
+        if fine_table is not None:                                          # --updateHMM: the fine track, device model
+            from .hmm import hmm2BED, hmmBED2GFF
+            if not np.any(~np.isnan(np.where(fine_table.kld_is_int0 != 0, 0.0, fine_table.kld))):
+                log.warning("--updateHMM skipped: the fine scan (-w %s -i %s) scored no window.", args.updateWin, args.updateInc)
+            else:
+                fine_intervals, fmodel = hmm2BED(fine_table, _fine_model(local_rank))
+                with open(os.path.join(args.tempDir, fineTrackName(args)), "w") as fh:
+                    fh.writelines(hmmBED2GFF(fine_intervals))
+                log.info("Fine HMM track (-w %s -i %s, %s windows): %s state features (fit: %s EM rounds, log-likelihood %s)",
+                         args.updateWin, args.updateInc, len(fine_table), len(fine_intervals), fmodel.n_iter_, fmodel.loglik_)
+            clock.lap("fine HMM segmentation + GFF (--updateHMM)")
         if args.runProjection:                                              # L1556-1596: counts for the projection
             from .fasta import readFasta
             from .projection import symmetricCounts
@@ -502,6 +555,10 @@ def _main(argv=None):
             with open(os.path.join(args.tempDir, args.gffOutfile), "w") as fh:
                 for line in pp.anomaly2GFF(anomalies, args):
                     fh.write(line)
+            if fine_intervals is not None:                                  # --updateHMM: the same set, boundaries refined
+                refined, _kept = pp.refineAnomalies(fine_intervals, anomalies)
+                with open(os.path.join(args.tempDir, "HMMupdated_" + args.gffOutfile), "w") as fh:
+                    fh.writelines(pp.anomaly2GFF(refined, args))
             if clustering:                                                  # L1688-1697
                 with open(os.path.join(args.tempDir, pp.clusterGffName(args)), "w") as fh:
                     fh.writelines(pp.anomClust2gff(pp.cluster_rows(anomLabels, y_pred)))

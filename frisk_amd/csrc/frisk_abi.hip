@@ -33,6 +33,7 @@
 #include "tsne_kernels.h"
 #include "mds_kernels.h"
 #include "ipca_kernels.h"
+#include "hmm_kernels.h"
 
 #define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
 #define FRISK_SIDE_SHARE 0.06       // 4-bit bulk takes the side-table form when the plain form would hand on more than this share of the sample
@@ -2087,6 +2088,36 @@ int frisk_kmeans(int device, const double* Y, int64_t n, int32_t d, int32_t k, c
     if (!on.ok) return FRISK_E_HIP;
     return frisk_proj::kmeans(Y, n, d, k, init_centers, max_iter, tol, labels_out, centers_out, inertia_out, n_iter_out)
                ? FRISK_E_HIP : FRISK_OK;
+}
+
+// ---- the same HMM on the device (hmm_kernels.h): context-free, host arrays in and out, device memory freed on every return
+int frisk_hmm_fit_gpu(int device, const double* x, int64_t n, int32_t n_iter, double tol, double min_covar, double covars_prior,
+                      double* means, double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
+    if (!x || n < 1 || n > (int64_t(1) << 40) || n_iter < 0 || !means || !covars || !startprob || !transmat || !all_finite(x, n))
+        return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    frisk_hmm::Fit F;
+    if (frisk_hmm_gpu::fit(x, n, n_iter, tol, min_covar, covars_prior, F)) return FRISK_E_HIP;
+    for (int i = 0; i < 2; ++i) { means[i] = F.m.means[i]; covars[i] = F.m.covars[i]; startprob[i] = F.m.startprob[i]; }
+    for (int i = 0; i < 4; ++i) transmat[i] = F.m.transmat[i];
+    if (loglik) *loglik = F.loglik;
+    if (iters) *iters = F.iters;
+    return FRISK_OK;
+}
+
+int frisk_hmm_viterbi_gpu(int device, const double* x, const int64_t* seg_off, int32_t n_seg, const double* means,
+                          const double* covars, const double* startprob, const double* transmat, int8_t* states) {
+    if (n_seg < 0 || !seg_off || !means || !covars || !startprob || !transmat) return FRISK_E_ARG;
+    for (int32_t s = 0; s < n_seg; ++s) if (seg_off[s + 1] < seg_off[s]) return FRISK_E_ARG;
+    if (n_seg == 0 || seg_off[n_seg] == seg_off[0]) return FRISK_OK;
+    if (!x || !states || seg_off[n_seg] - seg_off[0] > (int64_t(1) << 40)) return FRISK_E_ARG;
+    frisk_hmm::Model m;
+    for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
+    for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    return frisk_hmm_gpu::viterbi_segments(x, seg_off, n_seg, m, states) ? FRISK_E_HIP : FRISK_OK;
 }
 
 // ---- exact t-SNE (tsne_kernels.h): a handle whose state stays on its device between calls

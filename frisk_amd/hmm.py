@@ -15,6 +15,8 @@ Two implementations of the same model: the numpy one below (`native=False`: one 
 fine up to ~10^4 windows) and the library's host-native one (csrc/hmm_host.h through frisk_hmm_fit / frisk_hmm_viterbi: scaled
 forward-backward over fixed pieces in parallel, Viterbi per scaffold in parallel - 3 M windows in a fraction of a second),
 which `fit` / `predict` use by default.  They agree to rounding (parameters ~1e-12, tests).
+A third, `native="gpu"` (csrc/hmm_kernels.h through frisk_hmm_fit_gpu / frisk_hmm_viterbi_gpu, on `device`), is the same piece
+scheme on the GPU for the fine track of --updateHMM; nothing uses it unless asked, and without a GPU it raises.
 """
 import ctypes as C
 
@@ -34,8 +36,12 @@ def _logsumexp(a, axis):
 class GaussianHMM2:
     """1-D, 2 states, one variance per state ("full" covariance of one feature)."""
 
-    def __init__(self, n_iter=10, tol=1e-2, min_covar=1e-3, covars_prior=1e-2, native=True):
+    def __init__(self, n_iter=10, tol=1e-2, min_covar=1e-3, covars_prior=1e-2, native=True, device=0):
+        """native: False - the numpy specification; True - the host-native library (default); "gpu" - the HIP kernels on `device`."""
+        if native not in (False, True, "gpu"):
+            raise ValueError("native must be False, True or 'gpu', not %r" % (native,))
         self.n_iter, self.tol, self.min_covar, self.covars_prior, self.native = n_iter, tol, min_covar, covars_prior, native
+        self.device = int(device)
         self.loglik_, self.n_iter_ = None, 0
 
     # -- initialisation: 2-means from the extremes, hmmlearn-style shared variance, flat start / transitions
@@ -75,8 +81,14 @@ class GaussianHMM2:
         means, covars, start, trans = np.zeros(2), np.zeros(2), np.zeros(2), np.zeros(4)
         ll, iters = C.c_double(), C.c_int32()
         p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
-        rc = lib.frisk_hmm_fit(p(x), x.size, int(self.n_iter), float(self.tol), float(self.min_covar), float(self.covars_prior),
-                               p(means), p(covars), p(start), p(trans), C.byref(ll), C.byref(iters))
+        tail = (p(x), x.size, int(self.n_iter), float(self.tol), float(self.min_covar), float(self.covars_prior),
+                p(means), p(covars), p(start), p(trans), C.byref(ll), C.byref(iters))
+        if self.native == "gpu":
+            rc = lib.frisk_hmm_fit_gpu(self.device, *tail)
+            if rc == _ffi.E_HIP:
+                raise _ffi.FriskHipError(rc, "frisk_hmm_fit_gpu on device %d" % self.device)
+        else:
+            rc = lib.frisk_hmm_fit(*tail)
         if rc != _ffi.OK:
             raise ValueError("frisk_hmm_fit: the scores must be finite and at least one (code %d)" % rc)
         self.means_, self.covars_, self.startprob_, self.transmat_ = means, covars, start, trans.reshape(2, 2)
@@ -95,7 +107,13 @@ class GaussianHMM2:
         from . import _ffi
         p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
         pars = [np.ascontiguousarray(a, dtype=np.float64) for a in (self.means_, self.covars_, self.startprob_, np.ravel(self.transmat_))]
-        rc = _ffi.lib().frisk_hmm_viterbi(p(x), p(seg_off), int(seg_off.size - 1), p(pars[0]), p(pars[1]), p(pars[2]), p(pars[3]), p(out))
+        tail = (p(x), p(seg_off), int(seg_off.size - 1), p(pars[0]), p(pars[1]), p(pars[2]), p(pars[3]), p(out))
+        if self.native == "gpu":
+            rc = _ffi.lib().frisk_hmm_viterbi_gpu(self.device, *tail)
+            if rc == _ffi.E_HIP:
+                raise _ffi.FriskHipError(rc, "frisk_hmm_viterbi_gpu on device %d" % self.device)
+        else:
+            rc = _ffi.lib().frisk_hmm_viterbi(*tail)
         if rc != _ffi.OK:
             raise ValueError("frisk_hmm_viterbi failed (code %d)" % rc)
         return out
@@ -188,13 +206,15 @@ def range2interval(rangeList, windows, state):
 def hmm2BED(rows, model=None):
     """rows: (name, start, stop, KLD, ...) in table order.  Fits the model on all non-NaN scores stacked
     (L1541), decodes per scaffold, and returns intervals (name, start, stop, 'State1'|'State2') as STRINGS
-    sorted the way the reference sorts them - lexicographically on the string fields (L783)."""
+    sorted the way the reference sorts them - lexicographically on the string fields (L783).  A GaussianHMM2 that has not
+    been fitted (the way to choose its `native=` / `device=`) is fitted here, as the default one is."""
+    unfitted = isinstance(model, GaussianHMM2) and not hasattr(model, "means_")
     if hasattr(rows, "kld"):            # a ScoreTable: everything on the columns (3 M rows at GRCh38 scale)
         t = rows
         kld = np.where(t.kld_is_int0 != 0, 0.0, t.kld)
         ok = np.nonzero(~np.isnan(kld))[0]
-        if model is None:
-            model = GaussianHMM2().fit(kld[ok])
+        if model is None or unfitted:
+            model = (model or GaussianHMM2()).fit(kld[ok])
         if ok.size == 0:
             return [], model
         # scaffolds BY NAME in order of first appearance (L762: Counter over the name column; L765: all rows of that name)
@@ -228,8 +248,8 @@ def hmm2BED(rows, model=None):
                zip(run_name, t.start[rr[a]].tolist(), t.stop[rr[b]].tolist(), states[a].tolist())]
         return sorted(out, key=lambda x: (x[0], x[1], x[2])), model
     good = [r for r in rows if not (isinstance(r[3], float) and r[3] != r[3])]
-    if model is None:
-        model = GaussianHMM2().fit(np.array([float(r[3]) for r in good]))
+    if model is None or unfitted:
+        model = (model or GaussianHMM2()).fit(np.array([float(r[3]) for r in good]))
     names = []
     for r in good:
         if r[0] not in names:

@@ -2,13 +2,15 @@
 interval merging, GFF3 writers.  numpy/pandas on <= millions of floats - no kernels here.
 
 Reference counterparts (frisk/__init__.py): FDBins L508-513, otsu L515-543, setKLDThresh L664-690,
-thresholdKLD L647-662, anomaly2GFF L553-567, thresholdRIP L692-720, RIP2GFF L577-587, natural_sort L85-89.
+thresholdKLD L647-662, anomaly2GFF L553-567, thresholdRIP L692-720, RIP2GFF L577-587, natural_sort L85-89,
+updateHMM L737-755 (the reference never calls it; --updateHMM does here, cli.py).
 The reference delegates interval merging to the external `bedtools` binary through pybedtools
 (`merge -d D -c 4,4,4 -o max,min,mean`, `window -w 0 -u`), which is not available here: `merge_intervals`
 restates the documented bedtools semantics (sorted input; features whose gap is <= D are merged, so
 book-ended features merge at D = 0; numeric summaries printed with bedtools' default precision `-prec 5`).
 Parity for that part is pinned by construction and by tests only, not by the reference's own output.
 """
+import logging
 import math
 import os
 import re
@@ -257,6 +259,55 @@ def anomaly2GFF(features, args, category="Kmer-anomaly", version=FRISK_VERSION):
         if n == 1:
             yield "##gff-version 3\n"
         yield "\t".join([str(f[0]), "frisk_" + version, category, str(f[1]), str(f[2]), ".", "+", ".", ";".join(attrs)]) + "\n"
+
+
+def updateHMM(smallHMM, bigThresh):
+    """The reference's updateHMM (L737-755), operation for operation: every boundary of a coarse annotation (bigThresh: records
+    name, start, stop, ...) moves to the nearest boundary of the fine HMM track (smallHMM: records name, start, stop, ...) on the
+    same scaffold.  The scaffold's boundary list holds every start and every stop of its fine intervals in interval order; on
+    equal distance the first in that order wins (min with a key).  Returns [(name, str(left), str(right))] - the records the
+    reference hands to pybedtools.BedTool.  A scaffold without a fine interval raises KeyError, as there."""
+    hmmBounds = {}
+    for i in smallHMM:
+        hmmBounds.setdefault(i[0], []).extend((int(i[1]), int(i[2])))
+    updated = []
+    for y in bigThresh:
+        newLeft = min(hmmBounds[y[0]], key=lambda x: abs(x - int(y[1])))
+        newRight = min(hmmBounds[y[0]], key=lambda x: abs(x - int(y[2])))
+        updated.append((y[0], str(newLeft), str(newRight)))
+    return updated
+
+
+def refineAnomalies(fine_intervals, anomalies, emit=None):
+    """updateHMM around the cases the reference never had to decide (--updateHMM, cli.py): an anomaly on a scaffold with no
+    fine interval keeps its boundaries (the reference would raise KeyError), and so does one whose snapped left is >= its snapped
+    right; each is logged at INFO, and their total once.  Every other field of an anomaly's record is carried through unchanged.
+    Returns (records, number kept as they were)."""
+    emit = emit or logging.getLogger("frisk").info
+    lists = {}
+    for i in fine_intervals:
+        lists.setdefault(i[0], []).extend((int(i[1]), int(i[2])))
+    bounds = {k: np.asarray(v, dtype=np.int64) for k, v in lists.items()}      # (argmin: the first of equal distances, as min)
+    out, kept = [], 0
+    for f in anomalies:
+        f = tuple(f)
+        b = bounds.get(f[0])
+        if b is None:
+            emit("Anomaly %s:%s-%s keeps its boundaries: no fine HMM interval on this scaffold." % (f[0], f[1], f[2]))
+            out.append(f)
+            kept += 1
+            continue
+        left, right = int(b[np.argmin(np.abs(b - int(f[1])))]), int(b[np.argmin(np.abs(b - int(f[2])))])
+        if left >= right:
+            emit("Anomaly %s:%s-%s keeps its boundaries: the nearest fine HMM boundaries %s and %s do not span an interval."
+                 % (f[0], f[1], f[2], left, right))
+            out.append(f)
+            kept += 1
+            continue
+        cast = type(f[1]) if isinstance(f[1], (int, str)) else int
+        out.append((f[0], cast(left), cast(right)) + f[3:])
+    emit("Refined %s of %s anomalies to fine HMM boundaries; %s kept as they were." % (len(out) - kept, len(out), kept))
+    return out, kept
 
 
 def thresholdRIP(table, args):

@@ -269,6 +269,17 @@ int frisk_hmm_fit(const double* x, int64_t n, int32_t n_iter, double tol, double
 int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, const double* means, const double* covars,
                       const double* startprob, const double* transmat, int8_t* states);
 
+/* The same model on `device` (csrc/hmm_kernels.h), without a context: host arrays in and out, FP64 throughout, bit-identical from
+ * run to run (the sequence is cut into a number of pieces that depends on n alone, the sufficient statistics are added in a fixed
+ * order, no floating-point atomics); the stop rule of the fit is evaluated in double on the host once per round.  Arguments and
+ * results as frisk_hmm_fit / frisk_hmm_viterbi; the fitted numbers agree with the host form to rounding (a different exp / log
+ * and reassociated sums), the Viterbi states are those of the host form wherever no decision is closer than rounding (ties to
+ * the lower state).  FRISK_E_ARG on a bad argument (n < 1, non-finite scores, a decreasing seg_off), FRISK_E_HIP otherwise. */
+int frisk_hmm_fit_gpu(int device, const double* x, int64_t n, int32_t n_iter, double tol, double min_covar, double covars_prior,
+                      double* means, double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters);
+int frisk_hmm_viterbi_gpu(int device, const double* x, const int64_t* seg_off, int32_t n_seg, const double* means,
+                          const double* covars, const double* startprob, const double* transmat, int8_t* states);
+
 /* Projection and clustering of the anomalous windows' k-mer proportions (the reference's L1597-1697: sklearn PCA, DBSCAN and
  * KMeans), on `device`, without a context.  Inputs and outputs are host arrays (row-major); every result is bit-identical from
  * run to run (fixed-order reductions, no floating-point atomics).  Each returns FRISK_OK, FRISK_E_ARG on a bad argument (n < 1,
