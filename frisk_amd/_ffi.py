@@ -77,6 +77,8 @@ SYMBOLS = [
     ("frisk_hmm_fit_gpu", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
                                     C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     ("frisk_hmm_viterbi_gpu", C.c_int, [C.c_int, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("frisk_hmm_estep", C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("frisk_hmm_estep_gpu", C.c_int, [C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("frisk_proj_cov", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, _P, _P]),
     ("frisk_proj_transform", C.c_int, [C.c_int, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P]),
     ("frisk_dbscan", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),

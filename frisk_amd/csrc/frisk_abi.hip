@@ -2043,6 +2043,37 @@ int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, co
     return FRISK_OK;
 }
 
+namespace {
+// x and the model of one E step: finite, variances > 0, probabilities in [0, 1]
+bool estep_args_ok(const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
+                   const double* transmat, const double* stats_out) {
+    if (!x || n < 1 || !means || !covars || !startprob || !transmat || !stats_out) return false;
+    for (int i = 0; i < 2; ++i) {
+        if (!std::isfinite(means[i]) || !std::isfinite(covars[i]) || !(covars[i] > 0.0)) return false;
+        if (!(startprob[i] >= 0.0 && startprob[i] <= 1.0)) return false;
+    }
+    for (int i = 0; i < 4; ++i) if (!(transmat[i] >= 0.0 && transmat[i] <= 1.0)) return false;
+    for (int64_t t = 0; t < n; ++t) if (!std::isfinite(x[t])) return false;
+    return true;
+}
+frisk_hmm::Model model_of(const double* means, const double* covars, const double* startprob, const double* transmat) {
+    frisk_hmm::Model m;
+    for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
+    for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];
+    return m;
+}
+}  // namespace
+
+int frisk_hmm_estep(const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
+                    const double* transmat, double* post_out, double* stats_out) {
+    if (!estep_args_ok(x, n, means, covars, startprob, transmat, stats_out)) return FRISK_E_ARG;
+    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
+    frisk_hmm::Work w(n);
+    stats_out[8] = frisk_hmm::e_step(x, n, m, w, stats_out);
+    if (post_out) std::copy(w.A.begin(), w.A.end(), post_out);
+    return FRISK_OK;
+}
+
 int64_t frisk_last_scan_stat(const frisk_ctx* c, int which) { return (c && which >= 0 && which < 5) ? c->scan_stat[which] : -1; }
 
 // ---- projection and clustering (proj_kernels.h): context-free, host arrays in and out, device memory freed on every return
@@ -2106,12 +2137,22 @@ int frisk_hmm_fit_gpu(int device, const double* x, int64_t n, int32_t n_iter, do
     return FRISK_OK;
 }
 
+int frisk_hmm_estep_gpu(int device, const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
+                        const double* transmat, double* post_out, double* stats_out) {
+    if (!estep_args_ok(x, n, means, covars, startprob, transmat, stats_out) || n > (int64_t(1) << 40)) return FRISK_E_ARG;
+    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    return frisk_hmm_gpu::e_step_only(x, n, m, post_out, stats_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
 int frisk_hmm_viterbi_gpu(int device, const double* x, const int64_t* seg_off, int32_t n_seg, const double* means,
                           const double* covars, const double* startprob, const double* transmat, int8_t* states) {
     if (n_seg < 0 || !seg_off || !means || !covars || !startprob || !transmat) return FRISK_E_ARG;
     for (int32_t s = 0; s < n_seg; ++s) if (seg_off[s + 1] < seg_off[s]) return FRISK_E_ARG;
     if (n_seg == 0 || seg_off[n_seg] == seg_off[0]) return FRISK_OK;
     if (!x || !states || seg_off[n_seg] - seg_off[0] > (int64_t(1) << 40)) return FRISK_E_ARG;
+    if (!all_finite(x + seg_off[0], seg_off[n_seg] - seg_off[0])) return FRISK_E_ARG;
     frisk_hmm::Model m;
     for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
     for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];

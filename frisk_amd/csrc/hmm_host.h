@@ -85,6 +85,147 @@ inline void init(const double* x, int64_t n, double min_covar, Model& m) {
 
 struct Fit { Model m; double loglik; int iters; };
 
+// the arrays of one sequence: allocated once, used by every round
+struct Work {
+    int P;
+    std::vector<double> B, A;                                       // scaled emissions; forward vectors, then posteriors
+    std::vector<double> pm, edge, edgeB, pll, acc;
+    explicit Work(int64_t n)
+        : P(int(std::min<int64_t>(PIECES, std::max<int64_t>(1, n / 2048)))), B(size_t(n) * 2), A(size_t(n) * 2), pm(size_t(P) * 4),
+          edge((size_t(P) + 1) * 2), edgeB((size_t(P) + 1) * 2), pll(size_t(P)), acc(size_t(P) * 8) {}
+};
+
+// one E step of model m (what a round of fit runs, and all frisk_hmm_estep runs): the posteriors are left in w.A, the sums of
+// gamma (2), gamma x (2) and xi (4) in S; returns the log-likelihood
+inline double e_step(const double* x, int64_t n, const Model& m, Work& w, double* S) {
+    const int P = w.P;
+    std::vector<double>&B = w.B, &A = w.A, &pm = w.pm, &edge = w.edge, &edgeB = w.edgeB, &pll = w.pll, &acc = w.acc;
+    const double lc0 = std::log(m.covars[0]), lc1 = std::log(m.covars[1]), ic0 = 1.0 / m.covars[0], ic1 = 1.0 / m.covars[1];
+    const double a00 = m.transmat[0], a01 = m.transmat[1], a10 = m.transmat[2], a11 = m.transmat[3];
+    // 1. scaled emissions + the product of every piece's forward steps (row convention: alpha_t = (alpha_{t-1} A) o b_t)
+    parallel_for(P, [&](int p) {
+        const int64_t a = n * p / P, b = n * (p + 1) / P;
+        double m00 = 1, m01 = 0, m10 = 0, m11 = 1, ll = 0;
+        for (int64_t t = a; t < b; ++t) {
+            const double d0 = x[t] - m.means[0], d1 = x[t] - m.means[1];
+            const double l0 = -0.5 * ((LOG2PI + lc0) + d0 * d0 * ic0), l1 = -0.5 * ((LOG2PI + lc1) + d1 * d1 * ic1);
+            const double mx = std::max(l0, l1);
+            const double b0 = std::exp(l0 - mx), b1 = std::exp(l1 - mx);
+            B[size_t(t) * 2] = b0; B[size_t(t) * 2 + 1] = b1;
+            ll += mx;
+            if (t == 0) continue;                               // (the first window's step is the start vector, not a transition)
+            const double s00 = a00 * b0, s01 = a01 * b1, s10 = a10 * b0, s11 = a11 * b1;
+            const double n00 = m00 * s00 + m01 * s10, n01 = m00 * s01 + m01 * s11;
+            const double n10 = m10 * s00 + m11 * s10, n11 = m10 * s01 + m11 * s11;
+            const double r = 1.0 / (n00 + n01 + n10 + n11);
+            m00 = n00 * r; m01 = n01 * r; m10 = n10 * r; m11 = n11 * r;
+        }
+        pm[size_t(p) * 4] = m00; pm[size_t(p) * 4 + 1] = m01; pm[size_t(p) * 4 + 2] = m10; pm[size_t(p) * 4 + 3] = m11;
+        pll[size_t(p)] = ll;
+    });
+    // 2. forward vector in front of every piece (normalised), serial over the pieces
+    {
+        double v0 = m.startprob[0] * B[0], v1 = m.startprob[1] * B[1];
+        edge[0] = v0; edge[1] = v1;                             // piece 0 starts from the UNnormalised first vector
+        double s = v0 + v1;
+        v0 /= s; v1 /= s;
+        for (int p = 0; p < P; ++p) {
+            const double* M = &pm[size_t(p) * 4];
+            const double w0 = v0 * M[0] + v1 * M[2], w1 = v0 * M[1] + v1 * M[3];
+            s = w0 + w1;
+            v0 = w0 / s; v1 = w1 / s;
+            if (p + 1 < P) { edge[size_t(p + 1) * 2] = v0; edge[size_t(p + 1) * 2 + 1] = v1; }
+        }
+    }
+    // 3. forward vectors of every window, and the log-likelihood
+    parallel_for(P, [&](int p) {
+        const int64_t a = n * p / P, b = n * (p + 1) / P;
+        double v0, v1, ll = 0;
+        int64_t t = a;
+        if (p == 0) {
+            const double s = edge[0] + edge[1];
+            ll += std::log(s);
+            v0 = edge[0] / s; v1 = edge[1] / s;
+            A[0] = v0; A[1] = v1;
+            t = 1;
+        } else { v0 = edge[size_t(p) * 2]; v1 = edge[size_t(p) * 2 + 1]; }
+        double prod = 1.0;                                      // the scales, four to a logarithm (each is >= the smallest transition
+        int held = 0;                                           // probability: one of the two scaled emissions is exactly 1)
+        for (; t < b; ++t) {
+            const double w0 = (v0 * a00 + v1 * a10) * B[size_t(t) * 2], w1 = (v0 * a01 + v1 * a11) * B[size_t(t) * 2 + 1];
+            const double s = w0 + w1, r = 1.0 / s;
+            prod *= s;
+            if (++held == 4 || prod < 1e-200) { ll += std::log(prod); prod = 1.0; held = 0; }
+            v0 = w0 * r; v1 = w1 * r;
+            A[size_t(t) * 2] = v0; A[size_t(t) * 2 + 1] = v1;
+        }
+        ll += std::log(prod);
+        pll[size_t(p)] += ll;
+    });
+    double ll = 0;
+    for (int p = 0; p < P; ++p) ll += pll[size_t(p)];
+    // 4. the product of every piece's backward steps (column convention: beta_t = A (b_{t+1} o beta_{t+1}))
+    parallel_for(P, [&](int p) {
+        const int64_t a = n * p / P, b = n * (p + 1) / P;
+        double m00 = 1, m01 = 0, m10 = 0, m11 = 1;
+        for (int64_t t = b - 1; t >= a; --t) {                  // beta_{t-1} from beta_t: the step uses window t's emissions
+            if (t == 0) break;
+            const double b0 = B[size_t(t) * 2], b1 = B[size_t(t) * 2 + 1];
+            const double s00 = a00 * b0, s01 = a01 * b1, s10 = a10 * b0, s11 = a11 * b1;      // S = A diag(b_t)
+            const double n00 = s00 * m00 + s01 * m10, n01 = s00 * m01 + s01 * m11;            // S M
+            const double n10 = s10 * m00 + s11 * m10, n11 = s10 * m01 + s11 * m11;
+            const double r = 1.0 / (n00 + n01 + n10 + n11);
+            m00 = n00 * r; m01 = n01 * r; m10 = n10 * r; m11 = n11 * r;
+        }
+        pm[size_t(p) * 4] = m00; pm[size_t(p) * 4 + 1] = m01; pm[size_t(p) * 4 + 2] = m10; pm[size_t(p) * 4 + 3] = m11;
+    });
+    // 5. backward vector of every piece's LAST window, serial from the end: E[P] = beta of the sequence's last window (flat),
+    //    E[p] = M_p E[p + 1] (M_p = the steps of all of piece p's windows: it carries beta from p's last window to p-1's last)
+    {
+        double v0 = 0.5, v1 = 0.5;
+        edgeB[size_t(P) * 2] = v0; edgeB[size_t(P) * 2 + 1] = v1;
+        for (int p = P - 1; p >= 1; --p) {
+            const double* M = &pm[size_t(p) * 4];
+            const double w0 = M[0] * v0 + M[1] * v1, w1 = M[2] * v0 + M[3] * v1;
+            const double s = w0 + w1;
+            v0 = w0 / s; v1 = w1 / s;
+            edgeB[size_t(p) * 2] = v0; edgeB[size_t(p) * 2 + 1] = v1;
+        }
+    }
+    // 6. walk every piece backwards: posteriors (into A), transition posteriors, and the M step's sums
+    parallel_for(P, [&](int p) {
+        const int64_t a = n * p / P, b = n * (p + 1) / P;
+        double be0 = edgeB[size_t(p + 1) * 2], be1 = edgeB[size_t(p + 1) * 2 + 1];        // beta of the piece's last window
+        double g0s = 0, g1s = 0, gx0 = 0, gx1 = 0, x00 = 0, x01 = 0, x10 = 0, x11 = 0;
+        for (int64_t t = b - 1; t >= a; --t) {
+            const double al0 = A[size_t(t) * 2], al1 = A[size_t(t) * 2 + 1];
+            // posterior of window t
+            double g0 = al0 * be0, g1 = al1 * be1;
+            const double gr = 1.0 / (g0 + g1);
+            g0 *= gr; g1 *= gr;
+            A[size_t(t) * 2] = g0; A[size_t(t) * 2 + 1] = g1;
+            g0s += g0; g1s += g1; gx0 += g0 * x[t]; gx1 += g1 * x[t];
+            if (t == 0) break;
+            // transition posterior between windows t-1 and t, and beta of window t-1
+            const double b0 = B[size_t(t) * 2] * be0, b1 = B[size_t(t) * 2 + 1] * be1;
+            // forward vector of window t-1: still in A inside the piece; the last window of the piece before belongs to another
+            // task's walk (which turns it into a posterior) - its forward vector is the edge this piece started from
+            const double p0 = t > a ? A[size_t(t - 1) * 2] : edge[size_t(p) * 2], p1 = t > a ? A[size_t(t - 1) * 2 + 1] : edge[size_t(p) * 2 + 1];
+            const double e00 = p0 * a00 * b0, e01 = p0 * a01 * b1, e10 = p1 * a10 * b0, e11 = p1 * a11 * b1;
+            const double er = 1.0 / (e00 + e01 + e10 + e11);
+            x00 += e00 * er; x01 += e01 * er; x10 += e10 * er; x11 += e11 * er;
+            const double nb0 = a00 * b0 + a01 * b1, nb1 = a10 * b0 + a11 * b1;
+            const double br = 1.0 / (nb0 + nb1);
+            be0 = nb0 * br; be1 = nb1 * br;
+        }
+        double* q = &acc[size_t(p) * 8];
+        q[0] = g0s; q[1] = g1s; q[2] = gx0; q[3] = gx1; q[4] = x00; q[5] = x01; q[6] = x10; q[7] = x11;
+    });
+    for (int k = 0; k < 8; ++k) S[k] = 0;
+    for (int p = 0; p < P; ++p) for (int k = 0; k < 8; ++k) S[k] += acc[size_t(p) * 8 + k];
+    return ll;
+}
+
 // Baum-Welch, GaussianHMM2.fit: n_iter rounds at most, stop when the log-likelihood gains less than tol (the parameters of the
 // round that met the test are kept, as there)
 inline Fit fit(const double* x, int64_t n, int n_iter, double tol, double min_covar, double covars_prior) {
@@ -93,135 +234,13 @@ inline Fit fit(const double* x, int64_t n, int n_iter, double tol, double min_co
     Model& m = F.m;
     F.loglik = -std::numeric_limits<double>::infinity();
     F.iters = 0;
-    const int P = int(std::min<int64_t>(PIECES, std::max<int64_t>(1, n / 2048)));
-    std::vector<double> B(size_t(n) * 2), A(size_t(n) * 2);           // scaled emissions; forward vectors, then posteriors
-    const size_t np_ = size_t(P);
-    std::vector<double> pm(np_ * 4), edge((np_ + 1) * 2), edgeB((np_ + 1) * 2), pll(np_), acc(np_ * 8);
+    Work w(n);
+    const int P = w.P;
+    std::vector<double>&A = w.A, &acc = w.acc;
     double prev = -std::numeric_limits<double>::infinity();
     for (int it = 0; it < n_iter; ++it) {
-        const double lc0 = std::log(m.covars[0]), lc1 = std::log(m.covars[1]), ic0 = 1.0 / m.covars[0], ic1 = 1.0 / m.covars[1];
-        const double a00 = m.transmat[0], a01 = m.transmat[1], a10 = m.transmat[2], a11 = m.transmat[3];
-        // 1. scaled emissions + the product of every piece's forward steps (row convention: alpha_t = (alpha_{t-1} A) o b_t)
-        parallel_for(P, [&](int p) {
-            const int64_t a = n * p / P, b = n * (p + 1) / P;
-            double m00 = 1, m01 = 0, m10 = 0, m11 = 1, ll = 0;
-            for (int64_t t = a; t < b; ++t) {
-                const double d0 = x[t] - m.means[0], d1 = x[t] - m.means[1];
-                const double l0 = -0.5 * ((LOG2PI + lc0) + d0 * d0 * ic0), l1 = -0.5 * ((LOG2PI + lc1) + d1 * d1 * ic1);
-                const double mx = std::max(l0, l1);
-                const double b0 = std::exp(l0 - mx), b1 = std::exp(l1 - mx);
-                B[size_t(t) * 2] = b0; B[size_t(t) * 2 + 1] = b1;
-                ll += mx;
-                if (t == 0) continue;                               // (the first window's step is the start vector, not a transition)
-                const double s00 = a00 * b0, s01 = a01 * b1, s10 = a10 * b0, s11 = a11 * b1;
-                const double n00 = m00 * s00 + m01 * s10, n01 = m00 * s01 + m01 * s11;
-                const double n10 = m10 * s00 + m11 * s10, n11 = m10 * s01 + m11 * s11;
-                const double r = 1.0 / (n00 + n01 + n10 + n11);
-                m00 = n00 * r; m01 = n01 * r; m10 = n10 * r; m11 = n11 * r;
-            }
-            pm[size_t(p) * 4] = m00; pm[size_t(p) * 4 + 1] = m01; pm[size_t(p) * 4 + 2] = m10; pm[size_t(p) * 4 + 3] = m11;
-            pll[size_t(p)] = ll;
-        });
-        // 2. forward vector in front of every piece (normalised), serial over the pieces
-        {
-            double v0 = m.startprob[0] * B[0], v1 = m.startprob[1] * B[1];
-            edge[0] = v0; edge[1] = v1;                             // piece 0 starts from the UNnormalised first vector
-            double s = v0 + v1;
-            v0 /= s; v1 /= s;
-            for (int p = 0; p < P; ++p) {
-                const double* M = &pm[size_t(p) * 4];
-                const double w0 = v0 * M[0] + v1 * M[2], w1 = v0 * M[1] + v1 * M[3];
-                s = w0 + w1;
-                v0 = w0 / s; v1 = w1 / s;
-                if (p + 1 < P) { edge[size_t(p + 1) * 2] = v0; edge[size_t(p + 1) * 2 + 1] = v1; }
-            }
-        }
-        // 3. forward vectors of every window, and the log-likelihood
-        parallel_for(P, [&](int p) {
-            const int64_t a = n * p / P, b = n * (p + 1) / P;
-            double v0, v1, ll = 0;
-            int64_t t = a;
-            if (p == 0) {
-                const double s = edge[0] + edge[1];
-                ll += std::log(s);
-                v0 = edge[0] / s; v1 = edge[1] / s;
-                A[0] = v0; A[1] = v1;
-                t = 1;
-            } else { v0 = edge[size_t(p) * 2]; v1 = edge[size_t(p) * 2 + 1]; }
-            double prod = 1.0;                                      // the scales, four to a logarithm (each is >= the smallest transition
-            int held = 0;                                           // probability: one of the two scaled emissions is exactly 1)
-            for (; t < b; ++t) {
-                const double w0 = (v0 * a00 + v1 * a10) * B[size_t(t) * 2], w1 = (v0 * a01 + v1 * a11) * B[size_t(t) * 2 + 1];
-                const double s = w0 + w1, r = 1.0 / s;
-                prod *= s;
-                if (++held == 4 || prod < 1e-200) { ll += std::log(prod); prod = 1.0; held = 0; }
-                v0 = w0 * r; v1 = w1 * r;
-                A[size_t(t) * 2] = v0; A[size_t(t) * 2 + 1] = v1;
-            }
-            ll += std::log(prod);
-            pll[size_t(p)] += ll;
-        });
-        double ll = 0;
-        for (int p = 0; p < P; ++p) ll += pll[size_t(p)];
-        // 4. the product of every piece's backward steps (column convention: beta_t = A (b_{t+1} o beta_{t+1}))
-        parallel_for(P, [&](int p) {
-            const int64_t a = n * p / P, b = n * (p + 1) / P;
-            double m00 = 1, m01 = 0, m10 = 0, m11 = 1;
-            for (int64_t t = b - 1; t >= a; --t) {                  // beta_{t-1} from beta_t: the step uses window t's emissions
-                if (t == 0) break;
-                const double b0 = B[size_t(t) * 2], b1 = B[size_t(t) * 2 + 1];
-                const double s00 = a00 * b0, s01 = a01 * b1, s10 = a10 * b0, s11 = a11 * b1;      // S = A diag(b_t)
-                const double n00 = s00 * m00 + s01 * m10, n01 = s00 * m01 + s01 * m11;            // S M
-                const double n10 = s10 * m00 + s11 * m10, n11 = s10 * m01 + s11 * m11;
-                const double r = 1.0 / (n00 + n01 + n10 + n11);
-                m00 = n00 * r; m01 = n01 * r; m10 = n10 * r; m11 = n11 * r;
-            }
-            pm[size_t(p) * 4] = m00; pm[size_t(p) * 4 + 1] = m01; pm[size_t(p) * 4 + 2] = m10; pm[size_t(p) * 4 + 3] = m11;
-        });
-        // 5. backward vector of every piece's LAST window, serial from the end: E[P] = beta of the sequence's last window (flat),
-        //    E[p] = M_p E[p + 1] (M_p = the steps of all of piece p's windows: it carries beta from p's last window to p-1's last)
-        {
-            double v0 = 0.5, v1 = 0.5;
-            edgeB[size_t(P) * 2] = v0; edgeB[size_t(P) * 2 + 1] = v1;
-            for (int p = P - 1; p >= 1; --p) {
-                const double* M = &pm[size_t(p) * 4];
-                const double w0 = M[0] * v0 + M[1] * v1, w1 = M[2] * v0 + M[3] * v1;
-                const double s = w0 + w1;
-                v0 = w0 / s; v1 = w1 / s;
-                edgeB[size_t(p) * 2] = v0; edgeB[size_t(p) * 2 + 1] = v1;
-            }
-        }
-        // 6. walk every piece backwards: posteriors (into A), transition posteriors, and the M step's sums
-        parallel_for(P, [&](int p) {
-            const int64_t a = n * p / P, b = n * (p + 1) / P;
-            double be0 = edgeB[size_t(p + 1) * 2], be1 = edgeB[size_t(p + 1) * 2 + 1];        // beta of the piece's last window
-            double g0s = 0, g1s = 0, gx0 = 0, gx1 = 0, x00 = 0, x01 = 0, x10 = 0, x11 = 0;
-            for (int64_t t = b - 1; t >= a; --t) {
-                const double al0 = A[size_t(t) * 2], al1 = A[size_t(t) * 2 + 1];
-                // posterior of window t
-                double g0 = al0 * be0, g1 = al1 * be1;
-                const double gr = 1.0 / (g0 + g1);
-                g0 *= gr; g1 *= gr;
-                A[size_t(t) * 2] = g0; A[size_t(t) * 2 + 1] = g1;
-                g0s += g0; g1s += g1; gx0 += g0 * x[t]; gx1 += g1 * x[t];
-                if (t == 0) break;
-                // transition posterior between windows t-1 and t, and beta of window t-1
-                const double b0 = B[size_t(t) * 2] * be0, b1 = B[size_t(t) * 2 + 1] * be1;
-                // forward vector of window t-1: still in A inside the piece; the last window of the piece before belongs to another
-                // task's walk (which turns it into a posterior) - its forward vector is the edge this piece started from
-                const double p0 = t > a ? A[size_t(t - 1) * 2] : edge[size_t(p) * 2], p1 = t > a ? A[size_t(t - 1) * 2 + 1] : edge[size_t(p) * 2 + 1];
-                const double e00 = p0 * a00 * b0, e01 = p0 * a01 * b1, e10 = p1 * a10 * b0, e11 = p1 * a11 * b1;
-                const double er = 1.0 / (e00 + e01 + e10 + e11);
-                x00 += e00 * er; x01 += e01 * er; x10 += e10 * er; x11 += e11 * er;
-                const double nb0 = a00 * b0 + a01 * b1, nb1 = a10 * b0 + a11 * b1;
-                const double br = 1.0 / (nb0 + nb1);
-                be0 = nb0 * br; be1 = nb1 * br;
-            }
-            double* q = &acc[size_t(p) * 8];
-            q[0] = g0s; q[1] = g1s; q[2] = gx0; q[3] = gx1; q[4] = x00; q[5] = x01; q[6] = x10; q[7] = x11;
-        });
-        double S[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int p = 0; p < P; ++p) for (int k = 0; k < 8; ++k) S[k] += acc[size_t(p) * 8 + k];
+        double S[8];
+        const double ll = e_step(x, n, m, w, S);
         // M step (hmmlearn's defaults: flat Dirichlet priors, means_weight 0, covars_prior / weight 1e-2 / 1)
         m.startprob[0] = A[0] / (A[0] + A[1]); m.startprob[1] = A[1] / (A[0] + A[1]);
         if (n > 1) {

@@ -293,22 +293,66 @@ __global__ void __launch_bounds__(64) hmm_covar_walk(const double* __restrict__ 
         if ((call) != hipSuccess) return -2;                \
     } while (0)
 
+// the device arrays of one sequence: allocated once, used by every round
+struct Work {
+    frisk_proj::DevMem mem;
+    int P = 0, C = 0;
+    double* dx = nullptr;
+    double2 *B = nullptr, *A = nullptr;
+    double *pm = nullptr, *edge = nullptr, *edgeB = nullptr, *acc = nullptr, *cv = nullptr, *part = nullptr, *out = nullptr;
+    int load(const double* x, int64_t n) {
+        P = pieces_of(n); C = parts_of(n);
+        dx = mem.get<double>(size_t(n));
+        B = mem.get<double2>(size_t(n));
+        A = mem.get<double2>(size_t(n));
+        pm = mem.get<double>(size_t(P) * 4);
+        edge = mem.get<double>(size_t(P + 1) * 2);
+        edgeB = mem.get<double>(size_t(P + 1) * 2);
+        acc = mem.get<double>(size_t(P) * ACC);
+        cv = mem.get<double>(size_t(P) * 2);
+        part = mem.get<double>(size_t(PARTS) * 4);
+        out = mem.get<double>(16);
+        if (!dx || !B || !A || !pm || !edge || !edgeB || !acc || !cv || !part || !out) return -2;
+        HMMG_CHECK(hipMemcpy(dx, x, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
+// one E step of model m (what a round of fit runs, and all frisk_hmm_estep_gpu runs): the posteriors are left in w.A, the ACC
+// sums in S (the log-likelihood is S[8] + S[9])
+inline int e_step(const Work& w, int64_t n, const frisk_hmm::Model& m, double* S) {
+    const int P = w.P;
+    const unsigned gp = unsigned((P + 63) / 64);
+    const Par par{m.means[0], m.means[1], std::log(m.covars[0]), std::log(m.covars[1]), 1.0 / m.covars[0], 1.0 / m.covars[1],
+                  m.transmat[0], m.transmat[1], m.transmat[2], m.transmat[3], m.startprob[0], m.startprob[1]};
+    hipLaunchKernelGGL(hmm_emit_product, dim3(gp), dim3(64), 0, 0, w.dx, n, P, par, w.B, w.pm, w.acc);
+    hipLaunchKernelGGL(hmm_cuts, dim3(1), dim3(128), 0, 0, w.pm, P, par, w.B, w.edge, w.edgeB);
+    hipLaunchKernelGGL(hmm_forward_walk, dim3(gp), dim3(64), 0, 0, n, P, par, w.B, w.edge, w.A, w.acc);
+    hipLaunchKernelGGL(hmm_backward_walk, dim3(gp), dim3(64), 0, 0, w.dx, n, P, par, w.B, w.edge, w.edgeB, w.A, w.acc);
+    hipLaunchKernelGGL(hmm_reduce_rows, dim3(1), dim3(RED_T), 0, 0, w.acc, P, ACC, w.out);
+    HMMG_CHECK(hipGetLastError());
+    HMMG_CHECK(hipMemcpy(S, w.out, ACC * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// frisk_hmm_estep_gpu: post (n x 2, nullable), stats[9] = sum gamma (2), sum gamma x (2), sum xi (4), log-likelihood
+inline int e_step_only(const double* x, int64_t n, const frisk_hmm::Model& m, double* post, double* stats) {
+    Work w;
+    if (w.load(x, n)) return -2;
+    double S[ACC];
+    if (e_step(w, n, m, S)) return -2;
+    if (post) HMMG_CHECK(hipMemcpy(post, w.A, size_t(n) * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 8; ++k) stats[k] = S[k];
+    stats[8] = S[8] + S[9];
+    return 0;
+}
+
 inline int fit(const double* x, int64_t n, int n_iter, double tol, double min_covar, double covars_prior, frisk_hmm::Fit& F) {
-    using frisk_proj::DevMem;
-    DevMem mem;
-    const int P = pieces_of(n), C = parts_of(n);
-    double* dx = mem.get<double>(size_t(n));
-    double2* B = mem.get<double2>(size_t(n));
-    double2* A = mem.get<double2>(size_t(n));
-    double* pm = mem.get<double>(size_t(P) * 4);
-    double* edge = mem.get<double>(size_t(P + 1) * 2);
-    double* edgeB = mem.get<double>(size_t(P + 1) * 2);
-    double* acc = mem.get<double>(size_t(P) * ACC);
-    double* cv = mem.get<double>(size_t(P) * 2);
-    double* part = mem.get<double>(size_t(PARTS) * 4);
-    double* out = mem.get<double>(16);
-    if (!dx || !B || !A || !pm || !edge || !edgeB || !acc || !cv || !part || !out) return -2;
-    HMMG_CHECK(hipMemcpy(dx, x, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
+    Work w;
+    if (w.load(x, n)) return -2;
+    const int P = w.P, C = w.C;
+    double *dx = w.dx, *cv = w.cv, *part = w.part, *out = w.out;
+    double2* A = w.A;
     double h[16];
     frisk_hmm::Model& m = F.m;
     // start (GaussianHMM2._init)
@@ -342,15 +386,7 @@ inline int fit(const double* x, int64_t n, int n_iter, double tol, double min_co
     const unsigned gp = unsigned((P + 63) / 64);
     double prev = -std::numeric_limits<double>::infinity();
     for (int it = 0; it < n_iter; ++it) {
-        const Par par{m.means[0], m.means[1], std::log(m.covars[0]), std::log(m.covars[1]), 1.0 / m.covars[0], 1.0 / m.covars[1],
-                      m.transmat[0], m.transmat[1], m.transmat[2], m.transmat[3], m.startprob[0], m.startprob[1]};
-        hipLaunchKernelGGL(hmm_emit_product, dim3(gp), dim3(64), 0, 0, dx, n, P, par, B, pm, acc);
-        hipLaunchKernelGGL(hmm_cuts, dim3(1), dim3(128), 0, 0, pm, P, par, B, edge, edgeB);
-        hipLaunchKernelGGL(hmm_forward_walk, dim3(gp), dim3(64), 0, 0, n, P, par, B, edge, A, acc);
-        hipLaunchKernelGGL(hmm_backward_walk, dim3(gp), dim3(64), 0, 0, dx, n, P, par, B, edge, edgeB, A, acc);
-        hipLaunchKernelGGL(hmm_reduce_rows, dim3(1), dim3(RED_T), 0, 0, acc, P, ACC, out);
-        HMMG_CHECK(hipGetLastError());
-        HMMG_CHECK(hipMemcpy(h, out, ACC * sizeof(double), hipMemcpyDeviceToHost));
+        if (e_step(w, n, m, h)) return -2;
         double g[2];
         HMMG_CHECK(hipMemcpy(g, A, 2 * sizeof(double), hipMemcpyDeviceToHost));      // posterior of the first window
         const double* S = h;

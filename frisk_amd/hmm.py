@@ -95,6 +95,42 @@ class GaussianHMM2:
         self.loglik_, self.n_iter_ = float(ll.value), int(iters.value)
         return self
 
+    def _e_step_py(self, x):
+        """Posteriors (n x 2), summed transition posteriors (2 x 2) and log-likelihood of the current model: the numpy specification."""
+        b = self._loglik(x)
+        fwd, bwd, ll, lt = self._forward_backward(b)
+        post = np.exp(fwd + bwd - ll)
+        post /= post.sum(axis=1, keepdims=True)
+        if len(x) > 1:
+            xi = fwd[:-1, :, None] + lt[None] + (b[1:] + bwd[1:])[:, None, :] - ll
+            trans = np.exp(_logsumexp(xi, axis=0))
+        else:
+            trans = np.zeros((2, 2))
+        return post, trans, ll
+
+    def e_step(self, x):
+        """One E step of the CURRENT model (means_, covars_, startprob_, transmat_) over x, by the code a round of `fit` runs
+        (a test utility): (posteriors n x 2, stats, loglik) with stats = the sums over the windows of gamma_0, gamma_1,
+        gamma_0 x, gamma_1 x, xi_00, xi_01, xi_10, xi_11."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel())
+        if not self.native:
+            post, trans, ll = self._e_step_py(x)
+            return post, np.concatenate((post.sum(axis=0), (post * x[:, None]).sum(axis=0), trans.ravel())), float(ll)
+        from . import _ffi
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        pars = [np.ascontiguousarray(a, dtype=np.float64) for a in (self.means_, self.covars_, self.startprob_, np.ravel(self.transmat_))]
+        post, stats = np.zeros((x.size, 2)), np.zeros(9)
+        tail = (p(x), x.size, p(pars[0]), p(pars[1]), p(pars[2]), p(pars[3]), p(post), p(stats))
+        if self.native == "gpu":
+            rc = _ffi.lib().frisk_hmm_estep_gpu(self.device, *tail)
+            if rc == _ffi.E_HIP:
+                raise _ffi.FriskHipError(rc, "frisk_hmm_estep_gpu on device %d" % self.device)
+        else:
+            rc = _ffi.lib().frisk_hmm_estep(*tail)
+        if rc != _ffi.OK:
+            raise ValueError("frisk_hmm_estep: finite scores (at least one) and a valid model are required (code %d)" % rc)
+        return post, stats[:8].copy(), float(stats[8])
+
     def predict_segments(self, x, seg_off):
         """Viterbi paths of the sequences x[seg_off[s]:seg_off[s+1]], decoded independently (one scaffold each): int8 states."""
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -125,15 +161,7 @@ class GaussianHMM2:
         self._init(x)
         prev = -np.inf
         for _ in range(self.n_iter):
-            b = self._loglik(x)
-            fwd, bwd, ll, lt = self._forward_backward(b)
-            post = np.exp(fwd + bwd - ll)
-            post /= post.sum(axis=1, keepdims=True)
-            if len(x) > 1:
-                xi = fwd[:-1, :, None] + lt[None] + (b[1:] + bwd[1:])[:, None, :] - ll
-                trans = np.exp(_logsumexp(xi, axis=0))
-            else:
-                trans = np.zeros((2, 2))
+            post, trans, ll = self._e_step_py(x)
             # M step (hmmlearn's defaults: flat Dirichlet priors, means_weight 0, covars_prior/weight 1e-2 / 1)
             self.startprob_ = post[0] / post[0].sum()
             rows = trans.sum(axis=1, keepdims=True)

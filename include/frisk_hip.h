@@ -269,16 +269,29 @@ int frisk_hmm_fit(const double* x, int64_t n, int32_t n_iter, double tol, double
 int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, const double* means, const double* covars,
                       const double* startprob, const double* transmat, int8_t* states);
 
+/* Test utility: ONE E step of the given model over x[n], by the code a round of frisk_hmm_fit runs (csrc/hmm_host.h, e_step).
+ * post_out (n x 2, nullable) receives the posteriors; stats_out[9] the sums over the windows of gamma_0, gamma_1, gamma_0 x,
+ * gamma_1 x, xi_00, xi_01, xi_10, xi_11 and the log-likelihood.  FRISK_E_ARG for n < 1, a non-finite score or model value, a
+ * variance <= 0, a probability outside [0, 1]. */
+int frisk_hmm_estep(const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
+                    const double* transmat, double* post_out, double* stats_out);
+
 /* The same model on `device` (csrc/hmm_kernels.h), without a context: host arrays in and out, FP64 throughout, bit-identical from
  * run to run (the sequence is cut into a number of pieces that depends on n alone, the sufficient statistics are added in a fixed
  * order, no floating-point atomics); the stop rule of the fit is evaluated in double on the host once per round.  Arguments and
  * results as frisk_hmm_fit / frisk_hmm_viterbi; the fitted numbers agree with the host form to rounding (a different exp / log
  * and reassociated sums), the Viterbi states are those of the host form wherever no decision is closer than rounding (ties to
- * the lower state).  FRISK_E_ARG on a bad argument (n < 1, non-finite scores, a decreasing seg_off), FRISK_E_HIP otherwise. */
+ * the lower state).  FRISK_E_ARG on a bad argument (n < 1, non-finite scores - for the Viterbi form inside the decoded
+ * range [seg_off[0], seg_off[n_seg]) -, a decreasing seg_off), checked before any device is touched; FRISK_E_HIP otherwise. */
 int frisk_hmm_fit_gpu(int device, const double* x, int64_t n, int32_t n_iter, double tol, double min_covar, double covars_prior,
                       double* means, double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters);
 int frisk_hmm_viterbi_gpu(int device, const double* x, const int64_t* seg_off, int32_t n_seg, const double* means,
                           const double* covars, const double* startprob, const double* transmat, int8_t* states);
+
+/* Test utility: frisk_hmm_estep on `device`, by the code a round of frisk_hmm_fit_gpu runs (csrc/hmm_kernels.h, e_step): the same
+ * arguments and results with the device in front; the argument checks come before any device is touched. */
+int frisk_hmm_estep_gpu(int device, const double* x, int64_t n, const double* means, const double* covars,
+                        const double* startprob, const double* transmat, double* post_out, double* stats_out);
 
 /* Projection and clustering of the anomalous windows' k-mer proportions (the reference's L1597-1697: sklearn PCA, DBSCAN and
  * KMeans), on `device`, without a context.  Inputs and outputs are host arrays (row-major); every result is bit-identical from

@@ -27,6 +27,8 @@ FIT_CASES = {
     "below_pieces": (106, PIECES - 1, 0.01, (0.03, 0.010), (0.12, 0.050), None),
     "at_pieces": (107, PIECES, 0.01, (0.03, 0.010), (0.12, 0.050), None),
     "above_pieces": (108, PIECES + 1, 0.01, (0.03, 0.010), (0.12, 0.050), None),
+    # (below_pieces / at_pieces / above_pieces bracket n = PIECES, where P is 511 or 512 - NOT the cap P == PIECES, which is reached at
+    # n = 32 * PIECES = 524288 and is bracketed by tests/hmm_estep_cases.py's sizes)
     "rows_3m": (109, 3000000, 0.002, (0.03, 0.010), (0.12, 0.050), None),
 }
 BIG = ("rows_3m",)        # the numpy specification takes minutes on these: its fit is recorded, not recomputed by the tests
@@ -93,6 +95,13 @@ KLD_MODEL = dict(means=[0.04, 0.13], covars=[2e-4, 1.5e-3], start=[0.6, 0.4], tr
 FLAT_MODEL = dict(means=[-0.25, 0.25], covars=[0.0585, 0.0585], start=[0.5, 0.5], trans=[[0.95, 0.05], [0.05, 0.95]])
 
 
+HARD_MODELS = {
+    "forbidden": dict(means=[0.04, 0.13], covars=[2e-4, 1.5e-3], start=[0.6, 0.4], trans=[[1.0, 0.0], [0.08, 0.92]]),       # 0 -> 1 impossible
+    "absorbing_start": dict(means=[0.04, 0.13], covars=[2e-4, 1.5e-3], start=[0.0, 1.0], trans=[[0.97, 0.03], [0.0, 1.0]]),  # 1 -> 0 impossible
+    "symmetric": dict(means=[0.1, 0.1], covars=[1e-3, 1e-3], start=[0.5, 0.5], trans=[[0.5, 0.5], [0.5, 0.5]]),
+}
+
+
 def _two_regimes(rng, n, flip, model):
     st = np.cumsum(rng.random(n) < flip) % 2
     sd = np.sqrt(np.asarray(model["covars"]))
@@ -119,14 +128,22 @@ def viterbi_case(name):
         rng = np.random.default_rng(204)
         lens = np.array([0, 0, 5, 0, 0, 1, 0])
         model = KLD_MODEL
+    elif name in HARD_MODELS:
+        # every segment length around a cut of the device's pieces, hard models: a transition that cannot happen (log 0) and
+        # exact ties now CROSS cuts (hmm_vit_cuts' -inf and tie handling, hmm_vit_pieces' per-entry backpointers)
+        rng = np.random.default_rng(205 + list(HARD_MODELS).index(name))
+        V = VIT_STEPS
+        lens = np.array([V - 1, V, V + 1, 2 * V + 1, 5 * V, 0])
+        model = HARD_MODELS[name]
     else:
         raise KeyError(name)
     seg_off = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
-    x = _two_regimes(rng, int(seg_off[-1]), 0.02, model)
+    x = _two_regimes(rng, int(seg_off[-1]), 0.02, KLD_MODEL if name in HARD_MODELS else model)
     return np.ascontiguousarray(x, dtype=np.float64), seg_off, model
 
 
-VITERBI_CASES = ("short_segments", "long_segment", "cuts", "empty")
+VITERBI_CASES = ("short_segments", "long_segment", "cuts", "empty") + tuple(HARD_MODELS)
+TIED = ("symmetric",)     # every decision an exact tie: no margin to demand; the path must be all zeros
 
 
 def model_of(model, native, device=0):
@@ -136,9 +153,11 @@ def model_of(model, native, device=0):
     return m
 
 
-def numpy_path_and_margin(m, x):
+def numpy_path_and_margin(m, x, count=None):
     """GaussianHMM2._predict_py, operation for operation, and the smallest |cand[0][j] - cand[1][j]| over every step and both
-    target states j, the final choice included (inf for sequences of no decision)."""
+    target states j whose difference is FINITE, the final choice included (inf for sequences of no such decision).  A pair of
+    -inf candidates is a tie to the lower state (as numpy.argmax decides it), one -inf candidate is decided by an infinite margin;
+    `count` (a dict) receives how many decisions were finite, had one -inf candidate, or two."""
     if x.size == 0:
         return np.zeros(0, dtype=int), float("inf")
     b = m._loglik(x)
@@ -148,27 +167,39 @@ def numpy_path_and_margin(m, x):
     score = ls + b[0]
     back = np.zeros((n, 2), dtype=int)
     margin = float("inf")
+    tally = {"finite": 0, "one_neg_inf": 0, "two_neg_inf": 0}
+
+    def decide(c0, c1):
+        nonlocal margin
+        for u, v in zip(np.atleast_1d(c0).tolist(), np.atleast_1d(c1).tolist()):
+            ninf = (u == -np.inf) + (v == -np.inf)
+            tally[("finite", "one_neg_inf", "two_neg_inf")[ninf]] += 1
+            if ninf == 0:
+                margin = min(margin, abs(u - v))
     for t in range(1, n):
         cand = score[:, None] + lt
         back[t] = cand.argmax(axis=0)
-        margin = min(margin, float(np.min(np.abs(cand[0] - cand[1]))))
+        decide(cand[0], cand[1])
         score = cand.max(axis=0) + b[t]
-    margin = min(margin, float(abs(score[0] - score[1])))
+    decide(score[0], score[1])
     path = np.empty(n, dtype=int)
     path[-1] = int(score.argmax())
     for t in range(n - 1, 0, -1):
         path[t - 1] = back[t, path[t]]
+    if count is not None:
+        for k, v in tally.items():
+            count[k] = count.get(k, 0) + v
     return path, margin
 
 
-def numpy_states(model, x, seg_off, with_margin=False):
+def numpy_states(model, x, seg_off, with_margin=False, count=None):
     """States of every segment by the numpy path (int8), and - on request - the smallest decision margin."""
     m = model_of(model, native=False)
     out = np.zeros(x.size, dtype=np.int8)
     margin = float("inf")
     for a, b in zip(seg_off[:-1].tolist(), seg_off[1:].tolist()):
         if with_margin:
-            path, mg = numpy_path_and_margin(m, x[a:b])
+            path, mg = numpy_path_and_margin(m, x[a:b], count)
             margin = min(margin, mg)
         else:
             path = m._predict_py(x[a:b])

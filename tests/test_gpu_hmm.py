@@ -81,13 +81,17 @@ def test_device_fit_rejects_what_the_host_rejects():
 def test_device_viterbi_states_are_the_numpy_path(name):
     g = HMM["viterbi"][name]
     x, seg_off, model = H.viterbi_case(name)
-    assert H.sha(x) == g["sha256"] and g["margin"] > H.MARGIN
+    assert H.sha(x) == g["sha256"] and (g["margin"] > H.MARGIN or (name in H.TIED and g["margin"] == 0.0))
     want = H.numpy_states(model, x, seg_off)                    # the specification, recomputed (one Python step per window)
     assert H.sha(want) == g["states_sha256"]                    # ... and it is the path whose margin was measured
     got = H.model_of(model, "gpu").predict_segments(x, seg_off)
     assert got.dtype == np.int8 and np.array_equal(got, want)
     assert np.array_equal(got, H.model_of(model, "gpu").predict_segments(x, seg_off))
-    if x.size > 100:
+    if name == "symmetric":                     # exact ties at every step and at every cut: the lower state throughout
+        assert not got.any()
+    elif name == "absorbing_start":             # state 0 unreachable (-inf on both of its candidates, in every piece and at every cut)
+        assert got.all()
+    elif x.size > 100:
         assert 0 < int(got.sum()) < got.size
 
 

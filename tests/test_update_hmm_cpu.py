@@ -105,6 +105,13 @@ def test_device_hmm_symbols_are_declared_and_exported():
     assert lib.frisk_hmm_fit_gpu(0, p(x), 2, 10, 1e-2, 1e-3, 1e-2, p(out), p(out), p(out), p(np.zeros(4)), None, None) == _ffi.E_ARG
     off = np.array([0, 2, 1], dtype=np.int64)
     assert lib.frisk_hmm_viterbi_gpu(0, p(x), p(off), 2, p(out), p(out), p(out), p(np.zeros(4)), p(np.zeros(2, np.int8))) == _ffi.E_ARG
+    # a non-finite score inside the decoded range, as the header says - also before any device is touched; outside it, it is not read
+    fine = np.array([0, 1, 2], dtype=np.int64)
+    states = np.zeros(2, np.int8)
+    good = (p(np.array([0.04, 0.13])), p(np.array([2e-4, 1.5e-3])), p(np.array([0.6, 0.4])), p(np.array([0.97, 0.03, 0.08, 0.92])))
+    for v in (float("nan"), float("inf"), -float("inf")):
+        assert lib.frisk_hmm_viterbi_gpu(0, p(np.array([0.1, v])), p(fine), 2, *good, p(states)) == _ffi.E_ARG
+        assert lib.frisk_hmm_viterbi_gpu(0, p(np.array([v, 0.1])), p(fine[1:]), 1, *good, p(states)) != _ffi.E_ARG
     with pytest.raises(ValueError):
         GaussianHMM2(native="cuda")
 
@@ -148,8 +155,30 @@ def test_viterbi_inputs_keep_the_margin(name):
     g = HMM["viterbi"][name]
     x, seg_off, model = H.viterbi_case(name)
     assert H.sha(x) == g["sha256"]
-    states, margin = H.numpy_states(model, x, seg_off, with_margin=True)
-    assert margin == g["margin"] > H.MARGIN and H.sha(states) == g["states_sha256"]
+    count = {}
+    states, margin = H.numpy_states(model, x, seg_off, with_margin=True, count=count)
+    assert margin == g["margin"] and H.sha(states) == g["states_sha256"] and count == g["decisions"]
+    if name in H.TIED:
+        # every decision an exact tie (all four piece scores are the same bits): nothing to demand of a margin, but the path must
+        # be all zeros - on the float64 model of the device's pieces first
+        import hmm_piece_model as PM
+        assert margin == 0.0 and count["finite"] > 0 and not states.any()
+        for a, b in zip(seg_off[:-1].tolist(), seg_off[1:].tolist()):
+            assert not any(PM.viterbi(x[a:b], model)), (a, b)
+    else:
+        assert margin > H.MARGIN                    # every FINITE decision; a pair of -inf candidates is a tie to the lower state
+    if name in H.HARD_MODELS:
+        lens = np.diff(seg_off).tolist()
+        assert lens == [H.VIT_STEPS - 1, H.VIT_STEPS, H.VIT_STEPS + 1, 2 * H.VIT_STEPS + 1, 5 * H.VIT_STEPS, 0]
+    if name == "forbidden":                         # 0 -> 1 cannot happen: one -inf candidate at every step, and a path that uses both states
+        assert count["one_neg_inf"] > 0 and count["finite"] > 0 and 0 < int(states.sum()) < states.size
+        assert all(np.all(np.diff(states[a:b].astype(int)) <= 0) for a, b in zip(seg_off[:-1].tolist(), seg_off[1:].tolist()))
+    if name == "absorbing_start":                   # state 0 is never reachable: both of its candidates are -inf at every step
+        assert count["two_neg_inf"] > 0 and states.all()
+    if name in ("cuts", "forbidden"):               # the float64 model of the device's pieces gives the numpy path
+        import hmm_piece_model as PM
+        for a, b in zip(seg_off[:-1].tolist(), seg_off[1:].tolist()):
+            assert PM.viterbi(x[a:b], model) == states[a:b].tolist(), (a, b)
     assert np.array_equal(states, H.model_of(model, True).predict_segments(x, seg_off))      # host-native agrees
 
 
