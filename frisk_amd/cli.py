@@ -14,8 +14,13 @@ query again with the fine window, segments that track with the device HMM (csrc/
 updateWin_<w>_inc_<i>_<hmmOutfile>, and - with --gffOutfile - writes the anomalies with every boundary moved to the nearest
 boundary of the fine track (the reference's unused updateHMM, L737-755) to HMMupdated_<gffOutfile>.  No other output changes.
 Skipped with a warning in a sharded job, under --exitAfter, and where the fine scan meets the reference's ZeroDivisionError.
+--gffIn with --gffFeatures (and --gffRange, 0 when not given) is the reference's last step before plotting (L1709-1747): the
+records of the annotation whose type is one of --gffFeatures and that lie within --gffRange bases of an anomaly go to
+featuresIn_thresholded_Anomalies_<basename of gffIn>, and with --hmmKLD those near a State1 / State2 interval of the main track to
+featuresIn_hmm_State1_<basename> / featuresIn_hmm_State2_<basename> - `bedtools window -w gffRange -u` restated on the host
+(frisk_amd.postprocess.window_u); a file is written only when it has a record.  Rank 0, not under --exitAfter; no other output changes.
 Out of scope here: the other projections (SKL-TSNE, NMF) and SPECTRAL clustering,
---graphics (seaborn/matplotlib), --gffIn intersections (bedtools).
+--graphics (seaborn/matplotlib).
 Those options are accepted, as in the reference, and reported as unavailable if used.
 
 Run under `python -m torch.distributed.run --nproc-per-node N -m frisk_amd ...` to shard one job over N GPUs
@@ -108,8 +113,7 @@ def unavailable(args):
     after --runProjection PCA, PY-TSNE, MDS or IncrementalPCA (the reference clusters the projection, L1635-1655)."""
     clustering = args.runProjection in PROJECTIONS and args.cluster in CLUSTERINGS
     out = []
-    for opt, why in (("cluster", "sklearn clustering is out of scope"),
-                     ("graphics", "plotting is out of scope"), ("gffIn", "bedtools intersections are out of scope")):
+    for opt, why in (("cluster", "sklearn clustering is out of scope"), ("graphics", "plotting is out of scope")):
         if getattr(args, opt) and not (opt == "cluster" and clustering):
             out.append((opt, why))
     return out
@@ -119,6 +123,12 @@ def mainArgs(argv=None):
     args = build_parser().parse_args(argv)
     if args.minWordSize > args.maxWordSize:
         logging.error("[ERROR] Minimum kmer size (-m/--minWordSize) must be less than Maximum kmer size (-k/--maxWordSize)\n")
+        sys.exit(1)
+    if args.gffRange < 0:
+        logging.error("[ERROR] --gffRange must not be negative, got %s\n", args.gffRange)
+        sys.exit(1)
+    if args.gffIn and not os.path.isfile(args.gffIn):
+        logging.error("[ERROR] --gffIn %s: no such file\n", args.gffIn)
         sys.exit(1)
     return args
 
@@ -303,6 +313,31 @@ def _project(args, anomCounts, device, clock):
         log.info("%s: %s clusters, %s unclassified", args.cluster, len(set(y_pred.tolist()) - {-1}), int(np.sum(y_pred == -1)))
         clock.lap(args.cluster)
     return y_pred
+
+
+def _gff_features(args, anomalies, intervals):
+    """--gffIn (L1709-1747): the records of the annotation whose type is in --gffFeatures and that lie within --gffRange bases of
+    an anomaly (with a threshold option) or of a State1 / State2 interval of the main HMM track (--hmmKLD; `intervals` as hmm2BED
+    returns them, with the coordinates their GFF carries), one file each, written only when a record is kept."""
+    if not args.gffFeatures:
+        log.info("--gffIn %s is not used: name the feature types to report with --gffFeatures.", args.gffIn)
+        return
+    records = pp.read_gff(args.gffIn, args.gffFeatures)
+    base = os.path.basename(args.gffIn)
+
+    def report(regions, stem, found, none):
+        kept = pp.featuresNear(records, regions, args.gffRange)
+        if kept:
+            with open(os.path.join(args.tempDir, stem + base), "w") as fh:
+                fh.writelines(kept)
+            log.info("Successfully extracted %s features from within %sbp of %s annotations.", len(kept), args.gffRange, found)
+        else:
+            log.info("No features from %s detected within %s bases of %s.", args.gffIn, args.gffRange, none)
+    if args.threshTypeKLD or args.forceThresholdKLD:
+        report(anomalies, "featuresIn_thresholded_Anomalies_", "anomaly", "anomalies")
+    if args.hmmKLD:
+        for state in ("State1", "State2"):          # (the reference's filter is `type in 'State1'`; hmmBED2GFF writes these two types)
+            report(pp.gffRegions(intervals, state), "featuresIn_hmm_%s_" % state, state + " hmm", state + " hmm features")
 
 
 def _main(argv=None):
@@ -570,11 +605,14 @@ def _main(argv=None):
                         fh.write(line)
             else:
                 log.info("No RIP features detected.")
+        clock.lap("anomaly / RIP features + GFF")
+        if args.gffIn:                                                      # L1709-1747
+            _gff_features(args, anomalies, intervals if args.hmmKLD else None)
+            clock.lap("gffIn features")
     except BaseException:
         for th in out_threads:           # (the two output files are finished before the error travels on)
             th.join()
         raise
-    clock.lap("anomaly / RIP features + GFF")
     _join_outputs()
     clock.lap("score table text + window pickle written")
     clock.report()

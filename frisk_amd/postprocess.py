@@ -9,7 +9,13 @@ The reference delegates interval merging to the external `bedtools` binary throu
 restates the documented bedtools semantics (sorted input; features whose gap is <= D are merged, so
 book-ended features merge at D = 0; numeric summaries printed with bedtools' default precision `-prec 5`).
 Parity for that part is pinned by construction and by tests only, not by the reference's own output.
+The same holds for --gffIn (L1709-1747: `BedTool(gffIn).each(gffFilter).window(b=regions, w=gffRange, u=True)`): `read_gff`,
+`window_u` and `featuresNear` restate the documented `bedtools window -w W -u` (A widened by W on either side, the start clipped
+at 0; an A record reported once, as it was read, if the widened interval shares a base with any B record of the same chrom; a
+GFF record's start shifted by one to BED numbers) - pinned to tests/golden/bedtools_window_semantics.json and to a brute-force
+loop, not to bedtools' output.
 """
+import gzip
 import logging
 import math
 import os
@@ -387,6 +393,120 @@ def RIP2GFF(features, version=FRISK_VERSION):
         if n == 1:
             yield "##gff-version 3\n"
         yield "\t".join([str(f[0]), "frisk_" + version, "RIP", str(f[1]), str(f[2]), ".", "+", ".", ";".join(attrs)]) + "\n"
+
+
+# ------------------------------------------------------------------------------------------------ --gffIn: features near regions
+class GffRecords:
+    """The kept records of a GFF file: `lines` (the text of each, "\n"-terminated) and, as arrays in file order, `chrom`, and
+    `start`, `end` as half-open BED numbers [column 4 - 1, column 5) - what bedtools makes of a GFF record."""
+
+    def __init__(self, lines, chrom, start, end):
+        self.lines = lines
+        self.chrom = np.asarray(chrom, dtype=object)
+        self.start = np.asarray(start, dtype=np.int64)
+        self.end = np.asarray(end, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.lines)
+
+
+def read_gff(path, feature_types=None):
+    """GffRecords of the data lines of `path` whose type (column 3) is `in feature_types` - Python's `in`, as gffFilter applies it
+    (L545-551): membership for the list --gffFeatures gives, substring for a string such as 'State1'; None keeps every record.
+    A file that starts with the gzip magic is read through gzip.  Skipped: lines that start with '#', blank lines, `track` and
+    `browser` lines, and everything from a `##FASTA` directive on (GFF3's embedded sequences).  Any other line must have 9
+    tab-separated fields, integer columns 4 and 5 and start <= end, or ValueError names the file and the 1-based line number.
+    "\r\n" endings are stripped; the kept text ends in "\n"."""
+    with open(path, "rb") as fh:
+        magic = fh.read(2)
+    lines, chrom, start, end = [], [], [], []
+    with (gzip.open if magic == b"\x1f\x8b" else open)(path, "rt", encoding="utf-8", errors="surrogateescape", newline="\n") as fh:
+        for no, raw in enumerate(fh, 1):
+            line = raw.rstrip("\r\n")
+            if line.startswith("#"):
+                if line.startswith("##FASTA"):
+                    break
+                continue
+            if not line.strip() or line.startswith(("track", "browser")):
+                continue
+            f = line.split("\t")
+            if len(f) != 9:
+                raise ValueError("%s, line %d: %d tab-separated fields, a GFF record has 9" % (path, no, len(f)))
+            try:
+                s, e = int(f[3]), int(f[4])
+            except ValueError:
+                raise ValueError("%s, line %d: start %r and end %r must be integers" % (path, no, f[3], f[4])) from None
+            if s > e:
+                raise ValueError("%s, line %d: start %d lies behind end %d" % (path, no, s, e))
+            if feature_types is None or f[2] in feature_types:
+                lines.append(line + "\n")
+                chrom.append(f[0])
+                start.append(s - 1)
+                end.append(e)
+    return GffRecords(lines, chrom, start, end)
+
+
+def _chrom_codes(a, b):
+    """One integer per distinct name over both arrays: (codes of a, codes of b, number of names)."""
+    both = np.concatenate((np.asarray(a, dtype=object), np.asarray(b, dtype=object)))
+    try:
+        import pandas as pd
+        codes = pd.factorize(both)[0].astype(np.int64)          # hashed: no sort of a few million Python strings
+    except ImportError:
+        codes = np.unique(both.astype(str), return_inverse=True)[1].astype(np.int64)
+    return codes[:len(a)], codes[len(a):], int(codes.max()) + 1
+
+
+def window_u(a_chrom, a_start, a_end, b_chrom, b_start, b_end, w=0):
+    """`bedtools window -a A -b B -w w -u` as a boolean mask over A (file order kept, each A at most once).  All coordinates are
+    half-open BED numbers: a GFF record enters as [start - 1, end); a BED record as [start, end), taken as it is.  A is widened to
+    [max(0, a_start - w), a_end + w) and kept when it shares at least one base with some B of the same chrom name:
+    a_lo < b_end and b_start < a_hi (so book-ended intervals do not meet at w = 0, and do at w = 1).  B need not be sorted,
+    merged or non-overlapping; an empty B keeps nothing.
+    B is sorted by (chrom, start) with the running maximum of its ends inside a chrom: an A meets one iff, among the chrom's B
+    that start before a_hi, some end lies behind a_lo (the sweep thresholdRIP uses) - a searchsorted, no Python step per record."""
+    w = int(w)
+    if w < 0:
+        raise ValueError("window_u: w must not be negative, got %d" % w)
+    a_start, a_end = np.asarray(a_start, dtype=np.int64), np.asarray(a_end, dtype=np.int64)
+    b_start, b_end = np.asarray(b_start, dtype=np.int64), np.asarray(b_end, dtype=np.int64)
+    if not len(a_start) == len(a_end) == len(a_chrom) or not len(b_start) == len(b_end) == len(b_chrom):
+        raise ValueError("window_u: chrom, start and end of one side differ in length")
+    if a_start.size == 0 or b_start.size == 0:
+        return np.zeros(a_start.size, dtype=bool)
+    acode, bcode, ncodes = _chrom_codes(a_chrom, b_chrom)
+    # Only the order of A's ends against B's matters, so A is clipped to B's span (w may be larger than any scaffold) and
+    # everything is counted from the span's lower end: 0 <= coordinate < big, and code * big + coordinate orders by (chrom, coordinate)
+    lo = min(int(b_start.min()), int(b_end.min()), 0)
+    hi = max(int(b_start.max()), int(b_end.max())) + 1
+    big = hi - lo + 2
+    if ncodes * big >= 1 << 62:
+        raise OverflowError("window_u: %d chrom names over a span of %d bases do not fit one 64-bit key" % (ncodes, big))
+    w = min(w, 1 << 61)
+    a_lo = np.clip(np.maximum(np.clip(a_start, -(1 << 61), None) - w, 0), lo, hi) - lo
+    a_hi = np.clip(np.clip(a_end, None, 1 << 61) + w, lo, hi) - lo
+    order = np.lexsort((b_start, bcode))
+    bkey = bcode[order] * big + (b_start[order] - lo)
+    bend = np.maximum.accumulate(bcode[order] * big + (b_end[order] - lo))
+    k = np.searchsorted(bkey, acode * big + a_hi, side="left")             # B on earlier chroms, or on this one with b_start < a_hi
+    return (k > 0) & (bend[np.maximum(k, 1) - 1] > acode * big + a_lo)
+
+
+def featuresNear(gff_records, regions, w=0):
+    """The lines of `gff_records` (read_gff) that lie within w bases of a region, in file order: window_u of the records
+    against `regions`, records (chrom, start, end, ...) in half-open BED numbers.  The anomalies enter as the reference hands
+    them to bedtools - BED records whose start and end are the score table's numbers taken as they are (thresholdKLD L647-663),
+    no minus one; HMM states enter as records of the HMM GFF file, so as (name, start - 1, end) (gffRegions)."""
+    regions = list(regions)
+    keep = window_u(gff_records.chrom, gff_records.start, gff_records.end, [str(r[0]) for r in regions],
+                    [int(r[1]) for r in regions], [int(r[2]) for r in regions], w)
+    return [gff_records.lines[i] for i in np.nonzero(keep)[0].tolist()]
+
+
+def gffRegions(records, feature_types=None):
+    """Records (name, start, end, type) with GFF coordinates - hmm2BED's intervals, as hmmBED2GFF writes them - whose type is
+    `in feature_types` (gffFilter's test; the reference gives the string 'State1' or 'State2'), as BED regions (name, start - 1, end)."""
+    return [(str(r[0]), int(r[1]) - 1, int(r[2])) for r in records if feature_types is None or str(r[3]) in feature_types]
 
 
 # ------------------------------------------------------------------------------------------------ cluster-labelled GFF3
