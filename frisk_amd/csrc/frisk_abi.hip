@@ -22,6 +22,7 @@
 #include "scan_kernel.h"
 #include "scan8_kernel.h"
 #include "scan_big_kernel.h"
+#include "scan_schedule.h"
 #include "synth_kernel.h"
 #include "table_text.h"
 #include "fasta_index.h"
@@ -34,10 +35,6 @@
 #include "mds_kernels.h"
 #include "ipca_kernels.h"
 #include "hmm_kernels.h"
-
-#define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
-#define FRISK_SIDE_SHARE 0.06       // 4-bit bulk takes the side-table form when the plain form would hand on more than this share of the sample
-#define FRISK_K8_WIDTH 0            // order-8 counters of the default K = 8 path (scan8_kernel.h): 0 = adaptive 4/8 bits, 4, 8, 16 = off
 
 namespace {
 
@@ -656,64 +653,6 @@ int frisk_seq_load(frisk_ctx* c, const uint8_t* const* seqs, const int64_t* lens
     return run_pack(c);
 }
 
-static int upload_2bit(frisk_ctx* c, frisk_ctx::Batch& B, const uint32_t* codes, const int64_t* inv_runs, int64_t n_inv,
-                       const int64_t* low_runs, int64_t n_low, int64_t piece_bases, hipStream_t st);
-
-int frisk_fasta_load(frisk_ctx* c, const char* path, int32_t* n_seq_out, int64_t* total_len_out) {
-    if (!c || !path) return FRISK_E_ARG;
-    frisk_fasta::Records rec;
-    std::string err;
-#ifdef FRISK_TUNE
-    const auto tt0 = std::chrono::steady_clock::now();
-#endif
-    // Read and packed on the HOST, by the reader's threads, straight into the 0.25 B/base form (fasta_pack2.h: no one-byte-per-base
-    // buffer in between; seq_pack2.h: 2-bit codes + run lists of the two masks).  PCIe then carries a quarter of the bytes (3.3 GB
-    // of ASCII -> 0.82 GB for a GRCh38-sized assembly), and the host copy stays until the next load: the CLI's sequence cache is
-    // written from it without touching the device.
-    const unsigned hw = std::thread::hardware_concurrency();
-    frisk_fasta::CodeVec packed;
-    frisk_pack2::Runs packed_runs;
-    if (!frisk_fasta::parse_pack(path, rec, packed, packed_runs, err, int(std::min(32u, hw ? hw : 1u)))) return fail(c, FRISK_E_ARG, err);
-#ifdef FRISK_TUNE
-    const auto tt1 = std::chrono::steady_clock::now();
-#endif
-    HIPC(c, hipSetDevice(c->device));
-    int rc = layout_batch(c, rec.lens.data(), int32_t(rec.lens.size()));
-    if (rc) return rc;
-    frisk_ctx::Batch& B = c->b();
-    B.seq_name = rec.names;
-    if (packed.size() != size_t(B.padded_len / 32) * 2) return fail(c, FRISK_E_STATE, "frisk_fasta_load: packed length and batch layout disagree");
-    B.h_codes.swap(packed);
-    B.h_runs = std::move(packed_runs);
-    B.have_host2 = true;
-#ifdef FRISK_TUNE
-    const auto tt2 = std::chrono::steady_clock::now();
-#endif
-    HIPC(c, hipEventRecord(c->ev0, c->stream));
-    rc = upload_2bit(c, B, B.h_codes.data(), B.h_runs.inv.data(), int64_t(B.h_runs.inv.size() / 2), B.h_runs.low.data(),
-                     int64_t(B.h_runs.low.size() / 2), 0, c->stream);
-    if (rc) return rc;
-    HIPC(c, hipEventRecord(c->ev1, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->ms[2] = ms;                              // (upload + mask expansion: there is no device-side packing on this path)
-    B.have_seq = true;
-    c->plan_w = -1;
-#ifdef FRISK_TUNE
-    {
-        const auto tt3 = std::chrono::steady_clock::now();
-        auto msf = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        if (std::getenv("FRISK_LOAD_SPLIT")) std::fprintf(stderr, "[load] read + pack %.1f ms, layout %.1f ms, upload %.1f ms\n", msf(tt0, tt1), msf(tt1, tt2), msf(tt2, tt3));
-    }
-#endif
-    int64_t total = 0;
-    for (int64_t v : rec.lens) total += v;
-    if (n_seq_out) *n_seq_out = int32_t(rec.lens.size());
-    if (total_len_out) *total_len_out = total;
-    return FRISK_OK;
-}
-
 int frisk_fasta_pack_2bit(const char* path, int32_t* n_seq, int64_t** lens, uint32_t** codes, int64_t* n_code_words, int64_t** inv_runs,
                           int64_t* n_inv, int64_t** low_runs, int64_t* n_low) {
     if (!path || !n_seq || !lens || !codes || !n_code_words || !inv_runs || !n_inv || !low_runs || !n_low) return FRISK_E_ARG;
@@ -1086,6 +1025,61 @@ static int upload_2bit(frisk_ctx* c, frisk_ctx::Batch& B, const uint32_t* codes,
         HIPC(c, hipEventRecord(B.piece_ev[i], st));
         B.piece_end.push_back(b);
     }
+    return FRISK_OK;
+}
+
+int frisk_fasta_load(frisk_ctx* c, const char* path, int32_t* n_seq_out, int64_t* total_len_out) {
+    if (!c || !path) return FRISK_E_ARG;
+    frisk_fasta::Records rec;
+    std::string err;
+#ifdef FRISK_TUNE
+    const auto tt0 = std::chrono::steady_clock::now();
+#endif
+    // Read and packed on the HOST, by the reader's threads, straight into the 0.25 B/base form (fasta_pack2.h: no one-byte-per-base
+    // buffer in between; seq_pack2.h: 2-bit codes + run lists of the two masks).  PCIe then carries a quarter of the bytes (3.3 GB
+    // of ASCII -> 0.82 GB for a GRCh38-sized assembly), and the host copy stays until the next load: the CLI's sequence cache is
+    // written from it without touching the device.
+    const unsigned hw = std::thread::hardware_concurrency();
+    frisk_fasta::CodeVec packed;
+    frisk_pack2::Runs packed_runs;
+    if (!frisk_fasta::parse_pack(path, rec, packed, packed_runs, err, int(std::min(32u, hw ? hw : 1u)))) return fail(c, FRISK_E_ARG, err);
+#ifdef FRISK_TUNE
+    const auto tt1 = std::chrono::steady_clock::now();
+#endif
+    HIPC(c, hipSetDevice(c->device));
+    int rc = layout_batch(c, rec.lens.data(), int32_t(rec.lens.size()));
+    if (rc) return rc;
+    frisk_ctx::Batch& B = c->b();
+    B.seq_name = rec.names;
+    if (packed.size() != size_t(B.padded_len / 32) * 2) return fail(c, FRISK_E_STATE, "frisk_fasta_load: packed length and batch layout disagree");
+    B.h_codes.swap(packed);
+    B.h_runs = std::move(packed_runs);
+    B.have_host2 = true;
+#ifdef FRISK_TUNE
+    const auto tt2 = std::chrono::steady_clock::now();
+#endif
+    HIPC(c, hipEventRecord(c->ev0, c->stream));
+    rc = upload_2bit(c, B, B.h_codes.data(), B.h_runs.inv.data(), int64_t(B.h_runs.inv.size() / 2), B.h_runs.low.data(),
+                     int64_t(B.h_runs.low.size() / 2), 0, c->stream);
+    if (rc) return rc;
+    HIPC(c, hipEventRecord(c->ev1, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->ms[2] = ms;                              // (upload + mask expansion: there is no device-side packing on this path)
+    B.have_seq = true;
+    c->plan_w = -1;
+#ifdef FRISK_TUNE
+    {
+        const auto tt3 = std::chrono::steady_clock::now();
+        auto msf = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        if (std::getenv("FRISK_LOAD_SPLIT")) std::fprintf(stderr, "[load] read + pack %.1f ms, layout %.1f ms, upload %.1f ms\n", msf(tt0, tt1), msf(tt1, tt2), msf(tt2, tt3));
+    }
+#endif
+    int64_t total = 0;
+    for (int64_t v : rec.lens) total += v;
+    if (n_seq_out) *n_seq_out = int32_t(rec.lens.size());
+    if (total_len_out) *total_len_out = total;
     return FRISK_OK;
 }
 
@@ -1512,31 +1506,339 @@ int frisk_scan_plan(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_
     return FRISK_OK;
 }
 
-static int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_t c0, int64_t c1, int64_t cap,
-                     int32_t* seq_index, int64_t* start, int64_t* stop, uint32_t* status, double* kld, double* gc,
-                     double* pi, double* si, double* cri, uint32_t* dbg_counts, int64_t* dbg_meta);
+namespace {
 
-int frisk_scan(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_t c0, int64_t c1, int64_t cap,
-               int32_t* seq_index, int64_t* start, int64_t* stop, uint32_t* status, double* kld, double* gc,
-               double* pi, double* si, double* cri, uint32_t* dbg_counts, int64_t* dbg_meta) {
-    const int rc = scan_impl(c, w, inc, flags, c0, c1, cap, seq_index, start, stop, status, kld, gc, pi, si, cri, dbg_counts, dbg_meta);
-    if (rc != FRISK_OK && c) {
-        // a failure after work was queued: copies may still target the caller's row buffers (and locals of the call), kernels of
-        // the tail segment may still run - nothing of this call is in flight once it has returned
-        const std::string msg = c->err;
-        if (hipSetDevice(c->device) == hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipStreamSynchronize(c->tail_stream);
-            (void)hipGetLastError();
-        }
-        c->err = msg;
-    }
-    return rc;
+// what the schedule's decisions read (scan_schedule.h), from the context and the call
+ScanShape scan_shape_of(frisk_ctx* c, int64_t n, int32_t w, int32_t inc, uint32_t flags, bool debug) {
+    ScanShape s = ScanShape();
+    s.kmin = c->kmin; s.kmax = c->kmax; s.num_cu = c->num_cu; s.n = n; s.w = w; s.inc = inc; s.flags = flags;
+    s.plan_maxwin = c->plan_maxwin;
+    s.debug = debug; s.want_ivom = c->want_ivom != nullptr; s.rip = (flags & FRISK_SCAN_RIP) != 0;
+    const frisk_ctx::Batch& B = c->b();
+    s.width_hint = B.width_hint; s.hint_side = B.hint_side; s.hint_matches = B.hint_w == w && B.hint_inc == inc;
+    s.lv_shared = shared_level(c->kmin, c->kmax);
+    s.lds_shared = make_layout(c->kmin, c->kmax, scan_orphan_cap(c->plan_maxwin), s.lv_shared).total;
+    s.lds_level0 = make_layout(c->kmin, c->kmax, scan_orphan_cap(c->plan_maxwin), 0).total;
+    if (const char* ev = tune_env("FRISK_SCAN_CHUNK")) { s.has_scan_chunk = true; s.scan_chunk = std::atoll(ev); }
+    if (const char* ev = tune_env("FRISK_K8_BITS")) { s.has_k8_bits = true; s.k8_bits = std::atoi(ev); }
+    s.one_wg = tune_env("FRISK_ONE_WG") != nullptr;
+    s.no_slide = tune_env("FRISK_NO_SLIDE") != nullptr; s.no_deal = tune_env("FRISK_NO_DEAL") != nullptr;
+    s.one_segment = tune_env("FRISK_ONE_SEGMENT") != nullptr; s.tail_any = tune_env("FRISK_TAIL_ANY") != nullptr;
+    return s;
 }
 
-static int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_t c0, int64_t c1, int64_t cap,
-                     int32_t* seq_index, int64_t* start, int64_t* stop, uint32_t* status, double* kld, double* gc,
-                     double* pi, double* si, double* cri, uint32_t* dbg_counts, int64_t* dbg_meta) {
+// One frisk_scan between its schedule and its rows: the schedule (read, never decided, here), the kernel arguments of the whole
+// range and the caller's buffers.  reserve(), enqueue() and collect() run once each, in this order.
+struct ScanRun {
+    frisk_ctx* c;
+    const ScanShape& shape;
+    const ScanSchedule& sched;
+    int32_t* seq_index; int64_t* start; int64_t* stop; uint32_t* status; double* kld; double* gc; double* pi; double* si; double* cri;
+    uint32_t* dbg_counts; int64_t* dbg_meta;
+    ScanParams P;
+    size_t nk;                              // 4^kmax
+    unsigned int novf_sample[2];            // the sample's own hand-overs (its counters are cleared for the bulk segments)
+
+    // row buffers (short scans: one block, RowBlock), debug dumps, and the kernel arguments that every launch of the call starts from
+    int reserve(int64_t c0, int64_t c1) {
+        const size_t N = size_t(shape.n);
+        const bool rip = shape.rip;
+        const RowBlock& blk = sched.block;
+        if (sched.packed_rows) {
+            HIPC(c, c->o_block.reserve(blk.words));
+            if (c->h_block_cap < blk.words * 8) {
+                if (c->h_block) HIPC(c, hipHostFree(c->h_block));
+                c->h_block = nullptr; c->h_block_cap = 0;
+                HIPC(c, hipHostMalloc(&c->h_block, blk.words * 8 + blk.words, hipHostMallocDefault));
+                c->h_block_cap = blk.words * 8 + blk.words;
+            }
+        } else {
+            HIPC(c, c->o_seq.reserve(N)); HIPC(c, c->o_start.reserve(N)); HIPC(c, c->o_stop.reserve(N));
+            HIPC(c, c->o_status.reserve(N)); HIPC(c, c->o_kld.reserve(N)); HIPC(c, c->o_gc.reserve(N));
+            if (rip) { HIPC(c, c->o_pi.reserve(N)); HIPC(c, c->o_si.reserve(N)); HIPC(c, c->o_cri.reserve(N)); }
+        }
+        HIPC(c, c->o_sw.reserve(N)); HIPC(c, c->o_sg.reserve(N));
+        if (dbg_counts) {
+            HIPC(c, c->o_counts.reserve(N * size_t(c->nprof)));
+            HIPC(c, hipMemsetAsync(c->o_counts.p, 0, N * size_t(c->nprof) * 4, c->stream));
+        }
+        if (dbg_meta) {
+            HIPC(c, c->o_meta.reserve(N * 3));
+            HIPC(c, hipMemsetAsync(c->o_meta.p, 0, N * 3 * 8, c->stream));
+        }
+        P.codes = c->b().d_codes.p; P.inv = c->b().d_inv.p; P.low = c->b().d_low.p;
+        P.descs = c->d_desc.p; P.ig = c->d_ig.p; P.log_tab = c->d_logtab.p; P.log_tab64 = c->d_logtab64.p; P.log_tab32 = c->d_logtab32.p;
+        P.n_desc = c->b().n_seq + 1;
+        P.kmin = c->kmin; P.kmax = c->kmax; P.w = shape.w; P.inc = shape.inc; P.flags = shape.flags; P.c0 = c0; P.c1 = c1;
+        P.orphan_cap = sched.orphan_cap; P.lv = sched.lv; P.chunk = sched.chunk;
+        P.nprof = int32_t(c->nprof);
+        if (sched.packed_rows) {
+            double* b = c->o_block.p;
+            P.start = reinterpret_cast<int64_t*>(b + blk.start); P.stop = reinterpret_cast<int64_t*>(b + blk.stop);
+            P.kld = b + blk.kld; P.gc = b + blk.gc;
+            P.pi = rip ? b + blk.pi : nullptr; P.si = rip ? b + blk.si : nullptr; P.cri = rip ? b + blk.cri : nullptr;
+            P.seq_index = reinterpret_cast<int32_t*>(b + blk.seq_index); P.status = reinterpret_cast<uint32_t*>(b + blk.status);
+        } else {
+            P.seq_index = c->o_seq.p; P.start = c->o_start.p; P.stop = c->o_stop.p; P.status = c->o_status.p;
+            P.kld = c->o_kld.p; P.gc = c->o_gc.p;
+            P.pi = rip ? c->o_pi.p : nullptr; P.si = rip ? c->o_si.p : nullptr; P.cri = rip ? c->o_cri.p : nullptr;
+        }
+        P.sw = c->o_sw.p; P.sg = c->o_sg.p;
+        P.dbg_counts = dbg_counts ? c->o_counts.p : nullptr;
+        P.dbg_meta = dbg_meta ? c->o_meta.p : nullptr;
+        P.dbg_ivom = nullptr;
+        if (c->want_ivom) {
+            HIPC(c, c->o_ivom.reserve(N * 2 * nk));
+            HIPC(c, hipMemsetAsync(c->o_ivom.p, 0, N * 2 * nk * sizeof(double), c->stream));
+            P.dbg_ivom = c->o_ivom.p;
+        }
+        P.unused_stamps = nullptr;
+        P.rc_tab = c->d_rctab.p; P.in_list = nullptr; P.in_count = nullptr; P.out_list = nullptr; P.out_count = nullptr;
+        P.sel_mode = 0; P.sel_mod = sched.sel_mod; P.queue = nullptr; P.queue_n = 1; P.slide_pp = sched.slide_pp; P.ig_ring = nullptr;
+        P.verdict = nullptr; P.my_form = 0u;
+        return FRISK_OK;
+    }
+
+    // the 16-bit form (scan_kernel.h) over the candidates that PP names, by window class
+    hipError_t launch16(const ScanParams& PP, int g, hipStream_t st) const {
+        const int its = sched.its;
+        hipError_t le;
+#define FRISK_LAUNCH16(NT_, K8_, ITS_, DBG_) le = launch_scan<NT_, K8_, ITS_, DBG_>(PP, g, sched.lds_total, st)
+        if (c->kmax == 8) {
+            if (shape.debug) { if (its) FRISK_LAUNCH16(512, true, 16, true); else FRISK_LAUNCH16(1024, true, 0, true); }
+            else if (its == 4) FRISK_LAUNCH16(512, true, 4, false);
+            else if (its == 10) FRISK_LAUNCH16(512, true, 10, false);
+            else if (its == 16) FRISK_LAUNCH16(512, true, 16, false);
+            else FRISK_LAUNCH16(1024, true, 0, false);
+        } else {
+            if (shape.debug) { if (its) FRISK_LAUNCH16(512, false, 16, true); else FRISK_LAUNCH16(1024, false, 0, true); }
+            else if (its == 4) FRISK_LAUNCH16(512, false, 4, false);
+            else if (its == 10) FRISK_LAUNCH16(512, false, 10, false);
+            else if (its == 16) FRISK_LAUNCH16(512, false, 16, false);
+            else FRISK_LAUNCH16(1024, false, 0, false);
+        }
+#undef FRISK_LAUNCH16
+        return le;
+    }
+
+    // rows [r0, r1) to the caller's buffers
+    int copy_rows(int64_t r0, int64_t r1, hipStream_t st) {
+        const size_t m = size_t(r1 - r0);
+        if (sched.packed_rows) {        // (always the whole scan: short scans run in one segment) - unpacked behind the final wait
+            HIPC(c, hipMemcpyAsync(c->h_block, c->o_block.p, sched.block.words * 8, hipMemcpyDeviceToHost, st));
+            return FRISK_OK;
+        }
+        HIPC(c, hipMemcpyAsync(seq_index + r0, P.seq_index + r0, m * 4, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(start + r0, P.start + r0, m * 8, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(stop + r0, P.stop + r0, m * 8, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(status + r0, P.status + r0, m * 4, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(kld + r0, P.kld + r0, m * 8, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(gc + r0, P.gc + r0, m * 8, hipMemcpyDeviceToHost, st));
+        if (shape.rip) {
+            HIPC(c, hipMemcpyAsync(pi + r0, P.pi + r0, m * 8, hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(si + r0, P.si + r0, m * 8, hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(cri + r0, P.cri + r0, m * 8, hipMemcpyDeviceToHost, st));
+        }
+        return FRISK_OK;
+    }
+
+    // every path but the narrow-counter one: one launch over the whole range, the rows' scalar tail, the rows to the host
+    int enqueue_whole() {
+        const int64_t n = shape.n;
+        hipError_t e = hipSuccess;
+        if (sched.path == SCAN_PATH_BIG) {      // 32-bit tables of all orders in a global scratch slice per workgroup
+            const int64_t stride = (c->nprof + 3) / 4 * 4;
+            HIPC(c, c->d_big.reserve(size_t(sched.big_grid) * size_t(stride)));
+            HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(sched.big_grid) * size_t(stride) * 4, c->stream));
+            if (shape.debug) scan_big_kernel<true><<<sched.big_grid, FRISK_BIG_NT, 0, c->stream>>>(P, c->d_big.p, stride);
+            else scan_big_kernel<false><<<sched.big_grid, FRISK_BIG_NT, 0, c->stream>>>(P, c->d_big.p, stride);
+            e = hipGetLastError();
+        } else if (sched.path == SCAN_PATH_TWO_WG) {
+            if (sched.its == 8) e = launch_scan<256, false, 8, false>(P, sched.grid, sched.lds_total, c->stream);
+            else e = launch_scan<256, false, 20, false>(P, sched.grid, sched.lds_total, c->stream);
+        } else {
+            e = launch16(P, sched.grid, c->stream);
+        }
+        HIPC(c, e);
+        if (sched.path != SCAN_PATH_BIG) {      // the LDS kernels leave the rows' scalar tail to one thread per row
+            finish_rows_kernel<<<grid_for(n, 256, 1 << 20), 256, 0, c->stream>>>(n, P.status, P.kld, P.gc, P.sw, P.sg);
+            HIPC(c, hipGetLastError());
+        }
+        HIPC(c, hipEventRecord(c->ev1, c->stream));
+        return copy_rows(0, n, c->stream);
+    }
+
+    // The sample of the adaptive width, and its own hand-overs (list 1 -> 8-bit -> list 2 -> 16-bit) now, so that lists and counters
+    // are free for the bulk segments and no later pass touches rows of another segment
+    int sample() {
+        const int64_t n = shape.n, nsample = sched.nsample, chunk8 = sched.chunk8;
+        ScanParams S = P;
+        S.chunk = int32_t(chunk8);
+        S.sel_mode = 1; S.out_list = c->d_ovf_list.p; S.out_count = c->d_ovf_count.p;
+        if (sched.dealt) { S.queue = c->d_ovf_count.p + 8; S.queue_n = 8; }
+        HIPC(c, launch_narrow(c->kmax, 4, sched.small_w, false, S, c->num_cu, nsample, c->stream, true));
+        // The verdict is taken ON THE DEVICE (scan8_decide_kernel, one thread behind the sample): the host queues all three bulk forms
+        // behind it, each with the verdict's address and its own number, and two of them return at once - no host synchronisation
+        // in the first scan of a batch (round 3: sample -> copy -> hipStreamSynchronize -> decide -> launch).  The rule:
+        // 4-bit pays while fewer than about three windows in ten have to be redone (round 3, bench shard with simple repeats at
+        // 0.05 / 0.1 / 0.2 / 0.3 per kb = 10 / 20 / 37 / 51 % of the scored windows handed on: 4-bit bulk 7.27 / 7.96 / 8.97 /
+        // 9.98 ms, 8-bit bulk 8.51 / 8.57 / 8.71 / 8.78 ms - tools/exp/width_sweep.sh); the side table pays when the plain form
+        // would hand on more than FRISK_SIDE_SHARE of the windows that are scored (it costs a scored window 1.0 ns - ten
+        // instructions per position: 6.97 against 6.59 ms per scan -, a window handed on 18 ns: tools/exp/side_rate.py)
+        scan8_decide_kernel<<<1, 1, 0, c->stream>>>(c->d_ovf_count.p, static_cast<unsigned int>(nsample * chunk8), double(FRISK_SIDE_SHARE),
+                                                    sched.narrow8 && !shape.debug ? 1 : 0, c->d_verdict.p);
+        HIPC(c, hipGetLastError());
+        ScanParams H = P;
+        H.in_list = c->d_ovf_list.p; H.in_count = c->d_ovf_count.p;
+        H.out_list = c->d_ovf_list2.p; H.out_count = c->d_ovf_count.p + 1;
+        if (sched.dealt) H.queue = c->d_ovf_count.p + 16;
+        HIPC(c, launch_narrow(c->kmax, 8, sched.small_w, false, H, c->num_cu, nsample * chunk8, c->stream));
+        ScanParams H2 = P;
+        H2.in_list = c->d_ovf_list2.p; H2.in_count = c->d_ovf_count.p + 1;
+        int g16 = int(std::min<int64_t>(n, int64_t(c->num_cu)));
+        if (g16 >= 8) g16 &= ~7;
+        HIPC(c, launch16(H2, g16, c->stream));
+        HIPC(c, hipMemcpyAsync(novf_sample, c->d_ovf_count.p, sizeof(novf_sample), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemsetAsync(c->d_ovf_count.p, 0, 64 * sizeof(unsigned int), c->stream));
+        return FRISK_OK;
+    }
+
+    // Rows [r0, r1) of this scan on stream `st`: bulk launch, the two hand-over launches and the rows' scalar tail.  Segment `seg`
+    // has its own slice of the two lists (from entry r0) and its own 32 counters: [0], [1] the lists' lengths, [8..15] the bulk
+    // launch's chunk queues (one per XCD), [16] the 8-bit launch's.
+    int run_rows(int seg, int64_t r0, int64_t r1, hipStream_t st, bool fork_tail) {
+        const int64_t m = r1 - r0, chunk8 = sched.chunk8;
+        const bool small_w = sched.small_w, debug = shape.debug;
+        ScanParams R = P;
+        R.c0 = P.c0 + r0; R.c1 = P.c0 + r1;
+        R.seq_index += r0; R.start += r0; R.stop += r0; R.status += r0; R.kld += r0; R.gc += r0; R.sw += r0; R.sg += r0;
+        if (shape.rip) { R.pi += r0; R.si += r0; R.cri += r0; }
+        if (R.dbg_counts) R.dbg_counts += r0 * int64_t(c->nprof);
+        if (R.dbg_meta) R.dbg_meta += r0 * 3;
+        if (R.dbg_ivom) R.dbg_ivom += r0 * 2 * int64_t(nk);
+        unsigned int* cnt = c->d_ovf_count.p + 32 * seg;
+        int64_t* list1 = c->d_ovf_list.p + r0;
+        int64_t* list2 = c->d_ovf_list2.p + r0;
+        ScanParams B = R;                       // the bulk launch
+        B.chunk = int32_t(chunk8);
+        B.sel_mode = sched.sel_mode;
+        if (sched.bulk == 4) { B.out_list = list1; B.out_count = cnt; }
+        else { B.out_list = list2; B.out_count = cnt + 1; }
+        if (sched.dealt) { B.queue = cnt + 8; B.queue_n = 8; }
+        const int64_t mchunks = (m + chunk8 - 1) / chunk8;
+        const int64_t bulk_chunks = sched.sel_mode == 2 ? mchunks - (mchunks + B.sel_mod - 1) / B.sel_mod : mchunks;
+        if (sched.sample) {                     // plain 4-bit / 4-bit + side table / 8-bit: the device's verdict lets one of them run
+            B.verdict = c->d_verdict.p;
+            B.out_list = list1; B.out_count = cnt;
+            B.my_form = 1u;
+            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, false));
+            B.my_form = 2u;
+            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, true));
+            B.my_form = 3u;
+            B.out_list = list2; B.out_count = cnt + 1;
+            HIPC(c, launch_narrow(c->kmax, 8, small_w, false, B, c->num_cu, bulk_chunks, st));
+        } else
+        HIPC(c, launch_narrow(c->kmax, sched.bulk, small_w, debug, B, c->num_cu, bulk_chunks, st, false, sched.side));
+        if (sched.bulk == 4) {                  // list 1 (4-bit hand-overs) -> 8-bit -> list 2
+            ScanParams H = R;
+            H.in_list = list1; H.in_count = cnt;
+            H.out_list = list2; H.out_count = cnt + 1;
+            if (sched.dealt) H.queue = cnt + 16;
+            HIPC(c, launch_narrow(c->kmax, 8, small_w, debug, H, c->num_cu, m, st));
+        }
+        // list 2 -> 16-bit counters, one window per workgroup at a time (a no-op when the list is empty)
+        R.in_list = list2; R.in_count = cnt + 1;
+        int g16 = int(std::min<int64_t>(m, int64_t(c->num_cu)));
+        if (g16 >= 8) g16 &= ~7;
+        HIPC(c, launch16(R, g16, st));
+        if (fork_tail) {        // the tail segment starts here: beside this segment's scalar tail and its rows' way to the host
+            HIPC(c, hipEventRecord(c->ev_fork, st));
+            HIPC(c, hipStreamWaitEvent(c->tail_stream, c->ev_fork, 0));
+        }
+        finish_rows_kernel<<<grid_for(m, 256, 1 << 20), 256, 0, st>>>(m, R.status, R.kld, R.gc, R.sw, R.sg);
+        HIPC(c, hipGetLastError());
+        return FRISK_OK;
+    }
+
+    // the narrow-counter path (scan8_kernel.h): lists, counters and ring, the sample, then the rows in one or two segments
+    int enqueue_narrow() {
+        const int64_t n = shape.n, cut = sched.cut;
+        HIPC(c, c->d_ovf_list.reserve(size_t(n)));
+        HIPC(c, c->d_ovf_list2.reserve(size_t(n)));
+        HIPC(c, hipMemsetAsync(c->d_ovf_count.p, 0, 64 * sizeof(unsigned int), c->stream));
+        if (sched.ring_slices > 0) {    // a copy of the genome table (one base address for both), then one slice per workgroup launched
+            const double* had = c->d_ig_ring.p;
+            HIPC(c, c->d_ig_ring.reserve(nk + size_t(sched.ring_slices) * (20 * FRISK8_RING_COLS + FRISK8_RING_PAD)));
+            if (c->d_ig_ring.p != had || c->ring_gen != c->ig_gen) {        // (once per genome table, not once per scan)
+                HIPC(c, hipMemcpyAsync(c->d_ig_ring.p, c->d_ig.p, nk * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+                c->ring_gen = c->ig_gen;
+            }
+            P.ig_ring = c->d_ig_ring.p;
+        }
+        if (sched.sample) { if (int rc = sample()) return rc; }
+        if (int rc = run_rows(0, 0, cut, c->stream, cut < n)) return rc;
+        if (cut < n) {
+            if (int rc = run_rows(1, cut, n, c->tail_stream, false)) return rc;
+            HIPC(c, hipEventRecord(c->ev_tail_kernels, c->tail_stream));
+            if (int rc = copy_rows(cut, n, c->tail_stream)) return rc;
+            HIPC(c, hipEventRecord(c->ev_tail_done, c->tail_stream));
+            if (int rc = copy_rows(0, cut, c->stream)) return rc;
+            HIPC(c, hipStreamWaitEvent(c->stream, c->ev_tail_kernels, 0));
+            HIPC(c, hipEventRecord(c->ev1, c->stream));                     // every scan kernel of this call has finished
+            HIPC(c, hipStreamWaitEvent(c->stream, c->ev_tail_done, 0));
+            return FRISK_OK;
+        }
+        HIPC(c, hipEventRecord(c->ev1, c->stream));
+        return copy_rows(0, n, c->stream);
+    }
+
+    int enqueue() {
+        HIPC(c, hipEventRecord(c->ev0, c->stream));
+        return sched.path == SCAN_PATH_NARROW ? enqueue_narrow() : enqueue_whole();
+    }
+
+    // debug dumps and counters to the host, the one wait of the call, then what the host does with the rows
+    int collect() {
+        const size_t N = size_t(shape.n);
+        unsigned int novf[34] = {0}, verdict_host[4] = {0, 0, 0, 0};
+        if (dbg_counts)
+            HIPC(c, hipMemcpyAsync(dbg_counts, c->o_counts.p, N * size_t(c->nprof) * 4, hipMemcpyDeviceToHost, c->stream));
+        if (dbg_meta) HIPC(c, hipMemcpyAsync(dbg_meta, c->o_meta.p, N * 3 * 8, hipMemcpyDeviceToHost, c->stream));
+        if (c->want_ivom) HIPC(c, hipMemcpyAsync(c->want_ivom, c->o_ivom.p, N * 2 * nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (sched.path == SCAN_PATH_NARROW) HIPC(c, hipMemcpyAsync(novf, c->d_ovf_count.p, sizeof(novf), hipMemcpyDeviceToHost, c->stream));
+        if (sched.sample) HIPC(c, hipMemcpyAsync(verdict_host, c->d_verdict.p, sizeof(verdict_host), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        c->scan_stat[0] = sched.bulk; c->scan_stat[3] = sched.segments; c->scan_stat[4] = sched.side ? 1 : 0;
+        if (sched.sample) {             // what the device decided: remembered per batch and geometry (later scans launch that form alone)
+            frisk_ctx::Batch& VB = c->b();
+            VB.width_hint = verdict_host[0] == 3u ? 8 : 4; VB.hint_w = shape.w; VB.hint_inc = shape.inc; VB.hint_side = verdict_host[0] == 2u ? 1 : 0;
+            c->scan_stat[0] = VB.width_hint;
+            c->scan_stat[4] = VB.hint_side;
+        }
+        if (sched.packed_rows) {
+            const double* b = static_cast<const double*>(c->h_block);
+            const RowBlock& blk = sched.block;
+            std::memcpy(start, b + blk.start, N * 8); std::memcpy(stop, b + blk.stop, N * 8);
+            std::memcpy(kld, b + blk.kld, N * 8); std::memcpy(gc, b + blk.gc, N * 8);
+            if (shape.rip) { std::memcpy(pi, b + blk.pi, N * 8); std::memcpy(si, b + blk.si, N * 8); std::memcpy(cri, b + blk.cri, N * 8); }
+            std::memcpy(seq_index, b + blk.seq_index, N * 4); std::memcpy(status, b + blk.status, N * 4);
+        }
+        c->scan_stat[1] = novf[0] + novf[32] + novf_sample[0];
+        c->scan_stat[2] = novf[1] + novf[33] + novf_sample[1];
+        if (c->b().tiled)               // descriptor index -> index of the scaffold in the FASTA
+            for (size_t r = 0; r < N; ++r) seq_index[r] = c->b().tiles[size_t(seq_index[r])].scaf;
+        float ms = 0;
+        HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        c->ms[0] = ms;
+        return FRISK_OK;
+    }
+};
+
+// frisk_scan in five steps: validate the call, decide the schedule (plan_scan_schedule, scan_schedule.h), reserve the buffers,
+// enqueue the launches and copies, collect the rows
+int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_t c0, int64_t c1, int64_t cap,
+              int32_t* seq_index, int64_t* start, int64_t* stop, uint32_t* status, double* kld, double* gc,
+              double* pi, double* si, double* cri, uint32_t* dbg_counts, int64_t* dbg_meta) {
     if (!c) return FRISK_E_ARG;
     if (!c->profile_final) return fail(c, FRISK_E_STATE, "frisk_scan: genome profile not finalised");
     int64_t ncand_all = 0;
@@ -1555,411 +1857,37 @@ static int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64
     if (n == 0) return FRISK_OK;
     HIPC(c, hipSetDevice(c->device));
     if (int rs = settle_stream(c)) return rs;
-    const bool debug = dbg_counts || dbg_meta;
-    const size_t N = size_t(n);
-    // short scans: the row columns as consecutive pieces of one block - [start | stop | kld | gc | pi si cri | seq_index | status] - so
-    // that one copy brings them to the host
-    const bool packed_rows = n < (int64_t(1) << 17);
-    const size_t Np = (N + 1) / 2 * 2;                          // (the two 4-byte columns end on a multiple of 8 bytes)
-    const size_t blk_words = packed_rows ? (4 + (rip ? 3 : 0)) * Np + Np : 0;      // in doubles
-    if (packed_rows) {
-        HIPC(c, c->o_block.reserve(blk_words));
-        if (c->h_block_cap < blk_words * 8) {
-            if (c->h_block) HIPC(c, hipHostFree(c->h_block));
-            c->h_block = nullptr; c->h_block_cap = 0;
-            HIPC(c, hipHostMalloc(&c->h_block, blk_words * 8 + blk_words, hipHostMallocDefault));
-            c->h_block_cap = blk_words * 8 + blk_words;
-        }
-    } else {
-        HIPC(c, c->o_seq.reserve(N)); HIPC(c, c->o_start.reserve(N)); HIPC(c, c->o_stop.reserve(N));
-        HIPC(c, c->o_status.reserve(N)); HIPC(c, c->o_kld.reserve(N)); HIPC(c, c->o_gc.reserve(N));
-        if (rip) { HIPC(c, c->o_pi.reserve(N)); HIPC(c, c->o_si.reserve(N)); HIPC(c, c->o_cri.reserve(N)); }
-    }
-    HIPC(c, c->o_sw.reserve(N)); HIPC(c, c->o_sg.reserve(N));
-    if (dbg_counts) {
-        HIPC(c, c->o_counts.reserve(N * size_t(c->nprof)));
-        HIPC(c, hipMemsetAsync(c->o_counts.p, 0, N * size_t(c->nprof) * 4, c->stream));
-    }
-    if (dbg_meta) {
-        HIPC(c, c->o_meta.reserve(N * 3));
-        HIPC(c, hipMemsetAsync(c->o_meta.p, 0, N * 3 * 8, c->stream));
-    }
 
-    ScanParams P;
-    P.codes = c->b().d_codes.p; P.inv = c->b().d_inv.p; P.low = c->b().d_low.p;
-    P.descs = c->d_desc.p; P.ig = c->d_ig.p; P.log_tab = c->d_logtab.p; P.log_tab64 = c->d_logtab64.p; P.log_tab32 = c->d_logtab32.p;
-    P.n_desc = c->b().n_seq + 1;
-    P.kmin = c->kmin; P.kmax = c->kmax; P.w = w; P.inc = inc; P.flags = flags; P.c0 = c0; P.c1 = c1;
-    P.orphan_cap = int32_t(c->plan_maxwin / 8 + 2);
-    P.nprof = int32_t(c->nprof);
-    if (packed_rows) {
-        double* b = c->o_block.p;
-        P.start = reinterpret_cast<int64_t*>(b); P.stop = reinterpret_cast<int64_t*>(b + Np); P.kld = b + 2 * Np; P.gc = b + 3 * Np;
-        double* q = b + 4 * Np;
-        P.pi = rip ? q : nullptr; P.si = rip ? q + Np : nullptr; P.cri = rip ? q + 2 * Np : nullptr;
-        q += rip ? 3 * Np : 0;
-        P.seq_index = reinterpret_cast<int32_t*>(q); P.status = reinterpret_cast<uint32_t*>(q) + Np;
-    } else {
-        P.seq_index = c->o_seq.p; P.start = c->o_start.p; P.stop = c->o_stop.p; P.status = c->o_status.p;
-        P.kld = c->o_kld.p; P.gc = c->o_gc.p;
-        P.pi = rip ? c->o_pi.p : nullptr; P.si = rip ? c->o_si.p : nullptr; P.cri = rip ? c->o_cri.p : nullptr;
-    }
-    P.sw = c->o_sw.p; P.sg = c->o_sg.p;
-    P.dbg_counts = dbg_counts ? c->o_counts.p : nullptr;
-    P.dbg_meta = dbg_meta ? c->o_meta.p : nullptr;
-    P.dbg_ivom = nullptr;
-    const size_t nk = size_t(1) << (2 * c->kmax);
-    if (c->want_ivom) {
-        HIPC(c, c->o_ivom.reserve(N * 2 * nk));
-        HIPC(c, hipMemsetAsync(c->o_ivom.p, 0, N * 2 * nk * sizeof(double), c->stream));
-        P.dbg_ivom = c->o_ivom.p;
-    }
-    P.unused_stamps = nullptr;
-    P.rc_tab = c->d_rctab.p; P.in_list = nullptr; P.in_count = nullptr; P.out_list = nullptr; P.out_count = nullptr;
-    P.sel_mode = 0; P.sel_mod = 16; P.queue = nullptr; P.queue_n = 1; P.slide_pp = 0; P.ig_ring = nullptr;
-    P.verdict = nullptr; P.my_form = 0u;
+    const ScanShape shape = scan_shape_of(c, n, w, inc, flags, dbg_counts || dbg_meta);
+    const ScanSchedule sched = plan_scan_schedule(shape);
+    if (sched.error) return fail(c, sched.error_code, sched.error);
     c->scan_stat[0] = 16; c->scan_stat[1] = 0; c->scan_stat[2] = 0; c->scan_stat[3] = 1; c->scan_stat[4] = 0;
 
-    const bool k8 = (c->kmax == 8);
-    // LDS budget: 160 KB per workgroup.  Long windows at K = 8 need a long orphan list; the shared prefix tables
-    // (12 KB, an optimisation only) make room for it.
-    P.lv = shared_level(c->kmin, c->kmax);
-    LdsLayout L = make_layout(c->kmin, c->kmax, P.orphan_cap, P.lv);
-    if (L.total > 160 * 1024 && P.lv) { P.lv = 0; L = make_layout(c->kmin, c->kmax, P.orphan_cap, 0); }
-    if (c->kmax <= 8 && c->plan_maxwin <= 65535 && L.total > 160 * 1024)
-        return fail(c, FRISK_E_ARG, "window too long for the 160 KB LDS of one workgroup");
-    const int wg_per_cu = std::max(1, std::min(2, int(160 * 1024 / L.total)));
-    int grid = int(std::min<int64_t>(n, int64_t(c->num_cu) * wg_per_cu));
-    if (grid >= 8) grid &= ~7;
-    int64_t chunk = n / (int64_t(grid) * 8);
-    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, 8));     // measured: 8 is best, 1..64 within 3 %
-    if (const char* ev = tune_env("FRISK_SCAN_CHUNK")) chunk = std::max<int64_t>(1, std::atoll(ev));   // tuning knob
-    P.chunk = int32_t(chunk);
-    // fast paths: 512-thread workgroups, per-position loops unrolled ITS = 4 / 10 / 16 times (windows up to 2048 /
-    // 5120 / 8192 bases); anything longer (up to 65535): generic 1024-thread kernel with runtime loops
-    const int64_t need = (c->plan_maxwin + 511) / 512;
-    const int its = need <= 4 ? 4 : need <= 10 ? 10 : need <= 16 ? 16 : 0;
+    ScanRun run{c, shape, sched, seq_index, start, stop, status, kld, gc, pi, si, cri, dbg_counts, dbg_meta,
+                ScanParams(), size_t(1) << (2 * c->kmax), {0, 0}};
+    if ((rc = run.reserve(c0, c1))) return rc;
+    if ((rc = run.enqueue())) return rc;
+    return run.collect();
+}
 
-    const bool force_one = tune_env("FRISK_ONE_WG") != nullptr;      // tuning knob: never two workgroups per CU
-    // narrow-counter form (scan8_kernel.h): K = 8, kmin <= 5 (shared prefix level), windows of at most 256 x 20 bases.
-    // width 0 = adaptive (the default), 4 / 8 = fixed, anything else = off (scan_kernel.h's 16-bit form for everything)
-    int width = FRISK_K8_WIDTH;
-    if (const char* ev = tune_env("FRISK_K8_BITS")) width = std::atoi(ev);
-    // (decided by -w alone: rescued small scaffolds beyond the kernel's reach are handed on per window, see scan8_kernel.h)
-    const bool narrow8 = k8 && c->kmin <= 5 && w <= 5120 && c->plan_maxwin <= 65535 && (width == 0 || width == 4 || width == 8);
-    // K = 6, 7: the same kernel with 8-bit counters (a K-mer must occur 256 times in a window to wrap one)
-    const bool narrow7 = (c->kmax == 6 || c->kmax == 7) && c->kmin <= c->kmax - 3 && w <= 5120 && c->plan_maxwin <= 65535 && width != 16;
-    // (the per-max-mer IVOM dump of frisk_scan_ivom is written by scan_kernel.h's debug instantiation only)
-    const bool narrow = (narrow8 || narrow7) && !c->want_ivom;
-    // the 16-bit form (scan_kernel.h) over the candidates that PP names, by window class
-    auto launch16 = [&](const ScanParams& PP, int g, hipStream_t st) -> hipError_t {
-        hipError_t le;
-#define FRISK_LAUNCH16(NT_, K8_, ITS_, DBG_) le = launch_scan<NT_, K8_, ITS_, DBG_>(PP, g, L.total, st)
-        if (k8) {
-            if (debug) { if (its) FRISK_LAUNCH16(512, true, 16, true); else FRISK_LAUNCH16(1024, true, 0, true); }
-            else if (its == 4) FRISK_LAUNCH16(512, true, 4, false);
-            else if (its == 10) FRISK_LAUNCH16(512, true, 10, false);
-            else if (its == 16) FRISK_LAUNCH16(512, true, 16, false);
-            else FRISK_LAUNCH16(1024, true, 0, false);
-        } else {
-            if (debug) { if (its) FRISK_LAUNCH16(512, false, 16, true); else FRISK_LAUNCH16(1024, false, 0, true); }
-            else if (its == 4) FRISK_LAUNCH16(512, false, 4, false);
-            else if (its == 10) FRISK_LAUNCH16(512, false, 10, false);
-            else if (its == 16) FRISK_LAUNCH16(512, false, 16, false);
-            else FRISK_LAUNCH16(1024, false, 0, false);
+}  // namespace
+
+int frisk_scan(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_t c0, int64_t c1, int64_t cap,
+               int32_t* seq_index, int64_t* start, int64_t* stop, uint32_t* status, double* kld, double* gc,
+               double* pi, double* si, double* cri, uint32_t* dbg_counts, int64_t* dbg_meta) {
+    const int rc = scan_impl(c, w, inc, flags, c0, c1, cap, seq_index, start, stop, status, kld, gc, pi, si, cri, dbg_counts, dbg_meta);
+    if (rc != FRISK_OK && c) {
+        // a failure after work was queued: copies may still target the caller's row buffers (and locals of the call), kernels of
+        // the tail segment may still run - nothing of this call is in flight once it has returned
+        const std::string msg = c->err;
+        if (hipSetDevice(c->device) == hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipStreamSynchronize(c->tail_stream);
+            (void)hipGetLastError();
         }
-#undef FRISK_LAUNCH16
-        return le;
-    };
-    // rows [r0, r1) to the caller's buffers
-    auto copy_rows = [&](int64_t r0, int64_t r1, hipStream_t st) -> int {
-        const size_t m = size_t(r1 - r0);
-        if (packed_rows) {              // (always the whole scan: short scans run in one segment) - unpacked behind the final wait
-            HIPC(c, hipMemcpyAsync(c->h_block, c->o_block.p, blk_words * 8, hipMemcpyDeviceToHost, st));
-            return FRISK_OK;
-        }
-        HIPC(c, hipMemcpyAsync(seq_index + r0, P.seq_index + r0, m * 4, hipMemcpyDeviceToHost, st));
-        HIPC(c, hipMemcpyAsync(start + r0, P.start + r0, m * 8, hipMemcpyDeviceToHost, st));
-        HIPC(c, hipMemcpyAsync(stop + r0, P.stop + r0, m * 8, hipMemcpyDeviceToHost, st));
-        HIPC(c, hipMemcpyAsync(status + r0, P.status + r0, m * 4, hipMemcpyDeviceToHost, st));
-        HIPC(c, hipMemcpyAsync(kld + r0, P.kld + r0, m * 8, hipMemcpyDeviceToHost, st));
-        HIPC(c, hipMemcpyAsync(gc + r0, P.gc + r0, m * 8, hipMemcpyDeviceToHost, st));
-        if (rip) {
-            HIPC(c, hipMemcpyAsync(pi + r0, P.pi + r0, m * 8, hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(si + r0, P.si + r0, m * 8, hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(cri + r0, P.cri + r0, m * 8, hipMemcpyDeviceToHost, st));
-        }
-        return FRISK_OK;
-    };
-    bool rows_sent = false;                 // the narrow-counter path finishes and ships its rows itself, in two segments
-    bool verdict_pending = false;           // the adaptive width's verdict was taken on the device in this scan: read back at the end
-    unsigned int novf[34] = {0}, novf_sample[2] = {0, 0};
-    HIPC(c, hipEventRecord(c->ev0, c->stream));
-    hipError_t e = hipSuccess;
-    if (c->plan_maxwin > 65535 || c->kmax > 8) {
-        // windows beyond the 16-bit LDS counters, and every window at K > 8: 32-bit tables of all orders in a global scratch
-        // slice per workgroup
-        const int big_grid = int(std::min<int64_t>(n, c->num_cu));
-        const int64_t stride = (c->nprof + 3) / 4 * 4;
-        HIPC(c, c->d_big.reserve(size_t(big_grid) * size_t(stride)));
-        HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(big_grid) * size_t(stride) * 4, c->stream));
-        if (debug) scan_big_kernel<true><<<big_grid, FRISK_BIG_NT, 0, c->stream>>>(P, c->d_big.p, stride);
-        else scan_big_kernel<false><<<big_grid, FRISK_BIG_NT, 0, c->stream>>>(P, c->d_big.p, stride);
-        e = hipGetLastError();
-    } else
-#define FRISK_LAUNCH(NT_, K8_, ITS_, DBG_) e = launch_scan<NT_, K8_, ITS_, DBG_>(P, grid, L.total, c->stream)
-    if (narrow) {
-        // K = 8 default (scan8_kernel.h): narrow order-8 counters, three (4-bit) or two (8-bit) independent 256-thread
-        // workgroups per CU.  A window with a max-mer that occurs 16+ (256+) times - poly-A, microsatellites, satellite arrays -
-        // wraps a 4-bit (8-bit) counter; the kernel notices and hands it to the next wider form through a device-side list:
-        //     4-bit bulk -> list 1 -> 8-bit -> list 2 -> 16-bit (scan_kernel.h)        or        8-bit bulk -> list 2 -> 16-bit.
-        // Which width suits the bulk depends on the sequence, so (width 0) every 16th chunk of 8 windows is scanned with 4-bit
-        // counters first, and the share of it that had to be handed on decides the width for the other fifteen.  All three
-        // forms give the same bits for a window (same arithmetic; 16-bit only ever sees the windows that wrap 8 bits), so
-        // results do not depend on the choice, on the grid, or on the candidate range.
-        P.ig_ring = nullptr;        // (the ring of scan8_kernel.h: allocated below, where the launch's shape is known)
-        HIPC(c, c->d_ovf_list.reserve(N));
-        HIPC(c, c->d_ovf_list2.reserve(N));
-        HIPC(c, hipMemsetAsync(c->d_ovf_count.p, 0, 64 * sizeof(unsigned int), c->stream));
-        const bool small_w = w <= 2048;
-        // chunks of 16 consecutive windows where the tables slide and the genome-side values travel through the ring (one window
-        // in 16 is counted - and gathered - afresh; measured on the bench shard: 8: 6.71 ms, 12: 6.65, 16: 6.61, 24: 6.79), of 8 otherwise
-        const bool can_slide = 2 * int64_t(inc) <= int64_t(w) - (c->kmax - 1) && !tune_env("FRISK_NO_SLIDE");
-        // (chunks of 32 on long scans, FRISK8_CHUNK_LONG at c34d7fb: inside the noise, NOTES round 4)
-        const int64_t chunk_cap = can_slide ? 16 : 8;
-        int64_t chunk8 = std::max<int64_t>(1, std::min<int64_t>(n / (int64_t(c->num_cu) * 3 * 8), chunk_cap));
-        // A SHORT scan (fewer than 2 x 16 windows per workgroup: BASELINE's C3, a rank's share of a small genome) is dealt statically in
-        // TWO rounds of the launch's workgroups: chunks of ceil(n / (2 x workgroups)) windows, tables sliding and the ring inside a chunk.
-        // Measured (tools/exp/c3_sweep.py, us per scan of the first n windows of the shard; window by window / the best chunk):
-        // 1 500: 55 / 55 (1);  3 000: 87 / 86 (2);  6 000: 160 / 137 (4);  12 063: 303 / 243 (8);  24 000: 550 / 451 (16) - one round
-        // of longer chunks puts every workgroup through the same stage at the same time (12 063 in chunks of 16: 323), chunks dealt by
-        // counters cost such a scan an atomic's round trip per chunk (12 063 in chunks of 8: 269 dealt, 243 static).
-        const int64_t wgs3 = int64_t(c->num_cu) * (narrow8 ? 3 : FRISK_K7_WPS);
-        const bool short_scan = can_slide && n < wgs3 * 2 * 16 && !(flags & FRISK_SCAN_CHUNKS) && !tune_env("FRISK_SCAN_CHUNK");
-        if (short_scan) chunk8 = std::max<int64_t>(1, (n + wgs3 * 2 - 1) / (wgs3 * 2));
-        if (flags & FRISK_SCAN_CHUNKS) chunk8 = 8;
-        if (const char* ev = tune_env("FRISK_SCAN_CHUNK")) chunk8 = std::max<int64_t>(1, std::atoll(ev));
-        // inside a chunk the order-K table slides from window to window where two windows share more than half their bases
-        // (2 inc updates instead of w - K + 1 and a cleared table; scan8_kernel.h)
-        if (can_slide && chunk8 >= 2) P.slide_pp = int32_t((inc + 255) / 256);
-        // the ring through which genome-side values travel from window to window (scan8_kernel.h): a copy of the genome table (one
-        // base address for both) followed by one slice of 20 rows x 512 columns per workgroup launched.  Only the K = 8 / 4-bit
-        // instantiations with the ring read it: launches whose windows slide, and the debug form
-        if (narrow8 && (P.slide_pp > 0 || debug)) {
-            const size_t slices = size_t(std::min<int64_t>(std::max<int64_t>((n + chunk8 - 1) / chunk8, 1), int64_t(c->num_cu) * 4));
-            const double* had = c->d_ig_ring.p;
-            HIPC(c, c->d_ig_ring.reserve(nk + slices * (20 * FRISK8_RING_COLS + FRISK8_RING_PAD)));
-            if (c->d_ig_ring.p != had || c->ring_gen != c->ig_gen) {        // (once per genome table, not once per scan)
-                HIPC(c, hipMemcpyAsync(c->d_ig_ring.p, c->d_ig.p, nk * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-                c->ring_gen = c->ig_gen;
-            }
-            P.ig_ring = c->d_ig_ring.p;
-        }
-        const int64_t nchunks = (n + chunk8 - 1) / chunk8;
-        // (the sample of the adaptive width: every 16th chunk, every 32nd or fewer of a long scan - a short launch runs at two thirds
-        //  of a long one's rate, tools/exp/launch_size.py, and 12 000 windows tell the shares as well as 25 000
-        //  ... and no more chunks than the launch has workgroups - one round: a second chunk for a few of them doubled its time)
-        if (nchunks >= 64 * 32) P.sel_mod = int32_t(std::max<int64_t>(32, (nchunks + int64_t(c->num_cu) * 3 - 1) / (int64_t(c->num_cu) * 3)));
-        // chunks dealt by counters (scan8_kernel.h) where a chunk is long enough to pay for the exchange: a short scan keeps the static deal
-        const bool dealt = chunk8 >= 4 && !short_scan && !tune_env("FRISK_NO_DEAL");
-        int bulk = (width == 4 && narrow8) ? 4 : 8;
-        bool side = false;              // 4-bit bulk with the side table (scan8_kernel.h, SIDE)
-        const bool side_ok = narrow8 && !debug;
-        int sel_mode = 0;
-        bool undecided = false;         // the sample's verdict is on the device: all three bulk forms are queued, one of them runs
-        frisk_ctx::Batch& RB = c->b();
-        const bool hinted = RB.width_hint != 0 && RB.hint_w == w && RB.hint_inc == inc;
-        if (narrow7) { /* 8-bit bulk, no sample */ }
-        else if ((flags & (FRISK_SCAN_BITS4 | FRISK_SCAN_SIDE4)) && narrow8) { bulk = 4; side = (flags & FRISK_SCAN_SIDE4) && side_ok; }
-        else if (width == 0 && !debug && hinted) { bulk = RB.width_hint; side = RB.hint_side && side_ok; }   // same batch, same geometry: the earlier sample still holds
-        else if (width == 0 && !debug && nchunks >= 64 * P.sel_mod) {
-            ScanParams S = P;                   // the sample
-            S.chunk = int32_t(chunk8);
-            S.sel_mode = 1; S.out_list = c->d_ovf_list.p; S.out_count = c->d_ovf_count.p;
-            if (dealt) { S.queue = c->d_ovf_count.p + 8; S.queue_n = 8; }
-            const int64_t nsample = (nchunks + S.sel_mod - 1) / S.sel_mod;
-            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, S, c->num_cu, nsample, c->stream, true));
-            // The verdict is taken ON THE DEVICE (scan8_decide_kernel, one thread behind the sample): the host queues all three bulk forms
-            // behind it, each with the verdict's address and its own number, and two of them return at once - no host synchronisation
-            // in the first scan of a batch (round 3: sample -> copy -> hipStreamSynchronize -> decide -> launch).  The rule:
-            // 4-bit pays while fewer than about three windows in ten have to be redone (round 3, bench shard with simple repeats at
-            // 0.05 / 0.1 / 0.2 / 0.3 per kb = 10 / 20 / 37 / 51 % of the scored windows handed on: 4-bit bulk 7.27 / 7.96 / 8.97 /
-            // 9.98 ms, 8-bit bulk 8.51 / 8.57 / 8.71 / 8.78 ms - tools/exp/width_sweep.sh); the side table pays when the plain form
-            // would hand on more than FRISK_SIDE_SHARE of the windows that are scored (it costs a scored window 1.0 ns - ten
-            // instructions per position: 6.97 against 6.59 ms per scan -, a window handed on 18 ns: tools/exp/side_rate.py)
-            scan8_decide_kernel<<<1, 1, 0, c->stream>>>(c->d_ovf_count.p, static_cast<unsigned int>(nsample * chunk8), double(FRISK_SIDE_SHARE),
-                                                        side_ok ? 1 : 0, c->d_verdict.p);
-            HIPC(c, hipGetLastError());
-            undecided = true;
-            verdict_pending = true;
-            bulk = 4;                           // (what the launch shapes below assume until the verdict is read back)
-            sel_mode = 2;
-            // the sample's own hand-overs now (list 1 -> 8-bit -> list 2 -> 16-bit), so that lists and counters are free for
-            // the bulk segments and no later pass touches rows of another segment
-            ScanParams H = P;
-            H.in_list = c->d_ovf_list.p; H.in_count = c->d_ovf_count.p;
-            H.out_list = c->d_ovf_list2.p; H.out_count = c->d_ovf_count.p + 1;
-            if (dealt) H.queue = c->d_ovf_count.p + 16;
-            HIPC(c, launch_narrow(c->kmax, 8, small_w, false, H, c->num_cu, nsample * chunk8, c->stream));
-            ScanParams H2 = P;
-            H2.in_list = c->d_ovf_list2.p; H2.in_count = c->d_ovf_count.p + 1;
-            int g16 = int(std::min<int64_t>(n, int64_t(c->num_cu)));
-            if (g16 >= 8) g16 &= ~7;
-            HIPC(c, launch16(H2, g16, c->stream));
-            HIPC(c, hipMemcpyAsync(novf_sample, c->d_ovf_count.p, sizeof(novf_sample), hipMemcpyDeviceToHost, c->stream));
-            HIPC(c, hipMemsetAsync(c->d_ovf_count.p, 0, 64 * sizeof(unsigned int), c->stream));
-        }
-        c->scan_stat[0] = bulk;
-        c->scan_stat[4] = side ? 1 : 0;
-        // Rows [r0, r1) of this scan on stream `st`: bulk launch, the two hand-over launches, the rows' scalar tail, and the
-        // rows' scalar tail.  Segment `seg` has its own slice of the two lists (from entry r0) and its own 32 counters: [0], [1]
-        // the lists' lengths, [8..15] the bulk launch's chunk queues (one per XCD), [16] the 8-bit launch's.
-        auto run_rows = [&](int seg, int64_t r0, int64_t r1, hipStream_t st, bool fork_tail) -> int {
-            const int64_t m = r1 - r0;
-            ScanParams R = P;
-            R.c0 = P.c0 + r0; R.c1 = P.c0 + r1;
-            R.seq_index += r0; R.start += r0; R.stop += r0; R.status += r0; R.kld += r0; R.gc += r0; R.sw += r0; R.sg += r0;
-            if (rip) { R.pi += r0; R.si += r0; R.cri += r0; }
-            if (R.dbg_counts) R.dbg_counts += r0 * int64_t(c->nprof);
-            if (R.dbg_meta) R.dbg_meta += r0 * 3;
-            if (R.dbg_ivom) R.dbg_ivom += r0 * 2 * int64_t(nk);
-            unsigned int* cnt = c->d_ovf_count.p + 32 * seg;
-            int64_t* list1 = c->d_ovf_list.p + r0;
-            int64_t* list2 = c->d_ovf_list2.p + r0;
-            ScanParams B = R;                       // the bulk launch
-            B.chunk = int32_t(chunk8);
-            B.sel_mode = sel_mode;
-            if (bulk == 4) { B.out_list = list1; B.out_count = cnt; }
-            else { B.out_list = list2; B.out_count = cnt + 1; }
-            if (dealt) { B.queue = cnt + 8; B.queue_n = 8; }
-            const int64_t mchunks = (m + chunk8 - 1) / chunk8;
-            const int64_t bulk_chunks = sel_mode == 2 ? mchunks - (mchunks + B.sel_mod - 1) / B.sel_mod : mchunks;
-            if (undecided) {                        // plain 4-bit / 4-bit + side table / 8-bit: the device's verdict lets one of them run
-                B.verdict = c->d_verdict.p;
-                B.out_list = list1; B.out_count = cnt;
-                B.my_form = 1u;
-                HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, false));
-                B.my_form = 2u;
-                HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, true));
-                B.my_form = 3u;
-                B.out_list = list2; B.out_count = cnt + 1;
-                HIPC(c, launch_narrow(c->kmax, 8, small_w, false, B, c->num_cu, bulk_chunks, st));
-            } else
-            HIPC(c, launch_narrow(c->kmax, bulk, small_w, debug, B, c->num_cu, bulk_chunks, st, false, side));
-            if (bulk == 4) {                        // list 1 (4-bit hand-overs) -> 8-bit -> list 2
-                ScanParams H = R;
-                H.in_list = list1; H.in_count = cnt;
-                H.out_list = list2; H.out_count = cnt + 1;
-                if (dealt) H.queue = cnt + 16;
-                HIPC(c, launch_narrow(c->kmax, 8, small_w, debug, H, c->num_cu, m, st));
-            }
-            // list 2 -> 16-bit counters, one window per workgroup at a time (a no-op when the list is empty)
-            R.in_list = list2; R.in_count = cnt + 1;
-            int g16 = int(std::min<int64_t>(m, int64_t(c->num_cu)));
-            if (g16 >= 8) g16 &= ~7;
-            HIPC(c, launch16(R, g16, st));
-            if (fork_tail) {        // the tail segment starts here: beside this segment's scalar tail and its rows' way to the host
-                HIPC(c, hipEventRecord(c->ev_fork, st));
-                HIPC(c, hipStreamWaitEvent(c->tail_stream, c->ev_fork, 0));
-            }
-            finish_rows_kernel<<<grid_for(m, 256, 1 << 20), 256, 0, st>>>(m, R.status, R.kld, R.gc, R.sw, R.sg);
-            HIPC(c, hipGetLastError());
-            return FRISK_OK;
-        };
-        // The last sixteenth of a long scan goes to a second stream and starts when the kernels of the first fifteen are done:
-        // it runs while their rows travel to the host (16 MB per 410 k windows: 0.36 ms that used to follow the scan).  The
-        // cut is a multiple of 16 chunks: chunk numbering and the sample's stride stay aligned across it.
-        const int64_t unit = chunk8 * P.sel_mod;
-        int64_t cut = n;
-        // (worth a second launch only when the rows' way to the host is long against a launch: 40 B x 128 K rows ~ 0.1 ms)
-        if (!debug && !c->want_ivom && n >= (int64_t(1) << 17) && n >= 64 * unit && !tune_env("FRISK_ONE_SEGMENT")) {
-            cut = (n / unit - std::max<int64_t>(1, n / unit / 16)) * unit;
-            // ... and the tail is a launch of its own: about a sixteenth of the windows is two chunks per workgroup - 1 616 chunks on 768
-            // workgroups left a tenth of them a third chunk and the others idle (0.78 ms under the profiler for 0.40 ms of work).  So
-            // the tail takes whole rounds: the largest number of chunks <= rounds x workgroups that the cut's alignment allows.
-            const int64_t wgs = int64_t(c->num_cu) * (bulk == 4 ? 3 : 2);
-            const int64_t tail_chunks = (n - cut + chunk8 - 1) / chunk8;
-            if (tail_chunks >= wgs && !tune_env("FRISK_TAIL_ANY")) {
-                const int64_t rounds = (tail_chunks + wgs / 2) / wgs;
-                // (a cut is a whole number of units - the kernels number a segment's chunks from its first candidate - and leaves a tail)
-                cut = std::min((n / unit - 1) * unit, (n - rounds * wgs * chunk8 + unit - 1) / unit * unit);
-            }
-            if (cut <= 0 || cut >= n || cut % unit != 0) return fail(c, FRISK_E_STATE, "frisk_scan: row segments cut off a unit boundary");
-        }
-        rc = run_rows(0, 0, cut, c->stream, cut < n);
-        if (rc) return rc;
-        if (cut < n) {
-            rc = run_rows(1, cut, n, c->tail_stream, false);
-            if (rc) return rc;
-            HIPC(c, hipEventRecord(c->ev_tail_kernels, c->tail_stream));
-            rc = copy_rows(cut, n, c->tail_stream);
-            if (rc) return rc;
-            HIPC(c, hipEventRecord(c->ev_tail_done, c->tail_stream));
-            rc = copy_rows(0, cut, c->stream);
-            if (rc) return rc;
-            HIPC(c, hipStreamWaitEvent(c->stream, c->ev_tail_kernels, 0));
-            HIPC(c, hipEventRecord(c->ev1, c->stream));                     // every scan kernel of this call has finished
-            HIPC(c, hipStreamWaitEvent(c->stream, c->ev_tail_done, 0));
-        } else {
-            HIPC(c, hipEventRecord(c->ev1, c->stream));
-            rc = copy_rows(0, n, c->stream);
-            if (rc) return rc;
-        }
-        rows_sent = true;
-        c->scan_stat[3] = cut < n ? 2 : 1;
-    } else if (k8) {
-        e = launch16(P, grid, c->stream);
-    } else if (!debug && !force_one && c->plan_maxwin <= 5120 && L.total <= 80 * 1024) {
-        // K <= 7: the tables of a window take < 60 KB, so TWO independent 256-thread workgroups fit a CU.  The two waves of
-        // a SIMD then belong to different windows in different stages, and the LDS phases of one overlap the VALU phases of
-        // the other: measured -23 % (K = 7) and -26 % (K = 6) against one 512-thread workgroup with the same code.
-        grid = int(std::min<int64_t>(n, int64_t(c->num_cu) * 2));
-        if (grid >= 8) grid &= ~7;
-        P.chunk = int32_t(std::max<int64_t>(1, std::min<int64_t>(n / (int64_t(grid) * 8), 8)));
-        if (c->plan_maxwin <= 2048) FRISK_LAUNCH(256, false, 8, false); else FRISK_LAUNCH(256, false, 20, false);
-    } else {
-        e = launch16(P, grid, c->stream);
+        c->err = msg;
     }
-#undef FRISK_LAUNCH
-    HIPC(c, e);
-    if (!rows_sent) {
-        if (c->plan_maxwin <= 65535 && c->kmax <= 8 && n > 0) {     // the LDS kernels leave the rows' scalar tail to one thread per row
-            finish_rows_kernel<<<grid_for(n, 256, 1 << 20), 256, 0, c->stream>>>(n, P.status, P.kld, P.gc, P.sw, P.sg);
-            HIPC(c, hipGetLastError());
-        }
-        HIPC(c, hipEventRecord(c->ev1, c->stream));
-        rc = copy_rows(0, n, c->stream);
-        if (rc) return rc;
-    }
-    if (dbg_counts)
-        HIPC(c, hipMemcpyAsync(dbg_counts, c->o_counts.p, N * size_t(c->nprof) * 4, hipMemcpyDeviceToHost, c->stream));
-    if (dbg_meta) HIPC(c, hipMemcpyAsync(dbg_meta, c->o_meta.p, N * 3 * 8, hipMemcpyDeviceToHost, c->stream));
-    if (c->want_ivom) HIPC(c, hipMemcpyAsync(c->want_ivom, c->o_ivom.p, N * 2 * nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (narrow) HIPC(c, hipMemcpyAsync(novf, c->d_ovf_count.p, sizeof(novf), hipMemcpyDeviceToHost, c->stream));
-    unsigned int verdict_host[4] = {0, 0, 0, 0};
-    if (verdict_pending) HIPC(c, hipMemcpyAsync(verdict_host, c->d_verdict.p, sizeof(verdict_host), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (verdict_pending) {              // what the device decided: remembered per batch and geometry (later scans launch that form alone)
-        frisk_ctx::Batch& VB = c->b();
-        VB.width_hint = verdict_host[0] == 3u ? 8 : 4; VB.hint_w = w; VB.hint_inc = inc; VB.hint_side = verdict_host[0] == 2u ? 1 : 0;
-        c->scan_stat[0] = VB.width_hint;
-        c->scan_stat[4] = VB.hint_side;
-    }
-    if (packed_rows) {
-        const double* b = static_cast<const double*>(c->h_block);
-        std::memcpy(start, b, N * 8); std::memcpy(stop, b + Np, N * 8); std::memcpy(kld, b + 2 * Np, N * 8); std::memcpy(gc, b + 3 * Np, N * 8);
-        const double* q = b + 4 * Np;
-        if (rip) { std::memcpy(pi, q, N * 8); std::memcpy(si, q + Np, N * 8); std::memcpy(cri, q + 2 * Np, N * 8); q += 3 * Np; }
-        std::memcpy(seq_index, q, N * 4); std::memcpy(status, reinterpret_cast<const uint32_t*>(q) + Np, N * 4);
-    }
-    c->scan_stat[1] = novf[0] + novf[32] + novf_sample[0];
-    c->scan_stat[2] = novf[1] + novf[33] + novf_sample[1];
-    if (c->b().tiled)               // descriptor index -> index of the scaffold in the FASTA
-        for (size_t r = 0; r < N; ++r) seq_index[r] = c->b().tiles[size_t(seq_index[r])].scaf;
-    float ms = 0;
-    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->ms[0] = ms;
-    return FRISK_OK;
+    return rc;
 }
 
 int frisk_scan_ivom(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_t c0, int64_t c1, int64_t cap,
@@ -2018,16 +1946,28 @@ char* frisk_format_rows(int64_t n, const char* const* names, const int32_t* seq_
 void frisk_free(void* p) { std::free(p); }
 
 // ---- host-native 2-state Gaussian HMM (hmm_host.h): the model frisk_amd/hmm.py documents, for millions of windows ----------
-int frisk_hmm_fit(const double* x, int64_t n, int32_t n_iter, double tol, double min_covar, double covars_prior, double* means,
-                  double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
-    if (!x || n < 1 || n_iter < 0 || !means || !covars || !startprob || !transmat) return FRISK_E_ARG;
-    for (int64_t t = 0; t < n; ++t) if (!std::isfinite(x[t])) return FRISK_E_ARG;
-    const frisk_hmm::Fit F = frisk_hmm::fit(x, n, n_iter, tol, min_covar, covars_prior);
+namespace {
+frisk_hmm::Model model_of(const double* means, const double* covars, const double* startprob, const double* transmat) {
+    frisk_hmm::Model m;
+    for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
+    for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];
+    return m;
+}
+int fit_out(const frisk_hmm::Fit& F, double* means, double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
     for (int i = 0; i < 2; ++i) { means[i] = F.m.means[i]; covars[i] = F.m.covars[i]; startprob[i] = F.m.startprob[i]; }
     for (int i = 0; i < 4; ++i) transmat[i] = F.m.transmat[i];
     if (loglik) *loglik = F.loglik;
     if (iters) *iters = F.iters;
     return FRISK_OK;
+}
+}  // namespace
+
+int frisk_hmm_fit(const double* x, int64_t n, int32_t n_iter, double tol, double min_covar, double covars_prior, double* means,
+                  double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
+    if (!x || n < 1 || n_iter < 0 || !means || !covars || !startprob || !transmat) return FRISK_E_ARG;
+    for (int64_t t = 0; t < n; ++t) if (!std::isfinite(x[t])) return FRISK_E_ARG;
+    const frisk_hmm::Fit F = frisk_hmm::fit(x, n, n_iter, tol, min_covar, covars_prior);
+    return fit_out(F, means, covars, startprob, transmat, loglik, iters);
 }
 
 int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, const double* means, const double* covars,
@@ -2036,9 +1976,7 @@ int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, co
     for (int32_t s = 0; s < n_seg; ++s) if (seg_off[s + 1] < seg_off[s]) return FRISK_E_ARG;
     if (n_seg == 0 || seg_off[n_seg] == seg_off[0]) return FRISK_OK;
     if (!x || !states) return FRISK_E_ARG;
-    frisk_hmm::Model m;
-    for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
-    for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];
+    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
     frisk_hmm::viterbi_segments(x, seg_off, n_seg, m, states);
     return FRISK_OK;
 }
@@ -2055,12 +1993,6 @@ bool estep_args_ok(const double* x, int64_t n, const double* means, const double
     for (int i = 0; i < 4; ++i) if (!(transmat[i] >= 0.0 && transmat[i] <= 1.0)) return false;
     for (int64_t t = 0; t < n; ++t) if (!std::isfinite(x[t])) return false;
     return true;
-}
-frisk_hmm::Model model_of(const double* means, const double* covars, const double* startprob, const double* transmat) {
-    frisk_hmm::Model m;
-    for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
-    for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];
-    return m;
 }
 }  // namespace
 
@@ -2130,11 +2062,7 @@ int frisk_hmm_fit_gpu(int device, const double* x, int64_t n, int32_t n_iter, do
     if (!on.ok) return FRISK_E_HIP;
     frisk_hmm::Fit F;
     if (frisk_hmm_gpu::fit(x, n, n_iter, tol, min_covar, covars_prior, F)) return FRISK_E_HIP;
-    for (int i = 0; i < 2; ++i) { means[i] = F.m.means[i]; covars[i] = F.m.covars[i]; startprob[i] = F.m.startprob[i]; }
-    for (int i = 0; i < 4; ++i) transmat[i] = F.m.transmat[i];
-    if (loglik) *loglik = F.loglik;
-    if (iters) *iters = F.iters;
-    return FRISK_OK;
+    return fit_out(F, means, covars, startprob, transmat, loglik, iters);
 }
 
 int frisk_hmm_estep_gpu(int device, const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
@@ -2153,9 +2081,7 @@ int frisk_hmm_viterbi_gpu(int device, const double* x, const int64_t* seg_off, i
     if (n_seg == 0 || seg_off[n_seg] == seg_off[0]) return FRISK_OK;
     if (!x || !states || seg_off[n_seg] - seg_off[0] > (int64_t(1) << 40)) return FRISK_E_ARG;
     if (!all_finite(x + seg_off[0], seg_off[n_seg] - seg_off[0])) return FRISK_E_ARG;
-    frisk_hmm::Model m;
-    for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
-    for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];
+    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
     frisk_proj::OnDevice on(device);
     if (!on.ok) return FRISK_E_HIP;
     return frisk_hmm_gpu::viterbi_segments(x, seg_off, n_seg, m, states) ? FRISK_E_HIP : FRISK_OK;

@@ -1,6 +1,7 @@
 """The library's host-only code under AddressSanitizer + UBSan on the CPU (the GPU pool offers no sanitizers): tools/exp/san_host.cpp
 runs the 2-bit packer - the 8-letter form and, where the host has AVX-512BW + BMI2, the 64-letter form - against a letter-by-letter
-restatement, bitmap -> runs, the FASTA reader and the seek index on awkward files, and the HMM on series of awkward lengths."""
+restatement, bitmap -> runs, the FASTA reader and the seek index on awkward files, the HMM on series of awkward lengths, and the
+scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes and named shapes against hand-derived values."""
 import os
 import shutil
 import subprocess

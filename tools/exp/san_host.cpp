@@ -1,7 +1,8 @@
 // (CPU) the library's host-only headers under AddressSanitizer + UBSan (GPU sanitizers are not available on the pool): random batches
 // through the 2-bit packer (against a letter-by-letter restatement), bitmap -> runs, the HMM fit / Viterbi on random series of awkward
-// lengths.  build + run:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifrisk_amd/csrc
-//                         tools/exp/san_host.cpp -o build/san/san_host -lpthread -lz && build/san/san_host
+// lengths, and the scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes, named shapes against values worked out by
+// hand.  build + run:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifrisk_amd/csrc
+//                      tools/exp/san_host.cpp -o build/san/san_host -lpthread -lz && build/san/san_host
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -10,13 +11,146 @@
 #include "hmm_host.h"
 #include "fasta_index.h"
 #include "fasta_pack2.h"
+#include "scan_schedule.h"
 #include <fstream>
 #include <unistd.h>
 
 static int fails = 0;
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #c); ++fails; } } while (0)
 
+// make_layout(1, K, scan_orphan_cap(maxwin), lv).total restated (scan_kernel.h is a HIP header): order-8 table, 16-bit tables of the
+// orders 1..min(K, 6) or 1..K, orphan list (K = 8), prefix tables of level 5, window constants + log table + counters and scratch
+static uint32_t lds_of(int K, int64_t maxwin, int lv) {
+    int64_t bins = 0;
+    for (int k = 1; k <= (K == 8 ? 6 : K); ++k) bins += int64_t(1) << (2 * k);
+    int64_t o = (K == 8 ? 131072 : 0) + (bins * 2 + 15) / 16 * 16;
+    if (K == 8) o += (scan_orphan_cap(maxwin) * 2 + 15) / 16 * 16;
+    if (lv) o += 1024 * 8 + 1024 * 4;
+    return uint32_t(o + 16 * 8 + 128 * 16 + (2 * 16 * 4 + 16 * 6 * 8));
+}
+static ScanShape shape_of(int K, int num_cu, int64_t n, int w, int inc, uint32_t flags = 0, int hint = 0, int hint_side = 0, bool debug = false) {
+    ScanShape s = ScanShape();
+    s.kmin = 1; s.kmax = K; s.num_cu = num_cu; s.n = n; s.w = w; s.inc = inc; s.flags = flags; s.plan_maxwin = w; s.debug = debug;
+    s.rip = (flags & FRISK_SCAN_RIP) != 0;
+    s.width_hint = hint; s.hint_side = hint_side; s.hint_matches = true;
+    s.lv_shared = K >= 6 ? 5 : 0;
+    s.lds_shared = lds_of(K, w, s.lv_shared); s.lds_level0 = lds_of(K, w, 0);
+    return s;
+}
+
+static long long check_scan_schedule() {          // -> schedules planned
+    const int64_t two17 = int64_t(1) << 17;
+    // (a) invariants over a sweep
+    const int64_t ns[] = {1, 2, 7, 8, 9, 40, 200, 767, 3000, 12063, 24575, 24576, 24577, two17 - 1, two17, two17 + 1, 386173, 1000000, 3058000, 4000000};
+    const uint32_t flag_sets[] = {0u, FRISK_SCAN_CHUNKS, FRISK_SCAN_BITS4, FRISK_SCAN_SIDE4, FRISK_SCAN_CHUNKS | FRISK_SCAN_SIDE4 | FRISK_SCAN_RIP};
+    const int hints[][2] = {{0, 0}, {4, 0}, {4, 1}, {8, 0}};
+    int64_t plans = 0, two_segments = 0, sampled = 0;
+    for (int64_t n : ns) for (int num_cu : {1, 8, 256}) for (int K : {4, 6, 7, 8, 9}) for (int w : {400, 2048, 2049, 5000, 5120, 5121}) {
+        const int edge = (w - (K - 1)) / 2;                     // the largest inc with 2 inc <= w - (K - 1)
+        for (int inc : {1, w / 4, edge - 1, edge, edge + 1, w / 2, w / 2 + 1, w}) for (uint32_t flags : flag_sets) for (const auto& h : hints) for (int debug = 0; debug < 2; ++debug) {
+            ScanShape s = shape_of(K, num_cu, n, w, inc, flags, h[0], h[1], debug != 0);
+            const ScanSchedule S = plan_scan_schedule(s);
+            ++plans;
+            CHECK(S.error == nullptr);
+            if (S.error) continue;
+            CHECK(S.grid >= 1 && (S.grid < 8 || S.grid % 8 == 0));
+            CHECK(S.packed_rows == (n < two17));
+            CHECK(S.chunk >= 1 && S.orphan_cap == w / 8 + 2 && S.lds_total <= 160u * 1024 + (K > 8 ? ~0u / 2 : 0u));
+            CHECK((S.segments == 2) == (0 < S.cut && S.cut < n) && (S.segments == 1 || S.segments == 2) && (S.segments == 2 || S.cut == n));
+            CHECK((S.path == SCAN_PATH_BIG) == (K > 8) && S.big_grid == (K > 8 ? int(std::min<int64_t>(n, num_cu)) : 0));
+            if (S.packed_rows) {
+                const RowBlock& b = S.block;
+                const size_t N = size_t(n), cols[] = {b.start, b.stop, b.kld, b.gc};
+                for (int i = 0; i < 4; ++i) CHECK(cols[i] == (i ? cols[i - 1] + (N + 1) / 2 * 2 : 0) && cols[i] + N <= (i < 3 ? cols[i + 1] : s.rip ? b.pi : b.seq_index));
+                if (s.rip) CHECK(b.gc + N <= b.pi && b.pi + N <= b.si && b.si + N <= b.cri && b.cri + N <= b.seq_index);
+                // (offsets are in 8-byte words: the two 4-byte columns start on a multiple of 8 bytes and do not meet)
+                CHECK(b.seq_index * 8 + N * 4 <= b.status * 8 && b.status * 8 + N * 4 <= b.words * 8);
+            }
+            if (S.path != SCAN_PATH_NARROW) {
+                CHECK(!S.sample && !S.side && S.ring_slices == 0 && S.slide_pp == 0 && S.segments == 1 && S.bulk == 16);
+                continue;
+            }
+            CHECK((K == 8 && w <= 5120 && S.narrow8) || ((K == 6 || K == 7) && w <= 5120 && !S.narrow8));
+            CHECK(S.chunk8 >= 1 && S.nchunks == (n + S.chunk8 - 1) / S.chunk8);
+            CHECK(S.can_slide == (2 * inc <= w - (K - 1)));
+            CHECK(S.slide_pp == 0 || (S.can_slide && S.chunk8 >= 2));
+            CHECK(!S.dealt || (S.chunk8 >= 4 && !S.short_scan));
+            if (S.segments == 2) CHECK(S.cut % (S.chunk8 * S.sel_mod) == 0 && n >= two17 && !debug);
+            CHECK(!S.sample || (S.nchunks >= 64 * S.sel_mod && !debug && h[0] == 0 && S.bulk == 4 && S.sel_mode == 2 && S.nsample == (S.nchunks + S.sel_mod - 1) / S.sel_mod));
+            CHECK(S.sample || (S.sel_mode == 0 && S.nsample == 0));
+            CHECK(!S.side || (S.narrow8 && S.bulk == 4 && !debug));
+            CHECK(S.bulk == 4 || S.bulk == 8);
+            CHECK(S.ring_slices == 0 || (S.narrow8 && (S.slide_pp > 0 || debug) && S.ring_slices <= 4 * int64_t(num_cu) && S.ring_slices <= S.nchunks));
+            two_segments += S.segments == 2; sampled += S.sample;
+        }
+    }
+    CHECK(two_segments > 1000 && sampled > 1000);              // (the sweep reaches both)
+    // (b) named shapes: 256 CUs, K = 1..8, w = 5000, inc = 1000, no flags, no hint, not debug.  Every value below is worked out by hand
+    // from the rules ("frisk_scan in five steps"; the measurements behind them are in NOTES.md)
+    {   // BASELINE's C3: short (< 2 x 16 windows per workgroup of 768): two static rounds, ceil(12 063 / 1 536) = 8 windows per chunk
+        const ScanSchedule S = plan_scan_schedule(shape_of(8, 256, 12063, 5000, 1000));
+        CHECK(S.path == SCAN_PATH_NARROW && S.narrow8 && !S.small_w && S.chunk8 == 8 && S.short_scan && S.slide_pp == 4 && S.nchunks == 1508);
+        CHECK(S.sel_mod == 16 && !S.dealt && S.sample && S.nsample == 95 && S.ring_slices == 1024 && S.cut == 12063 && S.segments == 1 && S.packed_rows);
+        CHECK(S.lv == 5 && S.lds_total == 158624 && S.grid == 256 && S.its == 10 && S.orphan_cap == 627);
+    }
+    {   // the bench shard: chunks of 16, dealt; 24 136 chunks, every 32nd sampled; units of 512 windows, 754 whole ones: the tail first takes
+        // 47 units (1 512 chunks), which is 2 rounds of 768 workgroups = 24 576 windows, and the cut rounds up to unit 707
+        ScanShape s = shape_of(8, 256, 386173, 5000, 1000);
+        ScanSchedule S = plan_scan_schedule(s);
+        CHECK(S.chunk8 == 16 && !S.short_scan && S.slide_pp == 4 && S.nchunks == 24136 && S.sel_mod == 32 && S.dealt && S.sample && S.nsample == 755);
+        CHECK(S.ring_slices == 1024 && S.cut == 361984 && S.segments == 2 && !S.packed_rows && S.bulk == 4 && S.sel_mode == 2);
+        s.width_hint = 8;               // 8-bit bulk on 512 workgroups: 3 rounds, the same 24 576 windows
+        S = plan_scan_schedule(s);
+        CHECK(S.cut == 361984 && !S.sample && S.bulk == 8 && S.sel_mode == 0 && !S.side);
+        s.hint_matches = false;         // a hint taken with another geometry does not count
+        CHECK(plan_scan_schedule(s).sample);
+    }
+    {   // 2^17: the shortest scan in two segments - 256 units, the last 16 (512 chunks, less than a round) on the tail stream
+        const ScanSchedule S = plan_scan_schedule(shape_of(8, 256, two17, 5000, 1000));
+        CHECK(S.nchunks == 8192 && S.sel_mod == 32 && S.cut == 122880 && S.segments == 2 && !S.packed_rows);
+        const ScanSchedule T = plan_scan_schedule(shape_of(8, 256, two17 - 1, 5000, 1000));
+        CHECK(T.cut == two17 - 1 && T.segments == 1 && T.packed_rows);
+    }
+    {   // a long scan: 191 125 chunks, the sample one round of 768 workgroups (stride 249); units of 3 984, tail of 15 rounds
+        const ScanSchedule S = plan_scan_schedule(shape_of(8, 256, 3058000, 5000, 1000));
+        CHECK(S.chunk8 == 16 && S.nchunks == 191125 && S.sel_mod == 249 && S.nsample == 768 && S.cut == 2876448 && S.segments == 2);
+    }
+    {   // 40 windows: one per chunk, nothing slides, so no ring either
+        const ScanSchedule S = plan_scan_schedule(shape_of(8, 256, 40, 5000, 1000));
+        CHECK(S.chunk8 == 1 && S.short_scan && S.slide_pp == 0 && !S.sample && S.ring_slices == 0 && S.nchunks == 40 && S.grid == 40);
+    }
+    for (int inc : {2500, 2497}) {      // 2 inc > w - 7: not sliding, window by window; 3 000 chunks >= 64 x 32: stride 32, 94 sampled
+        const ScanSchedule S = plan_scan_schedule(shape_of(8, 256, 3000, 5000, inc));
+        CHECK(!S.can_slide && S.chunk8 == 1 && S.sel_mod == 32 && S.sample && S.nsample == 94 && S.slide_pp == 0 && S.ring_slices == 0);
+    }
+    CHECK(plan_scan_schedule(shape_of(8, 256, 3000, 5000, 2496)).can_slide);
+    {   // FRISK_SCAN_CHUNKS: chunks of 8 dealt by counters whatever the size
+        const ScanSchedule S = plan_scan_schedule(shape_of(8, 256, 200, 400, 150, FRISK_SCAN_CHUNKS));
+        CHECK(S.small_w && S.chunk8 == 8 && S.dealt && !S.short_scan && S.slide_pp == 1 && !S.sample && S.nchunks == 25 && S.ring_slices == 25);
+    }
+    {   // the other paths, the LDS fall-back and the two refusals
+        CHECK(plan_scan_schedule(shape_of(6, 256, 5000, 400, 150)).path == SCAN_PATH_NARROW);
+        const ScanSchedule S4 = plan_scan_schedule(shape_of(4, 256, 5000, 400, 150));
+        CHECK(S4.path == SCAN_PATH_TWO_WG && S4.grid == 512 && S4.chunk == 1 && S4.its == 8);
+        CHECK(plan_scan_schedule(shape_of(4, 256, 5000, 400, 150, 0, 0, 0, true)).path == SCAN_PATH_16BIT);
+        const ScanSchedule S8 = plan_scan_schedule(shape_of(8, 256, 5000, 5121, 1000));
+        CHECK(S8.path == SCAN_PATH_16BIT && S8.its == 16 && S8.grid == 256 && S8.chunk == 2);
+        ScanShape s = shape_of(8, 256, 5000, 5000, 1000);
+        s.plan_maxwin = 60000; s.lds_shared = lds_of(8, 60000, 5); s.lds_level0 = lds_of(8, 60000, 0);       // a rescued scaffold of 60 kb
+        ScanSchedule S = plan_scan_schedule(s);
+        CHECK(s.lds_shared > 160u * 1024 && S.error == nullptr && S.lv == 0 && S.lds_total == s.lds_level0 && S.its == 0 && S.path == SCAN_PATH_NARROW);
+        s.lds_level0 = 160 * 1024 + 16;
+        S = plan_scan_schedule(s);
+        CHECK(S.error && std::string(S.error) == "window too long for the 160 KB LDS of one workgroup" && S.error_code == FRISK_E_ARG);
+        s.plan_maxwin = 65536;
+        S = plan_scan_schedule(s);
+        CHECK(S.error == nullptr && S.path == SCAN_PATH_BIG && S.big_grid == 256);
+    }
+    return (long long)plans;
+}
+
 int main() {
+    const long long plans = check_scan_schedule();
     std::mt19937_64 rng(12345);
     const char alphabet[] = "ACGTacgtNnRYKM-*xACGTACGTACGT";
     for (int round = 0; round < 300; ++round) {
@@ -158,6 +292,6 @@ int main() {
         }
         ::unlink(path.c_str());
     }
-    std::printf("%s (%d failed checks; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
+    std::printf("%s (%d failed checks; %lld scan schedules; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
     return fails ? 1 : 0;
 }
