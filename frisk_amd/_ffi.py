@@ -102,6 +102,15 @@ SYMBOLS = [
     ("frisk_ipca_transform", C.c_int, [_P, _P, C.c_int64, _P]),
     ("frisk_ipca_last_ms", C.c_double, [_P, C.c_int]),
     ("frisk_ipca_destroy", None, [_P]),
+    ("frisk_nmf_create", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_P)]),
+    ("frisk_nmf_xq", C.c_int, [_P, _P, C.c_int32, _P]),
+    ("frisk_nmf_xtq", C.c_int, [_P, _P, C.c_int32, _P]),
+    ("frisk_nmf_step", C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(C.c_double)]),
+    ("frisk_nmf_get", C.c_int, [_P, _P, _P]),
+    ("frisk_nmf_set", C.c_int, [_P, _P, _P]),
+    ("frisk_nmf_transform_prepare", C.c_int, [_P]),
+    ("frisk_nmf_last_ms", C.c_double, [_P, C.c_int]),
+    ("frisk_nmf_destroy", None, [_P]),
     ("frisk_host_alloc", C.c_void_p, [_P, C.c_int64]),
     ("frisk_host_free", None, [_P, _P]),
     ("frisk_last_kernel_ms", C.c_double, [_P, C.c_int]),

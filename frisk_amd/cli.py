@@ -9,6 +9,8 @@ caches, GFF3) and the same row echo on stdout.  Phase A and phase B run through 
 --runProjection PCA, PY-TSNE (the reference's exact t-SNE, Y0 seeded by --seed, 0 when not given), MDS (sklearn's metric MDS,
 its starts seeded the same way) or IncrementalPCA (sklearn's, in batches of 5 F rows) with --cluster DBSCAN / KMEANS runs
 frisk_amd.projection on the GPU and writes the cluster-labelled GFF3.
+--runProjection NMF (sklearn's coordinate-descent NMF from the nndsvda start, seeded the same way) runs on the GPU too and, with
+--dumpPCAdata, writes the projection as the pickle anomNMF; --cluster after NMF is still reported as unavailable (no cluster GFF3).
 --updateHMM (with --updateWin / --updateInc; the reference advertises them as a future function and never wired them) scans the
 query again with the fine window, segments that track with the device HMM (csrc/hmm_kernels.h), writes it to
 updateWin_<w>_inc_<i>_<hmmOutfile>, and - with --gffOutfile - writes the anomalies with every boundary moved to the nearest
@@ -19,7 +21,7 @@ records of the annotation whose type is one of --gffFeatures and that lie within
 featuresIn_thresholded_Anomalies_<basename of gffIn>, and with --hmmKLD those near a State1 / State2 interval of the main track to
 featuresIn_hmm_State1_<basename> / featuresIn_hmm_State2_<basename> - `bedtools window -w gffRange -u` restated on the host
 (frisk_amd.postprocess.window_u); a file is written only when it has a record.  Rank 0, not under --exitAfter; no other output changes.
-Out of scope here: the other projections (SKL-TSNE, NMF) and SPECTRAL clustering,
+Out of scope here: the other projection (SKL-TSNE) and SPECTRAL clustering,
 --graphics (seaborn/matplotlib).
 Those options are accepted, as in the reference, and reported as unavailable if used.
 
@@ -79,7 +81,7 @@ def build_parser():
     p.add_argument("--peakCRI", type=float, default=1.0)
     p.add_argument("--minPI", type=float, default=1.0)
     p.add_argument("--maxSI", type=float, default=1.0)
-    # projection / clustering (PCA, PY-TSNE, MDS, IncrementalPCA, DBSCAN and KMEANS built; the other methods accepted, not available
+    # projection / clustering (PCA, PY-TSNE, MDS, IncrementalPCA, NMF, DBSCAN and KMEANS built; the other methods accepted, not available
     # in this build)
     p.add_argument("--runProjection", default=None, choices=[None, "PCA", "PY-TSNE", "SKL-TSNE", "IncrementalPCA", "NMF", "MDS"])
     p.add_argument("--projectionDims", type=int, default=2)
@@ -105,12 +107,15 @@ def build_parser():
 
 
 PROJECTIONS = ("PCA", "PY-TSNE", "MDS", "IncrementalPCA")     # --runProjection methods built here (frisk_amd.projection)
+PROJECTIONS_UNCLUSTERED = ("NMF",)      # built here too, but --cluster on them is still reported as unavailable (see unavailable)
 CLUSTERINGS = ("DBSCAN", "KMEANS")      # --cluster methods built here
 
 
 def unavailable(args):
     """(option, reason) of every given option this build accepts but does not run.  --cluster runs only as DBSCAN or KMEANS
-    after --runProjection PCA, PY-TSNE, MDS or IncrementalPCA (the reference clusters the projection, L1635-1655)."""
+    after --runProjection PCA, PY-TSNE, MDS or IncrementalPCA (the reference clusters the projection, L1635-1655).  The NMF
+    projection runs (PROJECTIONS_UNCLUSTERED), but clustering it is still reported as unavailable and writes no cluster GFF3:
+    tests/test_projection_cluster_cpu.py pins ("NMF", "DBSCAN") to this warning.  Moving "NMF" into PROJECTIONS lifts that."""
     clustering = args.runProjection in PROJECTIONS and args.cluster in CLUSTERINGS
     out = []
     for opt, why in (("cluster", "sklearn clustering is out of scope"), ("graphics", "plotting is out of scope")):
@@ -272,8 +277,9 @@ def _seed(args):
 
 
 def _project(args, anomCounts, device, clock):
-    """--runProjection PCA (L1612-1613), PY-TSNE (L1622-1623), MDS (L1624-1627) or IncrementalPCA (L1629-1631) on the anomalies' k-mer
-    proportions, then --cluster DBSCAN / KMEANS on the projection (L1635-1655).  Returns the cluster labels (None without a clustering this build runs)."""
+    """--runProjection PCA (L1612-1613), PY-TSNE (L1622-1623), MDS (L1624-1627), IncrementalPCA (L1629-1631) or NMF (L1632-1636) on
+    the anomalies' k-mer proportions, then --cluster DBSCAN / KMEANS on the projection (L1635-1655), except after NMF.  Returns the
+    cluster labels (None without a clustering this build runs)."""
     from . import projection as P
     if args.runProjection == "PY-TSNE":
         n = anomCounts.shape[0]
@@ -298,6 +304,15 @@ def _project(args, anomCounts, device, clock):
                  "eigh %.1f ms, transform %.1f ms", anomCounts.shape[0], anomCounts.shape[1], len(res.batch_sizes),
                  res.explained_variance_.tolist(), res.timings["stats_gram_ms"], res.timings["eigh_ms"],
                  res.timings["transform_ms"])
+    elif args.runProjection == "NMF":
+        res = P.nmf(anomCounts, args.projectionDims, seed=_seed(args), device=device)
+        log.info("NMF of %s x %s k-mer proportions: %s iterations (transform %s), last violation ratio %s; init %.1f ms, "
+                 "fit %.1f ms, transform %.1f ms", anomCounts.shape[0], anomCounts.shape[1], res.n_iter, res.transform_n_iter,
+                 res.violation_ratios[-1] if res.violation_ratios else 0.0, res.timings["init_ms"], res.timings["fit_ms"],
+                 res.timings["transform_ms"])
+        if args.dumpPCAdata:                                                # the projection itself, beside anomLabels / anomCounts
+            with open(os.path.join(args.tempDir, "anomNMF"), "wb") as fh:
+                pickle.dump(res.Y, fh, protocol=2)
     else:
         res = P.pca(anomCounts, args.projectionDims, device=device)
         log.info("PCA of %s x %s k-mer proportions: explained variance %s; covariance %.1f ms, eigh %.1f ms, transform %.1f ms",
@@ -305,6 +320,8 @@ def _project(args, anomCounts, device, clock):
                  res.timings["eigh_ms"], res.timings["transform_ms"])
     clock.lap(args.runProjection)
     y_pred = None
+    if args.runProjection in PROJECTIONS_UNCLUSTERED:
+        return None
     if args.cluster == "DBSCAN":
         y_pred = P.dbscan(res.Y, args.epsDBSCAN, device=device)
     elif args.cluster == "KMEANS":
@@ -374,8 +391,11 @@ def _main(argv=None):
         os.makedirs(os.path.abspath(args.tempDir))
     if sharded:
         dist.barrier()      # tempDir exists, and every rank sees the same cache files, before anyone looks for them
-    projection = args.runProjection in PROJECTIONS            # a projection this build runs
+    projection = args.runProjection in PROJECTIONS            # a projection this build runs and clusters
     clustering = projection and args.cluster in CLUSTERINGS
+    # NMF runs, but every file written under --runProjection NMF before it was built stays as it was: the merged anomalies in
+    # --gffOutfile and no cluster GFF3.  Both follow PROJECTIONS, so moving "NMF" there switches them together.
+    projected_only = args.runProjection in PROJECTIONS_UNCLUSTERED
     for opt, why in unavailable(args):
         log.warning("--%s is not available in this build: %s", opt, why)
     update = bool(args.updateHMM)
@@ -576,7 +596,7 @@ def _main(argv=None):
                     pickle.dump(anomLabels, fh, protocol=2)
                 with open(os.path.join(args.tempDir, "anomCounts"), "wb") as fh:
                     pickle.dump(anomCounts, fh, protocol=2)
-            if projection:
+            if projection or projected_only:
                 y_pred = _project(args, anomCounts, local_rank, clock)
             else:
                 log.info("Symmetric k-mer proportions of %s anomalous windows computed; the %s projection is not built here.",

@@ -34,6 +34,7 @@
 #include "tsne_kernels.h"
 #include "mds_kernels.h"
 #include "ipca_kernels.h"
+#include "nmf_kernels.h"
 #include "hmm_kernels.h"
 
 namespace {
@@ -2299,6 +2300,114 @@ int frisk_ipca_transform(frisk_ipca* h, const double* X, int64_t n, double* Y_ou
 double frisk_ipca_last_ms(const frisk_ipca* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
 
 void frisk_ipca_destroy(frisk_ipca* h) {
+    if (!h) return;
+    frisk_proj::OnDevice on(h->s.device);
+    delete h;
+}
+
+// ---- NMF (nmf_kernels.h): a handle holding X, W and H on its device between products and steps
+struct frisk_nmf {
+    frisk_nmf_impl::State s;
+};
+
+namespace {
+bool all_finite_nonneg(const double* x, int64_t count) {
+    for (int64_t e = 0; e < count; ++e) if (!std::isfinite(x[e]) || x[e] < 0.0) return false;
+    return true;
+}
+
+// H[d][f] (host) <-> Ht[f][d] (device)
+int nmf_put_H(frisk_nmf_impl::State& s, const double* H) {
+    std::vector<double> t(size_t(s.f) * size_t(s.d));
+    for (int q = 0; q < s.d; ++q)
+        for (int64_t c = 0; c < s.f; ++c) t[size_t(c) * size_t(s.d) + size_t(q)] = H[size_t(q) * size_t(s.f) + size_t(c)];
+    s.frozen = false;
+    return hipMemcpy(s.Ht, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? 0 : -2;
+}
+
+int nmf_take_H(frisk_nmf_impl::State& s, double* H) {
+    std::vector<double> t(size_t(s.f) * size_t(s.d));
+    if (hipMemcpy(t.data(), s.Ht, t.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -2;
+    for (int q = 0; q < s.d; ++q)
+        for (int64_t c = 0; c < s.f; ++c) H[size_t(q) * size_t(s.f) + size_t(c)] = t[size_t(c) * size_t(s.d) + size_t(q)];
+    return 0;
+}
+}  // namespace
+
+int frisk_nmf_create(int device, const double* X, int64_t n, int64_t f, int32_t d, frisk_nmf** out) {
+    if (!out) return FRISK_E_ARG;
+    *out = nullptr;
+    if (!X || n < 1 || f < 1 || d < 1 || d > frisk_nmf_impl::NMF_MAX_D || !all_finite_nonneg(X, n * f)) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(device);
+    if (!on.ok) return FRISK_E_HIP;
+    frisk_nmf* h = new (std::nothrow) frisk_nmf;
+    if (!h) return FRISK_E_HIP;
+    h->s.device = device;
+    h->s.n = n;
+    h->s.f = f;
+    h->s.d = d;
+    if (h->s.create(X)) {
+        delete h;
+        return FRISK_E_HIP;
+    }
+    *out = h;
+    return FRISK_OK;
+}
+
+int frisk_nmf_xq(frisk_nmf* h, const double* Q, int32_t p, double* Y_out) {
+    if (!h || !Q || !Y_out || p < 1 || p > frisk_nmf_impl::NMF_MAX_P || !all_finite(Q, h->s.f * p)) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.xq(Q, p, Y_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_nmf_xtq(frisk_nmf* h, const double* Q, int32_t p, double* Z_out) {
+    if (!h || !Q || !Z_out || p < 1 || p > frisk_nmf_impl::NMF_MAX_P || !all_finite(Q, h->s.n * p)) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.xtq(Q, p, Z_out) ? FRISK_E_HIP : FRISK_OK;
+}
+
+int frisk_nmf_set(frisk_nmf* h, const double* W, const double* H) {
+    if (!h) return FRISK_E_ARG;
+    if ((W && !all_finite(W, h->s.n * h->s.d)) || (H && !all_finite(H, int64_t(h->s.d) * h->s.f))) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    if (W && hipMemcpy(h->s.W, W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return FRISK_E_HIP;
+    if (H && nmf_put_H(h->s, H)) return FRISK_E_HIP;
+    return FRISK_OK;
+}
+
+int frisk_nmf_get(frisk_nmf* h, double* W, double* H) {
+    if (!h) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    if (W && hipMemcpy(W, h->s.W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return FRISK_E_HIP;
+    if (H && nmf_take_H(h->s, H)) return FRISK_E_HIP;
+    return FRISK_OK;
+}
+
+int frisk_nmf_step(frisk_nmf* h, double* W_inout, double* H_inout, int32_t update_H, double* violation) {
+    if (!h || !violation) return FRISK_E_ARG;
+    if (int e = frisk_nmf_set(h, W_inout, H_inout)) return e;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    if (h->s.step(update_H ? 1 : 0, violation)) return FRISK_E_HIP;
+    return frisk_nmf_get(h, W_inout, H_inout);
+}
+
+int frisk_nmf_transform_prepare(frisk_nmf* h) {
+    if (!h) return FRISK_E_ARG;
+    frisk_proj::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    return h->s.prepare() ? FRISK_E_HIP : FRISK_OK;
+}
+
+double frisk_nmf_last_ms(const frisk_nmf* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
+
+void frisk_nmf_destroy(frisk_nmf* h) {
     if (!h) return;
     frisk_proj::OnDevice on(h->s.device);
     delete h;

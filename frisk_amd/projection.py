@@ -2,8 +2,9 @@
 PCA, DBSCAN and k-means as the reference runs them through sklearn (L1597-1665), on the GPU (frisk_proj_* / frisk_dbscan /
 frisk_kmeans, csrc/proj_kernels.h), and the reference's own exact t-SNE, PY-TSNE (frisk/tsne.py, L1622-1623), on the GPU
 (frisk_tsne_*, csrc/tsne_kernels.h), sklearn's metric MDS (L1624-1627) on the GPU (frisk_mds_*, csrc/mds_kernels.h) and sklearn's
-IncrementalPCA (L1629-1631) on the GPU, batch by batch with the fit resident on the device (frisk_ipca_*, csrc/ipca_kernels.h).
-sklearn's t-SNE, NMF and spectral clustering are not built.
+IncrementalPCA (L1629-1631) on the GPU, batch by batch with the fit resident on the device (frisk_ipca_*, csrc/ipca_kernels.h),
+and sklearn's NMF (L1632-1636: the coordinate-descent solver from the nndsvda start) with X, W and H resident on the device
+(frisk_nmf_*, csrc/nmf_kernels.h).  sklearn's t-SNE and spectral clustering are not built.
 
 Reference (frisk/__init__.py): computeKmers(sym=True, pcaMode=True) L280-367 counts every valid word AND its
 reverse complement for orders pcaMin..pcaMax; scrubMirrors L797-811 keeps one key of each reverse-complement pair
@@ -13,6 +14,7 @@ The counting runs on the GPU (per-window forward counts from frisk_scan's count 
 host numpy.
 """
 import ctypes as C
+import logging
 import time
 
 import numpy as np
@@ -567,3 +569,208 @@ def incremental_pca(X, dims, batch_size=None, device=0):
         Y = fit.transform(X)
         t["transform_ms"] = 1e3 * (time.perf_counter() - t0)
         return IncrementalPCAResult(Y, fit, [hi - lo for lo, hi in batches], t)
+
+
+# ------------------------------------------------------------------------------------------------ NMF
+NMF_TOL, NMF_MAX_ITER = 1e-4, 200       # NMF(init=None, solver='cd', tol=0.0001, max_iter=200, shuffle=False) (L1633-1635)
+NMF_MAX_DIMS, NMF_MAX_P = 16, 26        # components; columns of one product (d plus the range finder's 10 oversamples)
+NMF_OVERSAMPLES, NMF_INIT_EPS = 10, 1e-6
+
+
+class NMF:
+    """An NMF problem on the GPU (frisk_nmf_*): X (n x f, non-negative) stays on the device with W (n x dims) and H (dims x f).
+    The caller drives the iterations: step() is one pass of sklearn's coordinate descent and returns its violation.  Use as a
+    context manager (or call close())."""
+
+    def __init__(self, X, dims=2, device=0):
+        X = _f64(X, 2)
+        self.n, self.f = X.shape
+        self.dims = int(dims)
+        self._h = C.c_void_p()
+        _call("frisk_nmf_create", device, _ptr(X), self.n, self.f, self.dims, C.byref(self._h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._h:
+            _ffi.lib().frisk_nmf_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def xq(self, Q):
+        """X Q for Q (f x p, p <= 26)."""
+        Q = _f64(Q, 2)
+        if Q.shape[0] != self.f:
+            raise ValueError("expected %d rows, got shape %s" % (self.f, Q.shape))
+        Y = np.empty((self.n, Q.shape[1]))
+        _call("frisk_nmf_xq", self._h, _ptr(Q), Q.shape[1], _ptr(Y))
+        return Y
+
+    def xtq(self, Q):
+        """XT Q for Q (n x p, p <= 26)."""
+        Q = _f64(Q, 2)
+        if Q.shape[0] != self.n:
+            raise ValueError("expected %d rows, got shape %s" % (self.n, Q.shape))
+        Z = np.empty((self.f, Q.shape[1]))
+        _call("frisk_nmf_xtq", self._h, _ptr(Q), Q.shape[1], _ptr(Z))
+        return Z
+
+    def set(self, W=None, H=None):
+        W, H = (None if W is None else _f64(W, 2)), (None if H is None else _f64(H, 2))
+        if W is not None and W.shape != (self.n, self.dims):
+            raise ValueError("expected W of shape %s, got %s" % ((self.n, self.dims), W.shape))
+        if H is not None and H.shape != (self.dims, self.f):
+            raise ValueError("expected H of shape %s, got %s" % ((self.dims, self.f), H.shape))
+        _call("frisk_nmf_set", self._h, None if W is None else _ptr(W), None if H is None else _ptr(H))
+
+    def get(self):
+        """(W, H): n x dims and dims x f."""
+        W, H = np.empty((self.n, self.dims)), np.empty((self.dims, self.f))
+        _call("frisk_nmf_get", self._h, _ptr(W), _ptr(H))
+        return W, H
+
+    def step(self, update_H=True):
+        """One iteration on the state on the device: the W sweep, then the H sweep when update_H.  Returns the violation."""
+        v = C.c_double()
+        _call("frisk_nmf_step", self._h, None, None, 1 if update_H else 0, C.byref(v))
+        return v.value
+
+    def transform_prepare(self):
+        """Freeze H HT and X HT of the current H for the steps of a transform."""
+        _call("frisk_nmf_transform_prepare", self._h)
+
+    def last_ms(self):
+        """Device ms of the last call: (X Q or X HT, XT Q or XT W, the whole last step)."""
+        ms = _ffi.lib().frisk_nmf_last_ms
+        return ms(self._h, 0), ms(self._h, 1), ms(self._h, 2)
+
+    def iterate(self, update_H, tol=NMF_TOL, max_iter=NMF_MAX_ITER):
+        """sklearn's _fit_coordinate_descent loop and stop rule from the state on the device: (iterations, violation ratios)."""
+        ratios, init, it = [], None, 0
+        for it in range(1, int(max_iter) + 1):
+            v = self.step(update_H)
+            if it == 1:
+                init = v
+            if init == 0:
+                break
+            ratios.append(v / init)
+            if v / init <= tol:
+                break
+        return it, ratios
+
+
+def nmf_randomized_svd(h, dims, seed=0):
+    """sklearn.utils.extmath._randomized_svd(X, dims, random_state=seed) (n_oversamples = 10, n_iter and transpose 'auto', the LU
+    power-iteration normaliser, svd_flip) with every product against X on the GPU through the handle h; the LU, QR and the small
+    SVD are scipy's on the host, on matrices at most dims + 10 wide.  Returns (U n x dims, S, V dims x f)."""
+    from scipy import linalg
+    n, f = h.n, h.f
+    n_iter = 7 if dims < 0.1 * min(n, f) else 4
+    transpose = n < f                                   # M = XT then: the range finder runs on the smaller side
+    mul, mul_t = (h.xtq, h.xq) if transpose else (h.xq, h.xtq)         # M Q and MT Q
+    Q = np.random.RandomState(seed).normal(size=(n if transpose else f, dims + NMF_OVERSAMPLES))
+    for _ in range(n_iter):
+        Q, _u = linalg.lu(mul(Q), permute_l=True, check_finite=False)
+        Q, _u = linalg.lu(mul_t(Q), permute_l=True, check_finite=False)
+    Q, _r = linalg.qr(mul(Q), mode="economic", check_finite=False)
+    B = mul_t(Q).T                                      # QT M
+    Uhat, s, Vt = linalg.svd(B, full_matrices=False, lapack_driver="gesdd")
+    U = Q @ Uhat
+    if not transpose:                                   # svd_flip(U, Vt): the largest |entry| of each column of U positive
+        signs = np.sign(U[np.argmax(np.abs(U), axis=0), np.arange(U.shape[1])])
+    else:                                               # svd_flip(U, Vt, u_based_decision=False): of each row of Vt
+        signs = np.sign(Vt[np.arange(Vt.shape[0]), np.argmax(np.abs(Vt), axis=1)])
+    U, Vt = U * signs[None, :], Vt * signs[:, None]
+    if transpose:
+        return Vt[:dims].T, s[:dims], U[:, :dims].T
+    return U[:, :dims], s[:dims], Vt[:dims]
+
+
+def nmf_nndsvda(U, S, V, avg):
+    """The NNDSVD split of sklearn's _initialize_nmf on the triplets (U, S, V), entries below 1e-6 zeroed, zeros set to avg."""
+    def norm(x):
+        return np.sqrt(np.dot(x, x))
+    W, H = np.zeros_like(U), np.zeros_like(V)
+    W[:, 0] = np.sqrt(S[0]) * np.abs(U[:, 0])
+    H[0, :] = np.sqrt(S[0]) * np.abs(V[0, :])
+    for j in range(1, U.shape[1]):
+        x, y = U[:, j], V[j, :]
+        x_p, y_p = np.maximum(x, 0), np.maximum(y, 0)
+        x_n, y_n = np.abs(np.minimum(x, 0)), np.abs(np.minimum(y, 0))
+        x_p_nrm, y_p_nrm, x_n_nrm, y_n_nrm = norm(x_p), norm(y_p), norm(x_n), norm(y_n)
+        m_p, m_n = x_p_nrm * y_p_nrm, x_n_nrm * y_n_nrm
+        if m_p > m_n:
+            u, v, sigma = x_p / x_p_nrm, y_p / y_p_nrm, m_p
+        else:
+            u, v, sigma = x_n / x_n_nrm, y_n / y_n_nrm, m_n
+        lbd = np.sqrt(S[j] * sigma)
+        W[:, j] = lbd * u
+        H[j, :] = lbd * v
+    W[W < NMF_INIT_EPS] = 0
+    H[H < NMF_INIT_EPS] = 0
+    W[W == 0] = avg
+    H[H == 0] = avg
+    return W, H
+
+
+def nmf_init(h, X, dims, seed=0):
+    """sklearn's _initialize_nmf(X, dims, init=None, random_state=seed): nndsvda when dims <= min(n, f), else 'random' (H drawn
+    first, then W).  Returns (W0, H0)."""
+    n, f = X.shape
+    if dims <= min(n, f):
+        U, S, V = nmf_randomized_svd(h, dims, seed)
+        return nmf_nndsvda(U, S, V, X.mean())
+    avg = np.sqrt(X.mean() / dims)
+    rs = np.random.RandomState(seed)
+    H = avg * rs.standard_normal(size=(dims, f))
+    W = avg * rs.standard_normal(size=(n, dims))
+    return np.abs(W), np.abs(H)
+
+
+class NMFResult:
+    """Y (n x dims, the transform of X), components (dims x f), n_iter and transform_n_iter, violation_ratios (violation /
+    violation of the first iteration, per fit iteration), W0 and H0 (the start); timings in ms (init / fit / transform)."""
+
+    def __init__(self, Y, components, n_iter, transform_n_iter, violation_ratios, W0, H0, timings):
+        self.Y, self.components, self.n_iter, self.transform_n_iter = Y, components, n_iter, transform_n_iter
+        self.violation_ratios, self.W0, self.H0, self.timings = violation_ratios, W0, H0, timings
+
+
+def nmf(X, dims, seed=0, tol=NMF_TOL, max_iter=NMF_MAX_ITER, device=0):
+    """sklearn's NMF(n_components=dims, init=None, solver='cd', tol, max_iter, shuffle=False, random_state=seed).fit(X)
+    .transform(X) (L1632-1636).  The start is sklearn's (nmf_init); every iteration of the fit and of the transform (W from zeros,
+    H fixed) is one step on the GPU, the stop rule evaluated on the host in double.  Clustering this projection is not offered by
+    the CLI yet (cli.PROJECTIONS_UNCLUSTERED)."""
+    X = _f64(X, 2)
+    n, f = X.shape
+    dims = int(dims)
+    if n < 1 or f < 1:
+        raise ValueError("NMF needs at least 1 sample and 1 feature, got shape %s" % (X.shape,))
+    if not 1 <= dims <= NMF_MAX_DIMS:
+        raise ValueError("n_components=%d must be between 1 and %d" % (dims, NMF_MAX_DIMS))
+    if not np.all(np.isfinite(X)) or X.min() < 0:
+        raise ValueError("Negative values in data passed to NMF (input X)" if np.all(np.isfinite(X)) else "X is not finite")
+    t0 = time.perf_counter()
+    with NMF(X, dims, device) as h:
+        W0, H0 = nmf_init(h, X, dims, seed)
+        t1 = time.perf_counter()
+        h.set(W0, H0)
+        n_iter, ratios = h.iterate(True, tol, max_iter)
+        if n_iter == max_iter and tol > 0:              # sklearn's ConvergenceWarning
+            logging.getLogger(__name__).warning("NMF: maximum number of iterations %d reached. Increase it to improve "
+                                                "convergence.", max_iter)
+        _W, H = h.get()
+        t2 = time.perf_counter()
+        h.set(W=np.zeros((n, dims)))
+        h.transform_prepare()
+        t_iter, _r = h.iterate(False, tol, max_iter)
+        if t_iter == max_iter and tol > 0:
+            logging.getLogger(__name__).warning("NMF transform: maximum number of iterations %d reached. Increase it to "
+                                                "improve convergence.", max_iter)
+        Y = h.get()[0]
+        t3 = time.perf_counter()
+    return NMFResult(Y, H, n_iter, t_iter, ratios, W0, H0,
+                     {"init_ms": 1e3 * (t1 - t0), "fit_ms": 1e3 * (t2 - t1), "transform_ms": 1e3 * (t3 - t2)})

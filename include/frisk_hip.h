@@ -392,6 +392,38 @@ int  frisk_ipca_transform(frisk_ipca* h, const double* X, int64_t n, double* Y_o
 double frisk_ipca_last_ms(const frisk_ipca* h, int which);
 void frisk_ipca_destroy(frisk_ipca* h);
 
+/* NMF of the reference's --runProjection NMF (sklearn.decomposition.NMF(n_components=d, init=None, solver='cd', shuffle=False):
+ * the coordinate descent of _fit_coordinate_descent / _update_cdnmf_fast with the identity permutation, no regularisation), FP64
+ * on `device`.  The handle keeps X[n][f], W[n][d] and H[d][f] on the device; the caller drives the iterations and evaluates
+ * sklearn's stop rule in double from the violation each step returns.  The two products are public because the initialisation
+ * (sklearn's randomized range finder) needs them on X as well.
+ * frisk_nmf_create: X[n][f], d components; W and H start as zeros.  FRISK_E_ARG, with nothing allocated, unless n >= 1, f >= 1,
+ *   1 <= d <= 16 and every entry of X is finite and >= 0.  Device memory: 8 n f bytes for X plus O((n + f) * 26) and the split
+ *   partials of frisk_nmf_xtq (at most 256 * f * 26 doubles).
+ * frisk_nmf_xq: Y_out[n][p] = X Q for Q[f][p];  frisk_nmf_xtq: Z_out[f][p] = XT Q for Q[n][p].  FRISK_E_ARG unless 1 <= p <= 26
+ *   and Q is finite.
+ * frisk_nmf_step: one iteration.  The W sweep against HHt = H HT and X HT: for each row s and t = 0 .. d - 1 in order,
+ *   g = -XHt[s][t] + sum_r HHt[t][r] W[s][r] (r in order), pg = W[s][t] == 0 ? min(0, g) : g, and W[s][t] = max(W[s][t] -
+ *   g / HHt[t][t], 0) where HHt[t][t] != 0; then, with update_H != 0, the same sweep of HT against WT W and XT W.  *violation =
+ *   the sum of |pg| of the W sweep plus that of the H sweep.  W_inout[n][d] and H_inout[d][f] are nullable: a given array
+ *   replaces the state on the device before the step and receives it after; with null the state stays on the device.
+ * frisk_nmf_get / frisk_nmf_set: W[n][d], H[d][f] (each nullable).  FRISK_E_ARG for a non-finite entry.
+ * frisk_nmf_transform_prepare: computes H HT and X HT of the current H once; steps with update_H == 0 reuse them until H is set
+ *   or updated (a step with update_H == 0 leaves them valid for the next one in the same way).  The results do not change.
+ * frisk_nmf_last_ms: device time in ms of the last call: which = 0 X Q (frisk_nmf_xq, or X HT within a step), 1 XT Q
+ *   (frisk_nmf_xtq, or XT W within a step), 2 the whole of the last step; else -1.
+ * Every result is bit-identical from run to run. */
+typedef struct frisk_nmf frisk_nmf;
+int  frisk_nmf_create(int device, const double* X, int64_t n, int64_t f, int32_t d, frisk_nmf** out);
+int  frisk_nmf_xq(frisk_nmf* h, const double* Q, int32_t p, double* Y_out);
+int  frisk_nmf_xtq(frisk_nmf* h, const double* Q, int32_t p, double* Z_out);
+int  frisk_nmf_step(frisk_nmf* h, double* W_inout, double* H_inout, int32_t update_H, double* violation);
+int  frisk_nmf_get(frisk_nmf* h, double* W, double* H);
+int  frisk_nmf_set(frisk_nmf* h, const double* W, const double* H);
+int  frisk_nmf_transform_prepare(frisk_nmf* h);
+double frisk_nmf_last_ms(const frisk_nmf* h, int which);
+void frisk_nmf_destroy(frisk_nmf* h);
+
 /* Page-locked host memory for result buffers: D2H copies into it are asynchronous and run at PCIe rate
  * (pageable buffers work too, at a fraction of it).  Free with frisk_host_free before frisk_destroy. */
 void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);
