@@ -37,14 +37,12 @@
 // Measurements, the adaptive choice between 4 and 8 bits, and what was tried and dropped: DESIGN.md section 3.3.
 #pragma once
 #include "scan_kernel.h"
+#include "ring_rows.h"              // FRISK8_RING_COLS and the ring's address arithmetic (no HIP there: checked on a CPU as well)
 
 #define FRISK8_ORPH_CAP 24         // orphan entries kept in LDS (two per invalid run); a window with more goes to the 16-bit form
 #define FRISK8_UNROLL1 2           // unroll factor of the stage-1 position loop
 #define FRISK8_SHORT_LANES 6        // stage 1: up to this many lanes of a wave with short words get a pass each (more: per position)
 #define FRISK8_PRIO 3               // wave priority (s_setprio) of every stage but the scoring loop
-#define FRISK8_RING_COLS 256        // ring geometry: ITS rows x 256 columns of doubles per workgroup (position p <-> row p % ITS, column p / ITS % 256):
-                                    // ITS x 256 = the most positions a window of this instantiation has - 40 KB per workgroup at 20 positions per lane
-                                    // (round 3 had 512 columns, 80 KB: the same time, twice the footprint beside 4 MB of L2 per XCD)
 #define FRISK8_RING_PAD 16          // doubles behind every workgroup's slice of the ring, touched by nobody (the idle lanes of FRISK8_DEAL's
                                     // parking waves stored there, at c34d7fb); part of the slice stride
 #define FRISK8_SLOTS 8             // misc counters per window (double-buffered by window parity)
@@ -419,18 +417,34 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             // scalar base) and the lane's column - one of two values per window, by whether the row index wrapped (round 3 computed
             // row, carry, column, mask, shift and sum on the vector unit for every position: four VALU instructions of the scoring
             // loop's ~52 per position; FRISK8_RING_SPLIT at c34d7fb)
-            const uint32_t lane_col0 = RING ? (((rb_q + uint32_t(tid)) & (FRISK8_RING_COLS - 1u)) << 3) : 0u;
-            const uint32_t lane_col1 = RING ? (((rb_q + 1u + uint32_t(tid)) & (FRISK8_RING_COLS - 1u)) << 3) : 0u;
+            // (the formulas themselves: ring_rows.h)
+            const uint32_t lane_col0 = RING ? ring_lane_col(rb_q, uint32_t(tid), 0u) : 0u;
+            const uint32_t lane_col1 = RING ? ring_lane_col(rb_q, uint32_t(tid), 1u) : 0u;
             auto ring_uni = [&](int it) __attribute__((always_inline)) -> uint32_t {        // (uniform) slice + row
-                const uint32_t rr = rb_r + uint32_t(it);
-                const uint32_t cy = rr >= uint32_t(ITS) ? 1u : 0u;
-                return slice_off + (((rr - cy * uint32_t(ITS)) * FRISK8_RING_COLS) << 3);
+                return ring_uni_general<ITS>(slice_off, rb_r, it);
             };
             auto ring_lane = [&](int it) __attribute__((always_inline)) -> uint32_t {       // the lane's column, in bytes
-                return (rb_r + uint32_t(it) >= uint32_t(ITS)) ? lane_col1 : lane_col0;
+                return ring_lane_general<ITS>(rb_r, it, lane_col0, lane_col1);
             };
             // (the sum of the two, as a call of its own: written out in fetch() it moved one kernel's register allocation)
             auto ring_mine = [&](int it) __attribute__((always_inline)) -> uint32_t { return ring_uni(it) + ring_lane(it); };
+            // ROW-ALIGNED WINDOWS.  rb_r is st % ITS, and a window that slides starts at st = j inc: at any increment that is a multiple of
+            // ITS - the usual 1000 at w = 5000 - rb_r is 0 for every window that reads the ring.  The row of position `it` is then `it`,
+            // the column lane_col0, and nothing wraps: the wrap's compare, carry and select (a dozen scalar instructions and a
+            // v_cndmask_b32 per position of the scoring loop, whose issue slots the scoring waves of a SIMD compete for) compute
+            // constants.  Such a window takes copies of the scoring loop (ROW0, one wave-uniform branch per window) in which position
+            // `it` sits at ring + slice_off + it x 2048 + lane_col0: the lane's column is the load's vector offset, and the row goes
+            // into the instruction's signed 13-bit immediate - -4096, -2048, 0, 2048 around a scalar base that moves on by four rows
+            // every four positions (kept from the optimiser, which would fold base and row into one 64-bit constant add per position).
+            // Any other window - an increment that is no multiple of ITS, a jumpback tail - takes the general copies as before; the
+            // two forms hand the ring to each other (ring_rows.h: the same offsets at rb_r = 0).  ITS = 20 only: windows of up to 2 048
+            // bases keep one form.
+            constexpr bool ROWS = RING && ITS == 20;
+            // (a pointer to global memory by its type: behind the asm that keeps it from the optimiser nothing else says so)
+            typedef const __attribute__((address_space(1))) char* GlobalBytes;
+            typedef const __attribute__((address_space(1))) double* GlobalDouble;
+            GlobalBytes row0_base = ROWS ? (GlobalBytes)(ring + slice_off + ring_row0_base_row(0) * FRISK8_RING_ROW_BYTES) : nullptr;          // (uniform) rows 0..3 at -4096 .. +2048
+            const uint32_t row0_lane = ROWS ? ring_off_row0(slice_off, rb_q, uint32_t(tid), 0) : 0u;      // the lane's offset of row 0 from the buffer's base
             const bool sliding = slide_next;
             // this lane gathers its positions' genome-side values from the table (and parks them in the ring): every lane of a
             // window counted afresh, the lanes that hold a position of the entering range in a window slid into
@@ -754,13 +768,23 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             struct Fetched { double Ig, A5; uint32_t W5, c8, w7, roff; uint4 w6; };       // (SIDE: W5 carries the side count of the code's 4-mer in its top bits)
             // (`it`: the lane's position the code belongs to, whose genome-side value waits in the ring - a 1.0 where the position
             //  starts no max-mer: the stand-in it scores has weight 0, any finite number will do;
-            //  mode: 0 counts only; 1 the scoring loop of a wave whose lanes all read the ring; 2 ... of a wave with lanes that gather)
+            //  mode: 0 counts only; 1 the scoring loop of a wave whose lanes all read the ring; 2 ... of a wave with lanes that gather;
+            //  3, 4: 1 and 2 of a row-aligned window - called for it = 0, 1, 2 ... in turn: row0_base moves along)
             auto fetch = [&](uint32_t c16, int it = 0, int mode = 0) __attribute__((always_inline)) -> Fetched {
                 Fetched f;
                 f.roff = 0;
                 if constexpr (RING) {
                     f.Ig = 1.0;
-                    if (mode) {
+                    if (mode == 3) {
+                        if (ring_row0_steps(it)) {
+                            row0_base += (ring_row0_base_row(it) - ring_row0_base_row(it - 1)) * FRISK8_RING_ROW_BYTES;
+                            asm volatile("" : "+s"(row0_base));
+                        }
+                        f.Ig = *(GlobalDouble)((row0_base + lane_col0) + ring_row0_imm(it));
+                    } else if (mode == 4) {
+                        f.roff = ring_row0_from_lane(row0_lane, it);
+                        f.Ig = *reinterpret_cast<const double*>(ring + (lane_new ? (c16 << 3) : f.roff));
+                    } else if (mode) {
                         f.roff = ring_mine(it);
                         if (mode == 1)      // every lane reads the ring: scalar base (slice + row) + the lane's column
                             f.Ig = *reinterpret_cast<const double*>((ring + ring_uni(it)) + ring_lane(it));
@@ -1191,10 +1215,14 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             //  Stores cost more than they look in this loop: loads and stores return in order on one counter, so every load behind a
             //  store waits for the store's acknowledgement - measured 1.1 ms per scan with every wave parking; storing behind the
             //  unrolled loop instead of inside it, FRISK8_PARK_LATE at c34d7fb: +-0)
-            auto score_all = [&](auto allon_c, auto orph_c, auto park_c) __attribute__((always_inline)) {
+            // (ROW0: a row-aligned window, see ROWS)
+            auto score_all = [&](auto allon_c, auto orph_c, auto park_c, auto row0_c) __attribute__((always_inline)) {
                 constexpr bool ALLON = decltype(allon_c)::value;
                 constexpr bool PARK = RING && decltype(park_c)::value;
-                constexpr int FMODE = PARK ? 2 : 1;
+                constexpr bool ROW0 = ROWS && decltype(row0_c)::value;
+                constexpr int FMODE = (PARK ? 2 : 1) + (ROW0 ? 2 : 0);
+                // (the row-aligned fetch moves its scalar base along: one call per position, in ascending order, `it` a constant)
+                static_assert(!(ROW0 && ROLLED), "the row-aligned ring access needs the unrolled scoring loop");
                 constexpr int ORPH = decltype(orph_c)::value;           // the orphan list holds <= 2 entries (one (K-1)-mer at most) / <= 4 / any number: 2 / 4 / 0
                 auto on_at = [&](int it) -> bool { return ALLON || ((fm4 >> (31 - it)) & 1u); };
                 auto code4_at = [&](int it) -> uint32_t {      // the position's max-mer, or the stand-in where it starts none
@@ -1278,16 +1306,24 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             using no = std::false_type;
             if constexpr (PLACE) {
                 if (n_list == 0) {              // (every orphan found room in the table: nearly every window)
-                    if (__all(fm4 == ALL_MINE)) { if (wave_parks) score_all(yes{}, orphX{}, yes{}); else score_all(yes{}, orphX{}, no{}); }
-                    else { if (wave_parks) score_all(no{}, orphX{}, yes{}); else score_all(no{}, orphX{}, no{}); }
-                } else if (n_list <= 4) score_all(no{}, orph4{}, yes{});
-                else score_all(no{}, orphN{}, yes{});
+                    // (the four copies without orphans, each in the general and in the row-aligned form; the two cold copies below keep
+                    //  the general form alone: two more unrolled loops for windows with orphans that found no room in the table)
+                    auto hot = [&](auto allon_c, auto park_c) __attribute__((always_inline)) {
+                        if constexpr (ROWS) {
+                            if (rb_r == 0u) { score_all(allon_c, orphX{}, park_c, yes{}); return; }
+                        }
+                        score_all(allon_c, orphX{}, park_c, no{});
+                    };
+                    if (__all(fm4 == ALL_MINE)) { if (wave_parks) hot(yes{}, yes{}); else hot(yes{}, no{}); }
+                    else { if (wave_parks) hot(no{}, yes{}); else hot(no{}, no{}); }
+                } else if (n_list <= 4) score_all(no{}, orph4{}, yes{}, no{});
+                else score_all(no{}, orphN{}, yes{}, no{});
             } else {
                 if (n_list <= 2 && n7 <= 1) {       // (every window without invalid bases)
-                    if (__all(fm4 == ALL_MINE)) score_all(yes{}, orph2{}, yes{});
-                    else score_all(no{}, orph2{}, yes{});
-                } else if (n_list <= 4) score_all(no{}, orph4{}, yes{});
-                else score_all(no{}, orphN{}, yes{});
+                    if (__all(fm4 == ALL_MINE)) score_all(yes{}, orph2{}, yes{}, no{});
+                    else score_all(no{}, orph2{}, yes{}, no{});
+                } else if (n_list <= 4) score_all(no{}, orph4{}, yes{}, no{});
+                else score_all(no{}, orphN{}, yes{}, no{});
             }
 
             // workgroup totals in a fixed order: DPP butterfly per wave, then the NW partials in wave order

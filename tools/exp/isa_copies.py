@@ -1,13 +1,21 @@
 #!/usr/bin/env python3
 """(CPU) device assembly of the library; for the K = 8 / 4-bit bulk kernels (plain and SIDE) the copies of the scoring loop:
-instructions per position and scratch accesses in each.  Usage: python tools/exp/isa_copies.py [extra -D flags]"""
+instructions per position and scratch accesses in each.  Usage: python tools/exp/isa_copies.py [extra -D flags]
+(--asm FILE: read that device assembly instead of compiling.)  Behind the runs of positions, the straight-line copies one by one: every
+basic block that scores at least half a lane's positions (the unrolled copies of the K = 8 scoring loop are one block each), with its
+instruction counts by kind for the whole block."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.makedirs(os.path.join(ROOT, "build/isa"), exist_ok=True)
 asm = os.path.join(ROOT, "build/isa/abi.s")
-subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-pass-failed"] + sys.argv[1:] +
-               ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "frisk_amd/csrc"), "--cuda-device-only", "-S", "-o", asm,
-                os.path.join(ROOT, "frisk_amd/csrc/frisk_abi.hip")], check=True, stderr=subprocess.DEVNULL)
+flags = sys.argv[1:]
+given = flags.index("--asm") if "--asm" in flags else -1
+if given >= 0:
+    asm, flags = flags[given + 1], flags[:given] + flags[given + 2:]
+else:
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-pass-failed"] + flags +
+                   ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "frisk_amd/csrc"), "--cuda-device-only", "-S", "-o", asm,
+                    os.path.join(ROOT, "frisk_amd/csrc/frisk_abi.hip")], check=True, stderr=subprocess.DEVNULL)
 L = open(asm).read().split('\n')
 for tag, kern in (('plain', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb0EEv10ScanParams'),
                   ('side', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb1EEv10ScanParams')):
@@ -31,3 +39,13 @@ for tag, kern in (('plain', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi
         c = lambda p: sum(1 for l in K[lo:hi] if re.match(r'\s+' + p, l))
         print(tag, 'copy at %5d..%5d: %2d positions; per position: valu %.1f salu %.1f lds %.1f vmem %.1f; scratch ops %d, labels %d' % (
             lo, hi, len(run), c('v_') / n, c('s_') / n, c('ds_') / n, c('(global|buffer|flat)_') / n, c('scratch_'), sum(1 for l in labels if lo < l < hi)))
+    # the straight-line copies: basic blocks (label to label / branch) of the scoring stage with >= 10 positions
+    cuts = sorted(set([seg[0]] + labels + [i for i in range(*seg) if re.match(r'\s+s_(c?branch|setpc)', K[i])] + [seg[1]]))
+    for lo, hi in zip(cuts, cuts[1:]):
+        B = K[lo:hi]
+        c = lambda p: sum(1 for l in B if re.match(r'\s+' + p, l))
+        npos = c('v_frexp_mant_f64')
+        if npos < 10: continue
+        print(tag, 'block at %5d..%5d: %2d positions; in all: valu %d (f64 %d, cndmask %d) salu %d (s_nop %d) lds %d vmem %d (stores %d); scratch ops %d, v_readlane/writelane %d' % (
+            lo, hi, npos, c('v_'), c(r'v_\w+_f64'), c('v_cndmask'), c('s_'), c('s_nop'), c('ds_'), c('(global|buffer|flat)_'), c('(global|buffer|flat)_store'),
+            c('scratch_'), c('v_(read|write)lane')))
