@@ -1,5 +1,6 @@
-// frisk_abi.hip - host side of libfrisk_hip.so: the C ABI declared in include/frisk_hip.h.
-// gfx950 (MI355X) only.  Build: see __graft_entry__.build().
+// frisk_abi.hip - host side of libfrisk_hip.so: the context, sequences, profile and scan of the C ABI declared in include/frisk_hip.h.
+// The scan kernels are launched through scan_launch.h (scan_launch.hip, scan8_launch.hip, scan8_launch4.hip); the entry points that
+// take no context (HMM, projection, clustering) are in frisk_analysis.hip.  gfx950 (MI355X) only.  Build: see __graft_entry__.build_hip().
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 #include <dlfcn.h>
@@ -19,23 +20,15 @@
 #include "frisk_hip.h"
 #include "frisk_device.h"
 #include "profile_kernels.h"
-#include "scan_kernel.h"
-#include "scan8_kernel.h"
-#include "scan_big_kernel.h"
+#include "scan_launch.h"
 #include "scan_schedule.h"
+#include "ring_rows.h"              // FRISK8_RING_COLS
 #include "synth_kernel.h"
 #include "table_text.h"
 #include "fasta_index.h"
 #include "fasta_reader.h"
 #include "fasta_pack2.h"
 #include "seq_pack2.h"
-#include "hmm_host.h"
-#include "proj_kernels.h"
-#include "tsne_kernels.h"
-#include "mds_kernels.h"
-#include "ipca_kernels.h"
-#include "nmf_kernels.h"
-#include "hmm_kernels.h"
 
 namespace {
 
@@ -349,72 +342,6 @@ void plan_scaffold(int64_t size, int32_t w, int32_t inc, bool all, int64_t& ncan
         kind = 0;
         ncand = (size - inc + 1 > 0) ? (size - inc) / inc + 1 : 0;            // len(range(0, size-inc+1, inc)), L228
     }
-}
-
-template <int NT, bool K8, int ITS, bool DEBUG>
-hipError_t launch_scan(const ScanParams& P, int grid, size_t lds, hipStream_t st) {
-    auto kern = scan_kernel<NT, K8, ITS, DEBUG>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       int(lds));
-    if (e != hipSuccess) return e;
-    kern<<<grid, NT, lds, st>>>(P);
-    return hipGetLastError();
-}
-
-template <int KMAX, int NT, int ITS, int BITS, int LOGN, int WPS, bool DEBUG, int ROLE = 0, bool SIDE = false>
-hipError_t launch_scan8(const ScanParams& P, int num_cu, int64_t work_items, hipStream_t st) {
-    constexpr int wg_per_cu = WPS * 256 / NT;
-    static_assert(Lds8<KMAX, BITS, LOGN, NT, SIDE>::granules * 1280 * wg_per_cu <= 160 * 1024, "the workgroups meant to share a CU must fit its LDS (allocated in pieces of 1280 bytes)");
-    int grid = int(std::max<int64_t>(1, std::min<int64_t>(work_items, int64_t(num_cu) * wg_per_cu)));
-    if (grid >= 8) grid &= ~7;
-    scan8_kernel<KMAX, NT, ITS, BITS, LOGN, WPS, DEBUG, ROLE, SIDE><<<grid, NT, 0, st>>>(P);      // LDS is static (Lds8)
-    return hipGetLastError();
-}
-
-// one launch of the narrow-counter K = 8 kernel: counter width, window class (<= 2048 / <= 5120 bases), debug dump
-// (side: 4-bit counters with the side table for the period-4 max-mers)
-hipError_t launch_narrow(int kmax, int bits, bool small_w, bool debug, const ScanParams& P, int num_cu, int64_t work_items, hipStream_t st,
-                         bool sample = false, bool side = false) {
-    const bool slides = P.slide_pp > 0 && P.in_list == nullptr;        // (else: the instantiation without the ring, ROLE bit 1)
-    if (sample) {           // the sample of the adaptive width: 4-bit counters, its own name in kernel statistics; it runs the
-                            // side-table form and counts what the plain form would have handed on as well
-        if (small_w) return slides ? launch_scan8<8, 256, 8, 4, 64, 3, false, 1, true>(P, num_cu, work_items, st)
-                                   : launch_scan8<8, 256, 8, 4, 64, 3, false, 3, true>(P, num_cu, work_items, st);
-        return slides ? launch_scan8<8, 256, 20, 4, 64, 3, false, 1, true>(P, num_cu, work_items, st)
-                      : launch_scan8<8, 256, 20, 4, 64, 3, false, 3, true>(P, num_cu, work_items, st);
-    }
-    if (side && P.in_list == nullptr && bits == 4 && kmax == 8 && !debug) {
-        if (small_w) return slides ? launch_scan8<8, 256, 8, 4, 64, 3, false, 0, true>(P, num_cu, work_items, st)
-                                   : launch_scan8<8, 256, 8, 4, 64, 3, false, 2, true>(P, num_cu, work_items, st);
-        return slides ? launch_scan8<8, 256, 20, 4, 64, 3, false, 0, true>(P, num_cu, work_items, st)
-                      : launch_scan8<8, 256, 20, 4, 64, 3, false, 2, true>(P, num_cu, work_items, st);
-    }
-#define FRISK_L7(K_, ITS_, DBG_) return launch_scan8<K_, 256, ITS_, 8, 64, FRISK_K7_WPS, DBG_>(P, num_cu, work_items, st)
-    if (kmax == 7) {        // K = 6, 7: the 8-bit table is 16 / 4 KiB - registers, not LDS, bound the workgroups per CU
-        if (debug) { if (small_w) FRISK_L7(7, 8, true); else FRISK_L7(7, 20, true); }
-        if (small_w) FRISK_L7(7, 8, false);
-        FRISK_L7(7, 20, false);
-    }
-    if (kmax == 6) {
-        if (debug) { if (small_w) FRISK_L7(6, 8, true); else FRISK_L7(6, 20, true); }
-        if (small_w) FRISK_L7(6, 8, false);
-        FRISK_L7(6, 20, false);
-    }
-#undef FRISK_L7
-#define FRISK_L8(ITS_, BITS_, WPS_, DBG_) return launch_scan8<8, 256, ITS_, BITS_, 64, WPS_, DBG_>(P, num_cu, work_items, st)
-    if (bits == 4) {
-        if (debug) { if (small_w) FRISK_L8(8, 4, 3, true); else FRISK_L8(20, 4, 3, true); }
-        if (!slides) {
-            if (small_w) return launch_scan8<8, 256, 8, 4, 64, 3, false, 2>(P, num_cu, work_items, st);
-            return launch_scan8<8, 256, 20, 4, 64, 3, false, 2>(P, num_cu, work_items, st);
-        }
-        if (small_w) FRISK_L8(8, 4, 3, false);
-        FRISK_L8(20, 4, 3, false);
-    }
-    if (debug) { if (small_w) FRISK_L8(8, 8, 2, true); else FRISK_L8(20, 8, 2, true); }
-    if (small_w) FRISK_L8(8, 8, 2, false);
-    FRISK_L8(20, 8, 2, false);
-#undef FRISK_L8
 }
 
 // Tuning knobs are read from the environment only in experiment builds (-DFRISK_TUNE); the product library has none.
@@ -1602,24 +1529,7 @@ struct ScanRun {
 
     // the 16-bit form (scan_kernel.h) over the candidates that PP names, by window class
     hipError_t launch16(const ScanParams& PP, int g, hipStream_t st) const {
-        const int its = sched.its;
-        hipError_t le;
-#define FRISK_LAUNCH16(NT_, K8_, ITS_, DBG_) le = launch_scan<NT_, K8_, ITS_, DBG_>(PP, g, sched.lds_total, st)
-        if (c->kmax == 8) {
-            if (shape.debug) { if (its) FRISK_LAUNCH16(512, true, 16, true); else FRISK_LAUNCH16(1024, true, 0, true); }
-            else if (its == 4) FRISK_LAUNCH16(512, true, 4, false);
-            else if (its == 10) FRISK_LAUNCH16(512, true, 10, false);
-            else if (its == 16) FRISK_LAUNCH16(512, true, 16, false);
-            else FRISK_LAUNCH16(1024, true, 0, false);
-        } else {
-            if (shape.debug) { if (its) FRISK_LAUNCH16(512, false, 16, true); else FRISK_LAUNCH16(1024, false, 0, true); }
-            else if (its == 4) FRISK_LAUNCH16(512, false, 4, false);
-            else if (its == 10) FRISK_LAUNCH16(512, false, 10, false);
-            else if (its == 16) FRISK_LAUNCH16(512, false, 16, false);
-            else FRISK_LAUNCH16(1024, false, 0, false);
-        }
-#undef FRISK_LAUNCH16
-        return le;
+        return launch_scan16(PP, c->kmax, sched.its, shape.debug, sched.lds_total, g, st);
     }
 
     // rows [r0, r1) to the caller's buffers
@@ -1651,19 +1561,15 @@ struct ScanRun {
             const int64_t stride = (c->nprof + 3) / 4 * 4;
             HIPC(c, c->d_big.reserve(size_t(sched.big_grid) * size_t(stride)));
             HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(sched.big_grid) * size_t(stride) * 4, c->stream));
-            if (shape.debug) scan_big_kernel<true><<<sched.big_grid, FRISK_BIG_NT, 0, c->stream>>>(P, c->d_big.p, stride);
-            else scan_big_kernel<false><<<sched.big_grid, FRISK_BIG_NT, 0, c->stream>>>(P, c->d_big.p, stride);
-            e = hipGetLastError();
+            e = launch_scan_big(P, shape.debug, sched.big_grid, c->d_big.p, stride, c->stream);
         } else if (sched.path == SCAN_PATH_TWO_WG) {
-            if (sched.its == 8) e = launch_scan<256, false, 8, false>(P, sched.grid, sched.lds_total, c->stream);
-            else e = launch_scan<256, false, 20, false>(P, sched.grid, sched.lds_total, c->stream);
+            e = launch_scan_two_wg(P, sched.its, sched.lds_total, sched.grid, c->stream);
         } else {
             e = launch16(P, sched.grid, c->stream);
         }
         HIPC(c, e);
         if (sched.path != SCAN_PATH_BIG) {      // the LDS kernels leave the rows' scalar tail to one thread per row
-            finish_rows_kernel<<<grid_for(n, 256, 1 << 20), 256, 0, c->stream>>>(n, P.status, P.kld, P.gc, P.sw, P.sg);
-            HIPC(c, hipGetLastError());
+            HIPC(c, launch_finish_rows(grid_for(n, 256, 1 << 20), c->stream, n, P.status, P.kld, P.gc, P.sw, P.sg));
         }
         HIPC(c, hipEventRecord(c->ev1, c->stream));
         return copy_rows(0, n, c->stream);
@@ -1686,9 +1592,8 @@ struct ScanRun {
         // 9.98 ms, 8-bit bulk 8.51 / 8.57 / 8.71 / 8.78 ms - tools/exp/width_sweep.sh); the side table pays when the plain form
         // would hand on more than FRISK_SIDE_SHARE of the windows that are scored (it costs a scored window 1.0 ns - ten
         // instructions per position: 6.97 against 6.59 ms per scan -, a window handed on 18 ns: tools/exp/side_rate.py)
-        scan8_decide_kernel<<<1, 1, 0, c->stream>>>(c->d_ovf_count.p, static_cast<unsigned int>(nsample * chunk8), double(FRISK_SIDE_SHARE),
-                                                    sched.narrow8 && !shape.debug ? 1 : 0, c->d_verdict.p);
-        HIPC(c, hipGetLastError());
+        HIPC(c, launch_scan8_decide(c->d_ovf_count.p, static_cast<unsigned int>(nsample * chunk8), sched.narrow8 && !shape.debug ? 1 : 0,
+                                    c->d_verdict.p, c->stream));
         ScanParams H = P;
         H.in_list = c->d_ovf_list.p; H.in_count = c->d_ovf_count.p;
         H.out_list = c->d_ovf_list2.p; H.out_count = c->d_ovf_count.p + 1;
@@ -1756,8 +1661,7 @@ struct ScanRun {
             HIPC(c, hipEventRecord(c->ev_fork, st));
             HIPC(c, hipStreamWaitEvent(c->tail_stream, c->ev_fork, 0));
         }
-        finish_rows_kernel<<<grid_for(m, 256, 1 << 20), 256, 0, st>>>(m, R.status, R.kld, R.gc, R.sw, R.sg);
-        HIPC(c, hipGetLastError());
+        HIPC(c, launch_finish_rows(grid_for(m, 256, 1 << 20), st, m, R.status, R.kld, R.gc, R.sw, R.sg));
         return FRISK_OK;
     }
 
@@ -1945,472 +1849,6 @@ char* frisk_format_rows(int64_t n, const char* const* names, const int32_t* seq_
     return frisk_text::format_all(c, out_len);
 }
 void frisk_free(void* p) { std::free(p); }
-
-// ---- host-native 2-state Gaussian HMM (hmm_host.h): the model frisk_amd/hmm.py documents, for millions of windows ----------
-namespace {
-frisk_hmm::Model model_of(const double* means, const double* covars, const double* startprob, const double* transmat) {
-    frisk_hmm::Model m;
-    for (int i = 0; i < 2; ++i) { m.means[i] = means[i]; m.covars[i] = covars[i]; m.startprob[i] = startprob[i]; }
-    for (int i = 0; i < 4; ++i) m.transmat[i] = transmat[i];
-    return m;
-}
-int fit_out(const frisk_hmm::Fit& F, double* means, double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
-    for (int i = 0; i < 2; ++i) { means[i] = F.m.means[i]; covars[i] = F.m.covars[i]; startprob[i] = F.m.startprob[i]; }
-    for (int i = 0; i < 4; ++i) transmat[i] = F.m.transmat[i];
-    if (loglik) *loglik = F.loglik;
-    if (iters) *iters = F.iters;
-    return FRISK_OK;
-}
-}  // namespace
-
-int frisk_hmm_fit(const double* x, int64_t n, int32_t n_iter, double tol, double min_covar, double covars_prior, double* means,
-                  double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
-    if (!x || n < 1 || n_iter < 0 || !means || !covars || !startprob || !transmat) return FRISK_E_ARG;
-    for (int64_t t = 0; t < n; ++t) if (!std::isfinite(x[t])) return FRISK_E_ARG;
-    const frisk_hmm::Fit F = frisk_hmm::fit(x, n, n_iter, tol, min_covar, covars_prior);
-    return fit_out(F, means, covars, startprob, transmat, loglik, iters);
-}
-
-int frisk_hmm_viterbi(const double* x, const int64_t* seg_off, int32_t n_seg, const double* means, const double* covars,
-                      const double* startprob, const double* transmat, int8_t* states) {
-    if (n_seg < 0 || !seg_off || !means || !covars || !startprob || !transmat) return FRISK_E_ARG;
-    for (int32_t s = 0; s < n_seg; ++s) if (seg_off[s + 1] < seg_off[s]) return FRISK_E_ARG;
-    if (n_seg == 0 || seg_off[n_seg] == seg_off[0]) return FRISK_OK;
-    if (!x || !states) return FRISK_E_ARG;
-    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
-    frisk_hmm::viterbi_segments(x, seg_off, n_seg, m, states);
-    return FRISK_OK;
-}
-
-namespace {
-// x and the model of one E step: finite, variances > 0, probabilities in [0, 1]
-bool estep_args_ok(const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
-                   const double* transmat, const double* stats_out) {
-    if (!x || n < 1 || !means || !covars || !startprob || !transmat || !stats_out) return false;
-    for (int i = 0; i < 2; ++i) {
-        if (!std::isfinite(means[i]) || !std::isfinite(covars[i]) || !(covars[i] > 0.0)) return false;
-        if (!(startprob[i] >= 0.0 && startprob[i] <= 1.0)) return false;
-    }
-    for (int i = 0; i < 4; ++i) if (!(transmat[i] >= 0.0 && transmat[i] <= 1.0)) return false;
-    for (int64_t t = 0; t < n; ++t) if (!std::isfinite(x[t])) return false;
-    return true;
-}
-}  // namespace
-
-int frisk_hmm_estep(const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
-                    const double* transmat, double* post_out, double* stats_out) {
-    if (!estep_args_ok(x, n, means, covars, startprob, transmat, stats_out)) return FRISK_E_ARG;
-    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
-    frisk_hmm::Work w(n);
-    stats_out[8] = frisk_hmm::e_step(x, n, m, w, stats_out);
-    if (post_out) std::copy(w.A.begin(), w.A.end(), post_out);
-    return FRISK_OK;
-}
-
 int64_t frisk_last_scan_stat(const frisk_ctx* c, int which) { return (c && which >= 0 && which < 5) ? c->scan_stat[which] : -1; }
-
-// ---- projection and clustering (proj_kernels.h): context-free, host arrays in and out, device memory freed on every return
-namespace {
-bool all_finite(const double* x, int64_t count) {
-    for (int64_t e = 0; e < count; ++e) if (!std::isfinite(x[e])) return false;
-    return true;
-}
-}  // namespace
-
-int frisk_proj_cov(int device, const double* X, int64_t n, int64_t f, double* mean_out, double* cov_out) {
-    if (!X || !mean_out || !cov_out || n < 1 || f < 1 || !all_finite(X, n * f)) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    return frisk_proj::cov(X, n, f, mean_out, cov_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_proj_transform(int device, const double* X, const double* mean, const double* V, int64_t n, int64_t f, int32_t d,
-                         double* Y_out) {
-    if (!X || !mean || !V || !Y_out || n < 1 || f < 1 || d < 1 || d > f || !all_finite(X, n * f) || !all_finite(mean, f) ||
-        !all_finite(V, f * d))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    return frisk_proj::transform(X, mean, V, n, f, d, Y_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_dbscan(int device, const double* Y, int64_t n, int32_t d, double eps, int32_t min_samples, int32_t* labels_out) {
-    if (!Y || !labels_out || n < 1 || n > INT32_MAX || d < 1 || d > frisk_proj::MAX_DIMS || !(eps > 0.0) || !std::isfinite(eps) ||
-        min_samples < 1 || !all_finite(Y, n * d))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    return frisk_proj::dbscan(Y, n, d, eps, min_samples, labels_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_kmeans(int device, const double* Y, int64_t n, int32_t d, int32_t k, const double* init_centers, int32_t max_iter,
-                 double tol, int32_t* labels_out, double* centers_out, double* inertia_out, int32_t* n_iter_out) {
-    if (!Y || !init_centers || !labels_out || !centers_out || n < 1 || n > INT32_MAX || d < 1 || d > frisk_proj::MAX_DIMS ||
-        k < 1 || k > n || max_iter < 1 || !(tol >= 0.0) || !all_finite(Y, n * d) || !all_finite(init_centers, int64_t(k) * d))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    return frisk_proj::kmeans(Y, n, d, k, init_centers, max_iter, tol, labels_out, centers_out, inertia_out, n_iter_out)
-               ? FRISK_E_HIP : FRISK_OK;
-}
-
-// ---- the same HMM on the device (hmm_kernels.h): context-free, host arrays in and out, device memory freed on every return
-int frisk_hmm_fit_gpu(int device, const double* x, int64_t n, int32_t n_iter, double tol, double min_covar, double covars_prior,
-                      double* means, double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
-    if (!x || n < 1 || n > (int64_t(1) << 40) || n_iter < 0 || !means || !covars || !startprob || !transmat || !all_finite(x, n))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    frisk_hmm::Fit F;
-    if (frisk_hmm_gpu::fit(x, n, n_iter, tol, min_covar, covars_prior, F)) return FRISK_E_HIP;
-    return fit_out(F, means, covars, startprob, transmat, loglik, iters);
-}
-
-int frisk_hmm_estep_gpu(int device, const double* x, int64_t n, const double* means, const double* covars, const double* startprob,
-                        const double* transmat, double* post_out, double* stats_out) {
-    if (!estep_args_ok(x, n, means, covars, startprob, transmat, stats_out) || n > (int64_t(1) << 40)) return FRISK_E_ARG;
-    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    return frisk_hmm_gpu::e_step_only(x, n, m, post_out, stats_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_hmm_viterbi_gpu(int device, const double* x, const int64_t* seg_off, int32_t n_seg, const double* means,
-                          const double* covars, const double* startprob, const double* transmat, int8_t* states) {
-    if (n_seg < 0 || !seg_off || !means || !covars || !startprob || !transmat) return FRISK_E_ARG;
-    for (int32_t s = 0; s < n_seg; ++s) if (seg_off[s + 1] < seg_off[s]) return FRISK_E_ARG;
-    if (n_seg == 0 || seg_off[n_seg] == seg_off[0]) return FRISK_OK;
-    if (!x || !states || seg_off[n_seg] - seg_off[0] > (int64_t(1) << 40)) return FRISK_E_ARG;
-    if (!all_finite(x + seg_off[0], seg_off[n_seg] - seg_off[0])) return FRISK_E_ARG;
-    const frisk_hmm::Model m = model_of(means, covars, startprob, transmat);
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    return frisk_hmm_gpu::viterbi_segments(x, seg_off, n_seg, m, states) ? FRISK_E_HIP : FRISK_OK;
-}
-
-// ---- exact t-SNE (tsne_kernels.h): a handle whose state stays on its device between calls
-struct frisk_tsne {
-    frisk_tsne_impl::State s;
-};
-
-int frisk_tsne_create(int device, const double* X, int64_t n, int32_t f, double perplexity, int32_t dims, const double* Y0,
-                      frisk_tsne** out) {
-    if (!out) return FRISK_E_ARG;
-    *out = nullptr;
-    if (!X || !Y0 || n < 2 || n > frisk_tsne_impl::MAX_N || f < 1 || f > frisk_tsne_impl::MAX_F || dims < 1 ||
-        dims > frisk_tsne_impl::MAX_D || !(perplexity > 0.0) || !std::isfinite(perplexity) || !all_finite(X, n * f) ||
-        !all_finite(Y0, n * dims))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    frisk_tsne* h = new (std::nothrow) frisk_tsne;
-    if (!h) return FRISK_E_HIP;
-    h->s.device = device;
-    h->s.n = n;
-    h->s.f = f;
-    h->s.d = dims;
-    h->s.perplexity = perplexity;
-    if (h->s.alloc(X, Y0)) {
-        delete h;
-        return FRISK_E_HIP;
-    }
-    *out = h;
-    return FRISK_OK;
-}
-
-int frisk_tsne_affinities(frisk_tsne* h, double* beta_out, int32_t* tries_out, double* q_out) {
-    if (!h) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    const int64_t n = h->s.n;
-    if (!h->s.have_p) {
-        const int e = h->s.affinities();
-        if (e) return e == -1 ? FRISK_E_ARG : FRISK_E_HIP;
-    }
-    if (beta_out && hipMemcpy(beta_out, h->s.beta, size_t(n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    if (tries_out && hipMemcpy(tries_out, h->s.tries, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return FRISK_E_HIP;
-    if (q_out && hipMemcpy(q_out, h->s.P, size_t(n) * size_t(n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return FRISK_E_HIP;
-    return FRISK_OK;
-}
-
-int frisk_tsne_run(frisk_tsne* h, int32_t iter_begin, int32_t iter_end, double* cost_out) {
-    if (!h || iter_begin < 0 || iter_end < iter_begin || iter_end > frisk_tsne_impl::MAX_ITER) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    if (!h->s.have_p) {
-        const int e = h->s.affinities();
-        if (e) return e == -1 ? FRISK_E_ARG : FRISK_E_HIP;
-    }
-    return h->s.run(iter_begin, iter_end, cost_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_tsne_get(frisk_tsne* h, double* Y, double* iY, double* gains) {
-    if (!h) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    const size_t bytes = size_t(h->s.n) * size_t(h->s.d) * sizeof(double);
-    if (Y && hipMemcpy(Y, h->s.Y, bytes, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    if (iY && hipMemcpy(iY, h->s.iY, bytes, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    if (gains && hipMemcpy(gains, h->s.gains, bytes, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    return FRISK_OK;
-}
-
-int frisk_tsne_set(frisk_tsne* h, const double* Y, const double* iY, const double* gains) {
-    if (!h) return FRISK_E_ARG;
-    const int64_t nd = h->s.n * h->s.d;
-    if ((Y && !all_finite(Y, nd)) || (iY && !all_finite(iY, nd)) || (gains && !all_finite(gains, nd))) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    const size_t bytes = size_t(nd) * sizeof(double);
-    if (Y && hipMemcpy(h->s.Y, Y, bytes, hipMemcpyHostToDevice) != hipSuccess) return FRISK_E_HIP;
-    if (iY && hipMemcpy(h->s.iY, iY, bytes, hipMemcpyHostToDevice) != hipSuccess) return FRISK_E_HIP;
-    if (gains && hipMemcpy(h->s.gains, gains, bytes, hipMemcpyHostToDevice) != hipSuccess) return FRISK_E_HIP;
-    return FRISK_OK;
-}
-
-void frisk_tsne_destroy(frisk_tsne* h) {
-    if (!h) return;
-    frisk_proj::OnDevice on(h->s.device);
-    delete h;
-}
-
-// ---- metric MDS (mds_kernels.h): a handle holding the dissimilarities on its device between runs
-struct frisk_mds {
-    frisk_mds_impl::State s;
-};
-
-int frisk_mds_create(int device, const double* X, int64_t n, int64_t f, int32_t dims, frisk_mds** out) {
-    if (!out) return FRISK_E_ARG;
-    *out = nullptr;
-    if (!X || n < 2 || n > frisk_mds_impl::MAX_N || f < 1 || dims < 1 || dims > frisk_mds_impl::MAX_D || !all_finite(X, n * f))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    frisk_mds* h = new (std::nothrow) frisk_mds;
-    if (!h) return FRISK_E_HIP;
-    h->s.device = device;
-    h->s.n = n;
-    h->s.f = f;
-    h->s.d = dims;
-    if (h->s.create(X)) {
-        delete h;
-        return FRISK_E_HIP;
-    }
-    *out = h;
-    return FRISK_OK;
-}
-
-int frisk_mds_dissimilarities(frisk_mds* h, double* D_out) {
-    if (!h || !D_out) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    const size_t bytes = size_t(h->s.n) * size_t(h->s.n) * sizeof(double);
-    return hipMemcpy(D_out, h->s.D, bytes, hipMemcpyDeviceToHost) == hipSuccess ? FRISK_OK : FRISK_E_HIP;
-}
-
-int frisk_mds_run(frisk_mds* h, const double* Y0, int32_t max_iter, double eps, double* Y_out, double* stress_out,
-                  int32_t* n_iter_out, double* stress_trace_out) {
-    if (!h || !Y0 || !Y_out || max_iter < 1 || !(eps >= 0.0) || !std::isfinite(eps) || !all_finite(Y0, h->s.n * h->s.d))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.run(Y0, max_iter, eps, Y_out, stress_out, n_iter_out, stress_trace_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-void frisk_mds_destroy(frisk_mds* h) {
-    if (!h) return;
-    frisk_proj::OnDevice on(h->s.device);
-    delete h;
-}
-
-// ---- incremental PCA (ipca_kernels.h): a handle holding the fit (rows seen, mean, variance, S, V) on its device between batches
-struct frisk_ipca {
-    frisk_ipca_impl::State s;
-};
-
-int frisk_ipca_create(int device, int64_t f, int32_t d, frisk_ipca** out) {
-    if (!out) return FRISK_E_ARG;
-    *out = nullptr;
-    if (f < 1 || d < 1 || d > f) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    frisk_ipca* h = new (std::nothrow) frisk_ipca;
-    if (!h) return FRISK_E_HIP;
-    h->s.device = device;
-    h->s.f = f;
-    h->s.d = d;
-    if (h->s.create()) {
-        delete h;
-        return FRISK_E_HIP;
-    }
-    *out = h;
-    return FRISK_OK;
-}
-
-int frisk_ipca_gram(frisk_ipca* h, const double* X, int64_t b, double* G_out) {
-    if (!h || !X || !G_out || b < 1 || (h->s.seen == 0 && b < h->s.d) || !all_finite(X, b * h->s.f)) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.gram(X, b, G_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_ipca_commit(frisk_ipca* h, const double* S, const double* Vt) {
-    if (!h || !S || !Vt || !all_finite(S, h->s.d) || !all_finite(Vt, int64_t(h->s.d) * h->s.f)) return FRISK_E_ARG;
-    if (!h->s.pending_b) return FRISK_E_STATE;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.commit(S, Vt) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_ipca_get(frisk_ipca* h, int64_t* n_seen, double* mean, double* var, double* S, double* Vt) {
-    if (!h) return FRISK_E_ARG;
-    if (n_seen) *n_seen = h->s.seen;
-    if (!mean && !var && !S && !Vt) return FRISK_OK;
-    if (!h->s.fitted) return FRISK_E_STATE;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    const size_t fb = size_t(h->s.f) * sizeof(double), db = size_t(h->s.d) * sizeof(double);
-    if (mean && hipMemcpy(mean, h->s.mean, fb, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    if (var && hipMemcpy(var, h->s.var, fb, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    if (S && hipMemcpy(S, h->s.S, db, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    if (Vt && hipMemcpy(Vt, h->s.Vt, size_t(h->s.d) * fb, hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    return FRISK_OK;
-}
-
-int frisk_ipca_set(frisk_ipca* h, int64_t n_seen, const double* mean, const double* var, const double* S, const double* Vt) {
-    if (!h || n_seen < 0) return FRISK_E_ARG;
-    if (n_seen > 0 && (!mean || !var || !S || !Vt || !all_finite(mean, h->s.f) || !all_finite(var, h->s.f) ||
-                       !all_finite(S, h->s.d) || !all_finite(Vt, int64_t(h->s.d) * h->s.f)))
-        return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.set(n_seen, mean, var, S, Vt) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_ipca_transform(frisk_ipca* h, const double* X, int64_t n, double* Y_out) {
-    if (!h || !X || !Y_out || n < 1 || !all_finite(X, n * h->s.f)) return FRISK_E_ARG;
-    if (!h->s.fitted) return FRISK_E_STATE;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.transform(X, n, Y_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-double frisk_ipca_last_ms(const frisk_ipca* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
-
-void frisk_ipca_destroy(frisk_ipca* h) {
-    if (!h) return;
-    frisk_proj::OnDevice on(h->s.device);
-    delete h;
-}
-
-// ---- NMF (nmf_kernels.h): a handle holding X, W and H on its device between products and steps
-struct frisk_nmf {
-    frisk_nmf_impl::State s;
-};
-
-namespace {
-bool all_finite_nonneg(const double* x, int64_t count) {
-    for (int64_t e = 0; e < count; ++e) if (!std::isfinite(x[e]) || x[e] < 0.0) return false;
-    return true;
-}
-
-// H[d][f] (host) <-> Ht[f][d] (device)
-int nmf_put_H(frisk_nmf_impl::State& s, const double* H) {
-    std::vector<double> t(size_t(s.f) * size_t(s.d));
-    for (int q = 0; q < s.d; ++q)
-        for (int64_t c = 0; c < s.f; ++c) t[size_t(c) * size_t(s.d) + size_t(q)] = H[size_t(q) * size_t(s.f) + size_t(c)];
-    s.frozen = false;
-    return hipMemcpy(s.Ht, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? 0 : -2;
-}
-
-int nmf_take_H(frisk_nmf_impl::State& s, double* H) {
-    std::vector<double> t(size_t(s.f) * size_t(s.d));
-    if (hipMemcpy(t.data(), s.Ht, t.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -2;
-    for (int q = 0; q < s.d; ++q)
-        for (int64_t c = 0; c < s.f; ++c) H[size_t(q) * size_t(s.f) + size_t(c)] = t[size_t(c) * size_t(s.d) + size_t(q)];
-    return 0;
-}
-}  // namespace
-
-int frisk_nmf_create(int device, const double* X, int64_t n, int64_t f, int32_t d, frisk_nmf** out) {
-    if (!out) return FRISK_E_ARG;
-    *out = nullptr;
-    if (!X || n < 1 || f < 1 || d < 1 || d > frisk_nmf_impl::NMF_MAX_D || !all_finite_nonneg(X, n * f)) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
-    if (!on.ok) return FRISK_E_HIP;
-    frisk_nmf* h = new (std::nothrow) frisk_nmf;
-    if (!h) return FRISK_E_HIP;
-    h->s.device = device;
-    h->s.n = n;
-    h->s.f = f;
-    h->s.d = d;
-    if (h->s.create(X)) {
-        delete h;
-        return FRISK_E_HIP;
-    }
-    *out = h;
-    return FRISK_OK;
-}
-
-int frisk_nmf_xq(frisk_nmf* h, const double* Q, int32_t p, double* Y_out) {
-    if (!h || !Q || !Y_out || p < 1 || p > frisk_nmf_impl::NMF_MAX_P || !all_finite(Q, h->s.f * p)) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.xq(Q, p, Y_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_nmf_xtq(frisk_nmf* h, const double* Q, int32_t p, double* Z_out) {
-    if (!h || !Q || !Z_out || p < 1 || p > frisk_nmf_impl::NMF_MAX_P || !all_finite(Q, h->s.n * p)) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.xtq(Q, p, Z_out) ? FRISK_E_HIP : FRISK_OK;
-}
-
-int frisk_nmf_set(frisk_nmf* h, const double* W, const double* H) {
-    if (!h) return FRISK_E_ARG;
-    if ((W && !all_finite(W, h->s.n * h->s.d)) || (H && !all_finite(H, int64_t(h->s.d) * h->s.f))) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    if (W && hipMemcpy(h->s.W, W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return FRISK_E_HIP;
-    if (H && nmf_put_H(h->s, H)) return FRISK_E_HIP;
-    return FRISK_OK;
-}
-
-int frisk_nmf_get(frisk_nmf* h, double* W, double* H) {
-    if (!h) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    if (W && hipMemcpy(W, h->s.W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return FRISK_E_HIP;
-    if (H && nmf_take_H(h->s, H)) return FRISK_E_HIP;
-    return FRISK_OK;
-}
-
-int frisk_nmf_step(frisk_nmf* h, double* W_inout, double* H_inout, int32_t update_H, double* violation) {
-    if (!h || !violation) return FRISK_E_ARG;
-    if (int e = frisk_nmf_set(h, W_inout, H_inout)) return e;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    if (h->s.step(update_H ? 1 : 0, violation)) return FRISK_E_HIP;
-    return frisk_nmf_get(h, W_inout, H_inout);
-}
-
-int frisk_nmf_transform_prepare(frisk_nmf* h) {
-    if (!h) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
-    if (!on.ok) return FRISK_E_HIP;
-    return h->s.prepare() ? FRISK_E_HIP : FRISK_OK;
-}
-
-double frisk_nmf_last_ms(const frisk_nmf* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
-
-void frisk_nmf_destroy(frisk_nmf* h) {
-    if (!h) return;
-    frisk_proj::OnDevice on(h->s.device);
-    delete h;
-}
 
 }  // extern "C"

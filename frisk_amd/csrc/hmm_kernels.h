@@ -288,11 +288,6 @@ __global__ void __launch_bounds__(64) hmm_covar_walk(const double* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host: fit
-#define HMMG_CHECK(call)                                    \
-    do {                                                    \
-        if ((call) != hipSuccess) return -2;                \
-    } while (0)
-
 // the device arrays of one sequence: allocated once, used by every round
 struct Work {
     frisk_proj::DevMem mem;
@@ -313,7 +308,7 @@ struct Work {
         part = mem.get<double>(size_t(PARTS) * 4);
         out = mem.get<double>(16);
         if (!dx || !B || !A || !pm || !edge || !edgeB || !acc || !cv || !part || !out) return -2;
-        HMMG_CHECK(hipMemcpy(dx, x, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(dx, x, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
         return 0;
     }
 };
@@ -330,8 +325,8 @@ inline int e_step(const Work& w, int64_t n, const frisk_hmm::Model& m, double* S
     hipLaunchKernelGGL(hmm_forward_walk, dim3(gp), dim3(64), 0, 0, n, P, par, w.B, w.edge, w.A, w.acc);
     hipLaunchKernelGGL(hmm_backward_walk, dim3(gp), dim3(64), 0, 0, w.dx, n, P, par, w.B, w.edge, w.edgeB, w.A, w.acc);
     hipLaunchKernelGGL(hmm_reduce_rows, dim3(1), dim3(RED_T), 0, 0, w.acc, P, ACC, w.out);
-    HMMG_CHECK(hipGetLastError());
-    HMMG_CHECK(hipMemcpy(S, w.out, ACC * sizeof(double), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(S, w.out, ACC * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -341,7 +336,7 @@ inline int e_step_only(const double* x, int64_t n, const frisk_hmm::Model& m, do
     if (w.load(x, n)) return -2;
     double S[ACC];
     if (e_step(w, n, m, S)) return -2;
-    if (post) HMMG_CHECK(hipMemcpy(post, w.A, size_t(n) * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (post) FRISK_HIP_CHECK(hipMemcpy(post, w.A, size_t(n) * 2 * sizeof(double), hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; ++k) stats[k] = S[k];
     stats[8] = S[8] + S[9];
     return 0;
@@ -358,15 +353,15 @@ inline int fit(const double* x, int64_t n, int n_iter, double tol, double min_co
     // start (GaussianHMM2._init)
     hipLaunchKernelGGL(hmm_init_range, dim3(C), dim3(RED_T), 0, 0, dx, n, C, part);
     hipLaunchKernelGGL(hmm_init_range_final, dim3(1), dim3(RED_T), 0, 0, part, C, out);
-    HMMG_CHECK(hipGetLastError());
-    HMMG_CHECK(hipMemcpy(h, out, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(h, out, 3 * sizeof(double), hipMemcpyDeviceToHost));
     double c[2] = {h[0], h[1]};
     const double mu = h[2] / double(n);
     for (int it = 0; it < 100; ++it) {
         hipLaunchKernelGGL(hmm_init_assign, dim3(C), dim3(RED_T), 0, 0, dx, n, C, c[0], c[1], part);
         hipLaunchKernelGGL(hmm_reduce_rows, dim3(1), dim3(RED_T), 0, 0, part, C, 4, out);
-        HMMG_CHECK(hipGetLastError());
-        HMMG_CHECK(hipMemcpy(h, out, 4 * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipMemcpy(h, out, 4 * sizeof(double), hipMemcpyDeviceToHost));
         const double nw[2] = {h[1] > 0 ? h[0] / h[1] : c[0], h[3] > 0 ? h[2] / h[3] : c[1]};
         // numpy.allclose(new, c); on convergence the centres of the PREVIOUS round are kept
         if (std::fabs(nw[0] - c[0]) <= 1e-8 + 1e-5 * std::fabs(c[0]) && std::fabs(nw[1] - c[1]) <= 1e-8 + 1e-5 * std::fabs(c[1])) break;
@@ -375,8 +370,8 @@ inline int fit(const double* x, int64_t n, int n_iter, double tol, double min_co
     m.means[0] = std::min(c[0], c[1]); m.means[1] = std::max(c[0], c[1]);
     hipLaunchKernelGGL(hmm_init_var, dim3(C), dim3(RED_T), 0, 0, dx, n, C, mu, part);
     hipLaunchKernelGGL(hmm_reduce_rows, dim3(1), dim3(RED_T), 0, 0, part, C, 1, out);
-    HMMG_CHECK(hipGetLastError());
-    HMMG_CHECK(hipMemcpy(h, out, sizeof(double), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(h, out, sizeof(double), hipMemcpyDeviceToHost));
     m.covars[0] = m.covars[1] = h[0] / double(n) + min_covar;
     m.startprob[0] = m.startprob[1] = 0.5;
     for (double& a : m.transmat) a = 0.5;
@@ -388,7 +383,7 @@ inline int fit(const double* x, int64_t n, int n_iter, double tol, double min_co
     for (int it = 0; it < n_iter; ++it) {
         if (e_step(w, n, m, h)) return -2;
         double g[2];
-        HMMG_CHECK(hipMemcpy(g, A, 2 * sizeof(double), hipMemcpyDeviceToHost));      // posterior of the first window
+        FRISK_HIP_CHECK(hipMemcpy(g, A, 2 * sizeof(double), hipMemcpyDeviceToHost));      // posterior of the first window
         const double* S = h;
         const double ll = S[8] + S[9];
         // M step (hmmlearn's defaults: flat Dirichlet priors, means_weight 0, covars_prior / weight 1e-2 / 1)
@@ -402,9 +397,9 @@ inline int fit(const double* x, int64_t n, int n_iter, double tol, double min_co
         const double w0 = S[0], w1 = S[1];
         hipLaunchKernelGGL(hmm_covar_walk, dim3(gp), dim3(64), 0, 0, dx, n, P, m.means[0], m.means[1], A, cv);
         hipLaunchKernelGGL(hmm_reduce_rows, dim3(1), dim3(RED_T), 0, 0, cv, P, 2, out);
-        HMMG_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipGetLastError());
         double cc[2];
-        HMMG_CHECK(hipMemcpy(cc, out, 2 * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipMemcpy(cc, out, 2 * sizeof(double), hipMemcpyDeviceToHost));
         m.covars[0] = std::max((covars_prior + cc[0]) / w0, 1e-300);
         m.covars[1] = std::max((covars_prior + cc[1]) / w1, 1e-300);
         F.loglik = ll;
@@ -535,11 +530,11 @@ inline int viterbi_segments(const double* x, const int64_t* off, int32_t n_seg, 
     uint8_t* entry = mem.get<uint8_t>(size_t(K));
     int8_t* dpath = mem.get<int8_t>(size_t(n));
     if (!dx || !dpa || !dpb || !dfirst || !dseg || !back || !M || !choice || !endst || !entry || !dpath) return -2;
-    HMMG_CHECK(hipMemcpy(dx, x + base, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
-    HMMG_CHECK(hipMemcpy(dpa, pa.data(), size_t(K) * sizeof(int64_t), hipMemcpyHostToDevice));
-    HMMG_CHECK(hipMemcpy(dpb, pb.data(), size_t(K) * sizeof(int64_t), hipMemcpyHostToDevice));
-    HMMG_CHECK(hipMemcpy(dfirst, pfirst.data(), size_t(K), hipMemcpyHostToDevice));
-    HMMG_CHECK(hipMemcpy(dseg, seg_piece.data(), (size_t(n_seg) + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dx, x + base, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dpa, pa.data(), size_t(K) * sizeof(int64_t), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dpb, pb.data(), size_t(K) * sizeof(int64_t), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dfirst, pfirst.data(), size_t(K), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dseg, seg_piece.data(), (size_t(n_seg) + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     const VPar par{m.means[0], m.means[1], m.covars[0], m.covars[1], std::log(m.covars[0]), std::log(m.covars[1]),
                    std::log(m.transmat[0]), std::log(m.transmat[1]), std::log(m.transmat[2]), std::log(m.transmat[3]),
                    std::log(m.startprob[0]), std::log(m.startprob[1])};
@@ -547,11 +542,10 @@ inline int viterbi_segments(const double* x, const int64_t* off, int32_t n_seg, 
     hipLaunchKernelGGL(hmm_vit_pieces, dim3(gk), dim3(64), 0, 0, dx, dpa, dpb, dfirst, K, par, back, M);
     hipLaunchKernelGGL(hmm_vit_cuts, dim3(gs), dim3(64), 0, 0, dseg, n_seg, M, choice, endst, entry);
     hipLaunchKernelGGL(hmm_vit_backtrack, dim3(gk), dim3(64), 0, 0, dpa, dpb, K, back, endst, entry, dpath);
-    HMMG_CHECK(hipGetLastError());
-    HMMG_CHECK(hipMemcpy(path + base, dpath, size_t(n), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(path + base, dpath, size_t(n), hipMemcpyDeviceToHost));
     return 0;
 }
 
-#undef HMMG_CHECK
 
 }  // namespace frisk_hmm_gpu

@@ -11,15 +11,10 @@
 // The right singular vectors of A are the eigenvectors of G and S^2 its eigenvalues; the caller decomposes G and hands S and V
 // back (commit), which also installs the batch's mean, variance and row count.
 // Every reduction has a fixed order that depends on the shape only, and there is no floating-point atomic: every output is
-// bit-identical from run to run.  Included from frisk_abi.hip after proj_kernels.h.
+// bit-identical from run to run.  Included from frisk_analysis.hip after proj_kernels.h.
 #pragma once
 
 #include "proj_kernels.h"
-
-#define IPCA_CHECK(call)                                    \
-    do {                                                    \
-        if ((call) != hipSuccess) return -2;                \
-    } while (0)
 
 namespace frisk_ipca_impl {
 
@@ -154,7 +149,7 @@ struct State {
         S = mem.get<double>(sd); Vt = mem.get<double>(sd * sf); Vfd = mem.get<double>(sd * sf);
         bsum = mem.get<double>(sf); T = mem.get<double>(sf); G = mem.get<double>(sf * sf);
         if (!mean || !var || !mean_new || !var_new || !S || !Vt || !Vfd || !bsum || !T || !G) return -2;
-        for (hipEvent_t& e : ev) IPCA_CHECK(hipEventCreate(&e));
+        for (hipEvent_t& e : ev) FRISK_HIP_CHECK(hipEventCreate(&e));
         return 0;
     }
 
@@ -167,19 +162,15 @@ struct State {
         const int nsplit = int((b + rows_per - 1) / rows_per);
         const int Tn = int(f_pad / COV_T);
         const int ntile = Tn * (Tn + 1) / 2;
-        // K split as frisk_proj::cov: enough blocks to fill the chip, a split length that depends on the shape only
-        int64_t ksplit = std::max<int64_t>(1, (2048 + ntile - 1) / ntile);
-        ksplit = std::min<int64_t>(ksplit, rows_pad / COV_KSTEP);
-        const int64_t k_per = round_up((rows_pad + ksplit - 1) / ksplit, COV_KSTEP);
-        ksplit = (rows_pad + k_per - 1) / k_per;
+        const auto [ksplit, k_per] = frisk_proj::cov_ksplit(rows_pad, ntile);
         double* dX = X.ensure(size_t(b) * size_t(f));
         double* dA = A.ensure(size_t(rows_pad) * size_t(f_pad));
         double* dpart = part.ensure(2 * size_t(nsplit) * size_t(f));
         double* dcov = covpart.ensure(size_t(ksplit) * size_t(ntile) * COV_T * COV_T);
         if (!dX || !dA || !dpart || !dcov) return -2;
-        IPCA_CHECK(hipEventRecord(ev[0], 0));
-        IPCA_CHECK(hipMemcpy(dX, X_in, size_t(b) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
-        IPCA_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(hipMemcpy(dX, X_in, size_t(b) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
         const unsigned gf = unsigned((f + 255) / 256);
         hipLaunchKernelGGL(frisk_proj::proj_colsum_part, dim3(gf, unsigned(nsplit)), dim3(256), 0, 0, dX, b, f, rows_per, dpart);
         hipLaunchKernelGGL(ipca_colsum, dim3(gf), dim3(256), 0, 0, dpart, nsplit, b, f, bsum, T);
@@ -190,16 +181,16 @@ struct State {
         const unsigned gs = unsigned(std::min<int64_t>((total + 255) / 256, 65536));
         hipLaunchKernelGGL(ipca_stack, dim3(gs), dim3(256), 0, 0, dX, T, mean_new, mean, S, Vt, seen, b, f, d, coef, rows_pad, f_pad,
                            dA);
-        IPCA_CHECK(hipEventRecord(ev[2], 0));
+        FRISK_HIP_CHECK(hipEventRecord(ev[2], 0));
         hipLaunchKernelGGL(frisk_proj::proj_cov_part, dim3(unsigned(ntile), unsigned(ksplit)), dim3(256), 0, 0, dA, f_pad, rows_pad,
                            k_per, Tn, ntile, dcov);
         hipLaunchKernelGGL(frisk_proj::proj_cov_reduce, dim3(unsigned(ntile)), dim3(256), 0, 0, dcov, int(ksplit), Tn, ntile, f, 1.0, G);
-        IPCA_CHECK(hipEventRecord(ev[3], 0));
-        IPCA_CHECK(hipGetLastError());
-        IPCA_CHECK(hipMemcpy(G_out, G, size_t(f) * size_t(f) * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipEventRecord(ev[3], 0));
+        FRISK_HIP_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipMemcpy(G_out, G, size_t(f) * size_t(f) * sizeof(double), hipMemcpyDeviceToHost));
         for (int k = 0; k < 3; ++k) {
             float t = 0.f;
-            IPCA_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+            FRISK_HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
             ms[k] = double(t);
         }
         pending_b = b;
@@ -209,11 +200,10 @@ struct State {
     // S[d], Vt[d][f] (host) become the decomposition; Vfd is its transpose for the transform kernel.
     int upload_sv(const double* S_in, const double* Vt_in) {
         std::vector<double> vfd(size_t(f) * size_t(d));
-        for (int q = 0; q < d; ++q)
-            for (int64_t c = 0; c < f; ++c) vfd[size_t(c) * size_t(d) + size_t(q)] = Vt_in[size_t(q) * size_t(f) + size_t(c)];
-        IPCA_CHECK(hipMemcpy(S, S_in, size_t(d) * sizeof(double), hipMemcpyHostToDevice));
-        IPCA_CHECK(hipMemcpy(Vt, Vt_in, size_t(d) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
-        IPCA_CHECK(hipMemcpy(Vfd, vfd.data(), vfd.size() * sizeof(double), hipMemcpyHostToDevice));
+        frisk_proj::transpose(Vt_in, d, f, vfd.data());
+        FRISK_HIP_CHECK(hipMemcpy(S, S_in, size_t(d) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(Vt, Vt_in, size_t(d) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(Vfd, vfd.data(), vfd.size() * sizeof(double), hipMemcpyHostToDevice));
         return 0;
     }
 
@@ -233,8 +223,8 @@ struct State {
         seen = n_seen;
         fitted = n_seen > 0;
         if (!fitted) return 0;
-        IPCA_CHECK(hipMemcpy(mean, mean_in, size_t(f) * sizeof(double), hipMemcpyHostToDevice));
-        IPCA_CHECK(hipMemcpy(var, var_in, size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(mean, mean_in, size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(var, var_in, size_t(f) * sizeof(double), hipMemcpyHostToDevice));
         return upload_sv(S_in, Vt_in);
     }
 
@@ -247,13 +237,13 @@ struct State {
         if (!dX || !dA || !dY) return -2;
         for (int64_t r0 = 0; r0 < n; r0 += piece) {
             const int64_t m = std::min<int64_t>(piece, n - r0);
-            IPCA_CHECK(hipMemcpy(dX, X_in + r0 * f, size_t(m) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+            FRISK_HIP_CHECK(hipMemcpy(dX, X_in + r0 * f, size_t(m) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
             const int64_t total = m * f_pad;
             const unsigned gc = unsigned(std::min<int64_t>((total + 255) / 256, 65536));
             hipLaunchKernelGGL(frisk_proj::proj_center, dim3(gc), dim3(256), 0, 0, dX, mean, m, f, m, f_pad, dA);
             hipLaunchKernelGGL(frisk_proj::proj_transform, dim3(unsigned((m + 3) / 4)), dim3(256), 0, 0, dA, Vfd, m, f, f_pad, d, dY);
-            IPCA_CHECK(hipGetLastError());
-            IPCA_CHECK(hipMemcpy(Y_out + r0 * d, dY, size_t(m) * size_t(d) * sizeof(double), hipMemcpyDeviceToHost));
+            FRISK_HIP_CHECK(hipGetLastError());
+            FRISK_HIP_CHECK(hipMemcpy(Y_out + r0 * d, dY, size_t(m) * size_t(d) * sizeof(double), hipMemcpyDeviceToHost));
         }
         return 0;
     }
@@ -261,4 +251,3 @@ struct State {
 
 }  // namespace frisk_ipca_impl
 
-#undef IPCA_CHECK

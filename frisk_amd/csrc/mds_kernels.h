@@ -14,7 +14,7 @@
 //                    row i of B X without its cancelling diagonal; X_{t+1} = (1 / n) that sum.  Per-thread sums, block_sum
 //                    per entry, per-block stress partials summed in block order by one block.
 // One pass on X_t yields stress(X_t) and X_{t+1}; the host driver evaluates sklearn's stop rule in double after each pass.
-// Included from frisk_abi.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
+// Included from frisk_analysis.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,11 +28,8 @@
 namespace frisk_mds_impl {
 
 using frisk_proj::block_sum;
-
-#define MDS_CHECK(call)                                     \
-    do {                                                    \
-        if ((call) != hipSuccess) return -2;                \
-    } while (0)
+using frisk_proj::load_rows;
+using frisk_proj::rows_per_block;
 
 constexpr int MAX_D = 64;           // output dims
 constexpr int64_t MAX_N = 50000;    // dense n x n FP64 dissimilarities: 20 GB at the cap
@@ -97,16 +94,6 @@ __global__ __launch_bounds__(256) void mds_dissimilarities(const double* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------- one SMACOF step
-// Rows i0 .. i0 + R - 1 of the block in LDS (zero beyond n and beyond d).
-template <int MAXD, int R>
-__device__ inline void load_rows(const double* __restrict__ Y, int64_t n, int d, int64_t i0, double (*yi)[MAXD]) {
-    for (int e = threadIdx.x; e < R * MAXD; e += 256) {
-        const int r = e / MAXD, k = e % MAXD;
-        yi[r][k] = (i0 + r < n && k < d) ? Y[(i0 + r) * d + k] : 0.0;
-    }
-    __syncthreads();
-}
-
 // From X_t = Y: part[2 b] = sum over the block's rows i and all j of (dist_ij - D_ij)^2, part[2 b + 1] = of dist_ij^2; with
 // guttman, Ynext[i] = (1 / n) sum_j ratio_ij (y_i - y_j).
 template <int MAXD, int R>
@@ -188,8 +175,6 @@ __global__ __launch_bounds__(256) void mds_sum_parts(const double* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------- host driver
-inline int rows_per_block(int d) { return d <= 4 ? 8 : d <= 16 ? 2 : 1; }
-
 // Device state of one MDS problem (the C handle frisk_mds).  Every buffer is allocated by create.
 struct State {
     int device = 0;
@@ -210,30 +195,30 @@ struct State {
         sums = mem.get<double>(2);
         double* X = mem.get<double>(size_t(n) * size_t(f));
         if (!D || !Ya || !Yb || !part || !sums || !X) return -2;
-        MDS_CHECK(hipMemcpy(X, X_in, size_t(n) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(X, X_in, size_t(n) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
         const unsigned T = unsigned((n + DIS_T - 1) / DIS_T);
         hipLaunchKernelGGL(mds_dissimilarities, dim3(T, T), dim3(256), 0, 0, X, n, f, D);
-        MDS_CHECK(hipGetLastError());
-        MDS_CHECK(hipDeviceSynchronize());
+        FRISK_HIP_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipDeviceSynchronize());
         return 0;
     }
 
     // One pass from Y: stress and sum of squared distances of Y to the host (sums_out[2]); with guttman, Ynext = the next state.
     int step(const double* Y, double* Ynext, int guttman, double* sums_out) {
         const unsigned nb = unsigned(step_blocks());
-        if (d <= 4) hipLaunchKernelGGL((mds_step<4, 8>), dim3(nb), dim3(256), 0, 0, Y, D, n, d, guttman, Ynext, part);
-        else if (d <= 16) hipLaunchKernelGGL((mds_step<16, 2>), dim3(nb), dim3(256), 0, 0, Y, D, n, d, guttman, Ynext, part);
-        else hipLaunchKernelGGL((mds_step<MAX_D, 1>), dim3(nb), dim3(256), 0, 0, Y, D, n, d, guttman, Ynext, part);
+        frisk_proj::for_rows_per_block<MAX_D>(d, [&](auto maxd, auto r) {
+            hipLaunchKernelGGL((mds_step<decltype(maxd)::value, decltype(r)::value>), dim3(nb), dim3(256), 0, 0, Y, D, n, d, guttman, Ynext, part);
+        });
         hipLaunchKernelGGL(mds_sum_parts, dim3(1), dim3(256), 0, 0, part, int64_t(nb), sums);
-        MDS_CHECK(hipGetLastError());
-        MDS_CHECK(hipMemcpy(sums_out, sums, 2 * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipMemcpy(sums_out, sums, 2 * sizeof(double), hipMemcpyDeviceToHost));
         return 0;
     }
 
     // _smacof_single(D, init=Y0, max_iter, eps) with metric=True.  Returns 0 or -2.
     int run(const double* Y0, int max_iter, double eps, double* Y_out, double* stress_out, int32_t* n_iter_out, double* trace) {
         const size_t bytes = size_t(n) * size_t(d) * sizeof(double);
-        MDS_CHECK(hipMemcpy(Ya, Y0, bytes, hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(Ya, Y0, bytes, hipMemcpyHostToDevice));
         double* cur = Ya;
         double* nxt = Yb;
         double s[2];
@@ -251,7 +236,7 @@ struct State {
             if (last) break;
             std::swap(cur, nxt);
         }
-        MDS_CHECK(hipMemcpy(Y_out, cur, bytes, hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipMemcpy(Y_out, cur, bytes, hipMemcpyDeviceToHost));
         if (stress_out) *stress_out = stress;
         if (n_iter_out) *n_iter_out = it + 1;
         return 0;
@@ -260,4 +245,3 @@ struct State {
 
 }  // namespace frisk_mds_impl
 
-#undef MDS_CHECK

@@ -15,7 +15,7 @@
 //                                      block_sum per block, the blocks in index order by one thread (nmf_sum_parts).
 // The two products serve the coordinate descent (p = d) and the range finder of the initialisation (p up to d + 10).  They are
 // plain VALU: each is bound by reading X once (DESIGN.md section 9.4 has the measured fraction of the HBM rate).
-// Included from frisk_abi.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
+// Included from frisk_analysis.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,11 +25,6 @@
 #include <vector>
 
 #include "proj_kernels.h"
-
-#define NMF_CHECK(call)                                     \
-    do {                                                    \
-        if ((call) != hipSuccess) return -2;                \
-    } while (0)
 
 namespace frisk_nmf_impl {
 
@@ -219,10 +214,10 @@ struct State {
         vpart = mem.get<double>(size_t(sweep_blocks(std::max(n, f))));
         viol = mem.get<double>(2);
         if (!X || !W || !Ht || !XHt || !XtW || !G || !Qn || !Qf || !xpart || !vpart || !viol) return -2;
-        for (hipEvent_t& e : ev) NMF_CHECK(hipEventCreate(&e));
-        NMF_CHECK(hipMemcpy(X, X_in, sn * sf * sizeof(double), hipMemcpyHostToDevice));
-        NMF_CHECK(hipMemset(W, 0, sn * sd * sizeof(double)));
-        NMF_CHECK(hipMemset(Ht, 0, sf * sd * sizeof(double)));
+        for (hipEvent_t& e : ev) FRISK_HIP_CHECK(hipEventCreate(&e));
+        FRISK_HIP_CHECK(hipMemcpy(X, X_in, sn * sf * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemset(W, 0, sn * sd * sizeof(double)));
+        FRISK_HIP_CHECK(hipMemset(Ht, 0, sf * sd * sizeof(double)));
         return 0;
     }
 
@@ -259,30 +254,30 @@ struct State {
 
     int elapsed(int k, int a, int b) {
         float t = 0.f;
-        NMF_CHECK(hipEventElapsedTime(&t, ev[a], ev[b]));
+        FRISK_HIP_CHECK(hipEventElapsedTime(&t, ev[a], ev[b]));
         ms[k] = double(t);
         return 0;
     }
 
     // Y_out[n][p] = X Q_in[f][p] (host buffers)
     int xq(const double* Q_in, int p, double* Y_out) {
-        NMF_CHECK(hipMemcpy(Qf, Q_in, size_t(f) * size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-        NMF_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(hipMemcpy(Qf, Q_in, size_t(f) * size_t(p) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
         launch_xq(Qf, p, Qn);
-        NMF_CHECK(hipEventRecord(ev[1], 0));
-        NMF_CHECK(hipGetLastError());
-        NMF_CHECK(hipMemcpy(Y_out, Qn, size_t(n) * size_t(p) * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipMemcpy(Y_out, Qn, size_t(n) * size_t(p) * sizeof(double), hipMemcpyDeviceToHost));
         return elapsed(0, 0, 1);
     }
 
     // Z_out[f][p] = XT Q_in[n][p] (host buffers)
     int xtq(const double* Q_in, int p, double* Z_out) {
-        NMF_CHECK(hipMemcpy(Qn, Q_in, size_t(n) * size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-        NMF_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(hipMemcpy(Qn, Q_in, size_t(n) * size_t(p) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
         launch_xtq(Qn, p, Qf);
-        NMF_CHECK(hipEventRecord(ev[1], 0));
-        NMF_CHECK(hipGetLastError());
-        NMF_CHECK(hipMemcpy(Z_out, Qf, size_t(f) * size_t(p) * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipMemcpy(Z_out, Qf, size_t(f) * size_t(p) * sizeof(double), hipMemcpyDeviceToHost));
         return elapsed(1, 0, 1);
     }
 
@@ -290,30 +285,30 @@ struct State {
     int prepare() {
         hipLaunchKernelGGL(nmf_gram, dim3(unsigned(d * d)), dim3(256), 0, 0, Ht, f, d, G);
         launch_xq(Ht, d, XHt);
-        NMF_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipGetLastError());
         frozen = true;
         return 0;
     }
 
     // One iteration of _fit_coordinate_descent: the W sweep, then with update_H the Ht sweep on XT.  violation = the sum of both.
     int step(int update_H, double* violation) {
-        NMF_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
         if (!frozen) {
             hipLaunchKernelGGL(nmf_gram, dim3(unsigned(d * d)), dim3(256), 0, 0, Ht, f, d, G);
             launch_xq(Ht, d, XHt);
         }
-        NMF_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
         launch_sweep(W, XHt, n, viol);
         frozen = !update_H;             // without update_H, G and XHt stay those of the unchanged Ht
         if (update_H) hipLaunchKernelGGL(nmf_gram, dim3(unsigned(d * d)), dim3(256), 0, 0, W, n, d, G);
-        NMF_CHECK(hipEventRecord(ev[2], 0));
+        FRISK_HIP_CHECK(hipEventRecord(ev[2], 0));
         if (update_H) launch_xtq(W, d, XtW);
-        NMF_CHECK(hipEventRecord(ev[3], 0));
+        FRISK_HIP_CHECK(hipEventRecord(ev[3], 0));
         if (update_H) launch_sweep(Ht, XtW, f, viol + 1);
-        NMF_CHECK(hipEventRecord(ev[4], 0));
-        NMF_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipEventRecord(ev[4], 0));
+        FRISK_HIP_CHECK(hipGetLastError());
         double v[2] = {0.0, 0.0};
-        NMF_CHECK(hipMemcpy(v, viol, (update_H ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipMemcpy(v, viol, (update_H ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost));
         double total = 0.0;             // sklearn: violation = 0.; violation += (W sweep); violation += (H sweep)
         total += v[0];
         if (update_H) total += v[1];
@@ -325,4 +320,3 @@ struct State {
 
 }  // namespace frisk_nmf_impl
 
-#undef NMF_CHECK

@@ -8,7 +8,7 @@
 //   DBSCAN        integer counts; union-find whose result does not depend on the order of the unions (see dbscan below);
 //   k-means       per-block partials (fixed wave butterfly + waves in order), blocks summed in order by one thread per value;
 //                 empty clusters take the farthest points by exact comparisons (descending distance, lowest index on a tie).
-// Included from frisk_abi.hip (one translation unit); the C entry points there are thin wrappers of the drivers below.
+// Included from frisk_analysis.hip; the C entry points there are thin wrappers of the drivers below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,7 +16,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
+
+// every host driver of the analysis headers returns 0 or -2 (a HIP call failed)
+#define FRISK_HIP_CHECK(call)                               \
+    do {                                                    \
+        if ((call) != hipSuccess) return -2;                \
+    } while (0)
 
 namespace frisk_proj {
 
@@ -249,6 +256,25 @@ __device__ inline double block_sum(double v, double* red) {
     return s;
 }
 
+// Rows i0 .. i0 + R - 1 of a block in LDS, zero beyond n and beyond d (t-SNE's passes, MDS's step: each thread then takes the
+// points j = tid, tid + 256, ... in order).
+template <int MAXD, int R>
+__device__ inline void load_rows(const double* __restrict__ Y, int64_t n, int d, int64_t i0, double (*yi)[MAXD]) {
+    for (int e = threadIdx.x; e < R * MAXD; e += 256) {
+        const int r = e / MAXD, k = e % MAXD;
+        yi[r][k] = (i0 + r < n && k < d) ? Y[(i0 + r) * d + k] : 0.0;
+    }
+    __syncthreads();
+}
+// ... how many rows that is at output dimension d, and the instantiation that goes with it: f(MAXD, R) as integral constants
+inline int rows_per_block(int d) { return d <= 4 ? 8 : d <= 16 ? 2 : 1; }
+template <int MAX_D, typename F>
+inline void for_rows_per_block(int d, F&& f) {
+    if (d <= 4) f(std::integral_constant<int, 4>(), std::integral_constant<int, 8>());
+    else if (d <= 16) f(std::integral_constant<int, 16>(), std::integral_constant<int, 2>());
+    else f(std::integral_constant<int, MAX_D>(), std::integral_constant<int, 1>());
+}
+
 // One Lloyd step, first half: nearest centre of each point (lowest index on a tie), whether any label changed, dist[i] = the
 // squared distance of point i to that centre, and per block part[b][c (d+1) + q] = sum of coordinate q (q = d: the count) of the
 // block's points of centre c, part[b][k (d+1)] = their squared distances.
@@ -438,11 +464,6 @@ struct OnDevice {
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-#define PROJ_CHECK(call)                                    \
-    do {                                                    \
-        if ((call) != hipSuccess) return -2;                \
-    } while (0)
-
 // Centred, zero-padded copy of X on the device; mean (length f) on the device.  Returns 0 or -2.
 struct Centred {
     double* Xc = nullptr;
@@ -457,10 +478,10 @@ inline int upload_centred(DevMem& mem, const double* X, int64_t n, int64_t f, co
     out.Xc = mem.get<double>(size_t(out.n_pad * out.f_pad));
     out.mean = mem.get<double>(size_t(f));
     if (!dX || !out.Xc || !out.mean) return -2;
-    PROJ_CHECK(hipMemcpy(dX, X, size_t(n * f) * sizeof(double), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dX, X, size_t(n * f) * sizeof(double), hipMemcpyHostToDevice));
     const unsigned gf = unsigned((f + 255) / 256);
     if (mean_in) {
-        PROJ_CHECK(hipMemcpy(out.mean, mean_in, size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(out.mean, mean_in, size_t(f) * sizeof(double), hipMemcpyHostToDevice));
     } else {
         const int64_t rows_per = (n + MEAN_SPLITS - 1) / MEAN_SPLITS;
         const int nsplit = int((n + rows_per - 1) / rows_per);
@@ -472,8 +493,26 @@ inline int upload_centred(DevMem& mem, const double* X, int64_t n, int64_t f, co
     const int64_t total = out.n_pad * out.f_pad;
     const unsigned gc = unsigned(std::min<int64_t>((total + 255) / 256, 65536));
     hipLaunchKernelGGL(proj_center, dim3(gc), dim3(256), 0, 0, dX, out.mean, n, f, out.n_pad, out.f_pad, out.Xc);
-    PROJ_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// K split of the n_pad rows (a multiple of COV_KSTEP) that proj_cov_part sums per tile: enough blocks to fill the chip, a split
+// length that depends on the shape only (so results are reproducible)
+struct KSplit {
+    int64_t nsplit, rows_per;
+};
+inline KSplit cov_ksplit(int64_t n_pad, int ntile) {
+    int64_t nsplit = std::max<int64_t>(1, (2048 + ntile - 1) / ntile);
+    nsplit = std::min<int64_t>(nsplit, n_pad / COV_KSTEP);
+    const int64_t rows_per = round_up((n_pad + nsplit - 1) / nsplit, COV_KSTEP);
+    return {(n_pad + rows_per - 1) / rows_per, rows_per};
+}
+
+// dst[cols][rows] = the transpose of src[rows][cols], on the host (H and Vt arrive as [d][f]; the kernels read [f][d])
+inline void transpose(const double* src, int64_t rows, int64_t cols, double* dst) {
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t c = 0; c < cols; ++c) dst[size_t(c) * size_t(rows) + size_t(r)] = src[size_t(r) * size_t(cols) + size_t(c)];
 }
 
 // mean_out[f], cov_out[f*f] = XcT Xc / (n - 1) (n = 1: / 1).  Returns 0 or -2.
@@ -483,11 +522,7 @@ inline int cov(const double* X, int64_t n, int64_t f, double* mean_out, double* 
     if (int e = upload_centred(mem, X, n, f, nullptr, COV_KSTEP, cx)) return e;
     const int T = int(cx.f_pad / COV_T);
     const int ntile = T * (T + 1) / 2;
-    // K split: enough blocks to fill the chip, a split length that depends on the shape only (so results are reproducible)
-    int64_t nsplit = std::max<int64_t>(1, (2048 + ntile - 1) / ntile);
-    nsplit = std::min<int64_t>(nsplit, cx.n_pad / COV_KSTEP);
-    const int64_t rows_per = round_up((cx.n_pad + nsplit - 1) / nsplit, COV_KSTEP);
-    nsplit = (cx.n_pad + rows_per - 1) / rows_per;
+    const auto [nsplit, rows_per] = cov_ksplit(cx.n_pad, ntile);
     double* part = mem.get<double>(size_t(nsplit) * size_t(ntile) * COV_T * COV_T);
     double* dcov = mem.get<double>(size_t(f * f));
     if (!part || !dcov) return -2;
@@ -495,9 +530,9 @@ inline int cov(const double* X, int64_t n, int64_t f, double* mean_out, double* 
                        ntile, part);
     hipLaunchKernelGGL(proj_cov_reduce, dim3(unsigned(ntile)), dim3(256), 0, 0, part, int(nsplit), T, ntile, f,
                        n > 1 ? double(n - 1) : 1.0, dcov);
-    PROJ_CHECK(hipGetLastError());
-    PROJ_CHECK(hipMemcpy(mean_out, cx.mean, size_t(f) * sizeof(double), hipMemcpyDeviceToHost));
-    PROJ_CHECK(hipMemcpy(cov_out, dcov, size_t(f * f) * sizeof(double), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(mean_out, cx.mean, size_t(f) * sizeof(double), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipMemcpy(cov_out, dcov, size_t(f * f) * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -509,10 +544,10 @@ inline int transform(const double* X, const double* mean, const double* V, int64
     double* dV = mem.get<double>(size_t(f) * size_t(d));
     double* dY = mem.get<double>(size_t(n) * size_t(d));
     if (!dV || !dY) return -2;
-    PROJ_CHECK(hipMemcpy(dV, V, size_t(f) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dV, V, size_t(f) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(proj_transform, dim3(unsigned((n + 3) / 4)), dim3(256), 0, 0, cx.Xc, dV, n, f, cx.f_pad, d, dY);
-    PROJ_CHECK(hipGetLastError());
-    PROJ_CHECK(hipMemcpy(Y_out, dY, size_t(n) * size_t(d) * sizeof(double), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(Y_out, dY, size_t(n) * size_t(d) * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -534,15 +569,15 @@ inline int dbscan(const double* Y, int64_t n, int d, double eps, int32_t min_sam
     int32_t* P = mem.get<int32_t>(size_t(n));
     int32_t* lab = mem.get<int32_t>(size_t(n));
     if (!dY || !cnt || !P || !lab) return -2;
-    PROJ_CHECK(hipMemcpy(dY, Y, size_t(n) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(dY, Y, size_t(n) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
     const unsigned grid = unsigned((n + 255) / 256);
     hipLaunchKernelGGL(db_init, dim3(grid), dim3(256), 0, 0, n, P);
     db_launch<DB_COUNT>(d, grid, dY, n, eps, min_samples, cnt, P, lab);
     db_launch<DB_UNION>(d, grid, dY, n, eps, min_samples, cnt, P, lab);
     hipLaunchKernelGGL(db_compress, dim3(grid), dim3(256), 0, 0, n, cnt, min_samples, P);
     db_launch<DB_BORDER>(d, grid, dY, n, eps, min_samples, cnt, P, lab);
-    PROJ_CHECK(hipGetLastError());
-    PROJ_CHECK(hipMemcpy(labels_out, lab, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(labels_out, lab, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
     // a root is the smallest core index of its cluster: number the roots in index order
     std::vector<int32_t> id(size_t(n), -1);
     int32_t next = 0;
@@ -573,9 +608,9 @@ inline int kmeans(const double* Y, int64_t n, int d, int k, const double* init_c
     int32_t* emp = mem.get<int32_t>(size_t(k));
     int64_t* far = mem.get<int64_t>(size_t(k));
     if (!dY || !C || !Cn || !part || !res || !lab || !changed || !dist || !S || !W || !emp || !far) return -2;
-    PROJ_CHECK(hipMemcpy(dY, Y, size_t(n) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
-    PROJ_CHECK(hipMemcpy(C, init_centers, size_t(k) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
-    PROJ_CHECK(hipMemset(lab, 0xff, size_t(n) * sizeof(int32_t)));          // -1: every label changes in the first step
+    FRISK_HIP_CHECK(hipMemcpy(dY, Y, size_t(n) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemcpy(C, init_centers, size_t(k) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
+    FRISK_HIP_CHECK(hipMemset(lab, 0xff, size_t(n) * sizeof(int32_t)));          // -1: every label changes in the first step
     auto step = [&](double* from, double* to) {
         if (d <= 4) hipLaunchKernelGGL(km_assign<4>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, dist, part);
         else if (d <= 16)
@@ -587,25 +622,24 @@ inline int kmeans(const double* Y, int64_t n, int d, int k, const double* init_c
     double h[2];
     int32_t ch = 0;
     for (it = 0; it < max_iter; ++it) {
-        PROJ_CHECK(hipMemset(changed, 0, sizeof(int32_t)));
+        FRISK_HIP_CHECK(hipMemset(changed, 0, sizeof(int32_t)));
         step(C, Cn);
-        PROJ_CHECK(hipGetLastError());
-        PROJ_CHECK(hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost));
-        PROJ_CHECK(hipMemcpy(&ch, changed, sizeof(ch), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipMemcpy(&ch, changed, sizeof(ch), hipMemcpyDeviceToHost));
         std::swap(C, Cn);
         if (!ch || h[0] <= tol) break;
     }
     const int32_t iters = it < max_iter ? it + 1 : max_iter;
     step(C, Cn);                    // final assignment to the final centres (Cn is scratch here)
-    PROJ_CHECK(hipGetLastError());
-    PROJ_CHECK(hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost));
-    PROJ_CHECK(hipMemcpy(labels_out, lab, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    PROJ_CHECK(hipMemcpy(centers_out, C, size_t(k) * size_t(d) * sizeof(double), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipGetLastError());
+    FRISK_HIP_CHECK(hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipMemcpy(labels_out, lab, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FRISK_HIP_CHECK(hipMemcpy(centers_out, C, size_t(k) * size_t(d) * sizeof(double), hipMemcpyDeviceToHost));
     if (inertia_out) *inertia_out = h[1];
     if (n_iter_out) *n_iter_out = iters;
     return 0;
 }
 
-#undef PROJ_CHECK
 
 }  // namespace frisk_proj

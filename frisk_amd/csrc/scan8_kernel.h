@@ -43,8 +43,6 @@
 #define FRISK8_UNROLL1 2           // unroll factor of the stage-1 position loop
 #define FRISK8_SHORT_LANES 6        // stage 1: up to this many lanes of a wave with short words get a pass each (more: per position)
 #define FRISK8_PRIO 3               // wave priority (s_setprio) of every stage but the scoring loop
-#define FRISK8_RING_PAD 16          // doubles behind every workgroup's slice of the ring, touched by nobody (the idle lanes of FRISK8_DEAL's
-                                    // parking waves stored there, at c34d7fb); part of the slice stride
 #define FRISK8_SLOTS 8             // misc counters per window (double-buffered by window parity)
 
 enum { M8_NPLACED = 1,             // misc slots (0, 2, 4, 5: M_UPA, M_UPG, M_NORPH, M_NVALID): orphans folded into the order-K table ...
@@ -105,20 +103,6 @@ __device__ inline uint32_t wave_sum_u32(uint32_t x) {
     x = dpp_addu<0xB1>(x); x = dpp_addu<0x4E>(x); x = dpp_addu<0x141>(x); x = dpp_addu<0x140>(x);
     return __builtin_amdgcn_readlane(int(x), 0) + __builtin_amdgcn_readlane(int(x), 16) +
            __builtin_amdgcn_readlane(int(x), 32) + __builtin_amdgcn_readlane(int(x), 48);
-}
-
-// The adaptive width's verdict, on the device (one thread, behind the sample launch): which form scores the rest of the scan.
-// counts[0] = sampled windows handed on anyway, [2] = scored, but a plain 4-bit counter would have wrapped, [3] = scored;
-// n_sampled = windows in the sample.  The rule is frisk_abi.hip's (measured break-evens there): 8-bit bulk when more than three
-// sampled windows in ten overflow 4 bits anyway; else the side table when the plain form would hand on more than side_share of
-// the windows that are scored.  verdict[0] = 1 plain 4-bit, 2 4-bit + side table, 3 8-bit; verdict[1..3] = the three counts (for
-// the host's statistics, read at the end of the scan).
-__global__ void scan8_decide_kernel(const unsigned int* __restrict__ counts, unsigned int n_sampled, double side_share, int side_ok,
-                                    unsigned int* __restrict__ verdict) {
-    const unsigned int handed = counts[0], would = counts[2], scored = counts[3];
-    unsigned int form = (double(handed) <= 0.3 * double(n_sampled)) ? 1u : 3u;
-    if (form == 1u && side_ok && double(handed + would) > side_share * double(handed + scored)) form = 2u;
-    verdict[0] = form; verdict[1] = handed; verdict[2] = would; verdict[3] = scored;
 }
 
 // ROLE names the launch (bit 0: the sample of the adaptive width, bit 1: no sliding, hence no ring): the code is otherwise the same, but a profiler's

@@ -11,7 +11,7 @@
 //               pass B: dY_i = sum_j (P_ij - Q_ij) num_ij (y_i - y_j) for R rows per block (each thread keeps its points in
 //               registers and its rows' sums in order, block_sum per entry), and on cost iterations sum P log(P / Q);
 //               update: gains, iY, Y per entry, per-block column sums; centring: every block sums the partials in order.
-// Included from frisk_abi.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
+// Included from frisk_analysis.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,11 +24,8 @@
 namespace frisk_tsne_impl {
 
 using frisk_proj::block_sum;
-
-#define TSNE_CHECK(call)                                    \
-    do {                                                    \
-        if ((call) != hipSuccess) return -2;                \
-    } while (0)
+using frisk_proj::load_rows;
+using frisk_proj::rows_per_block;
 
 constexpr int MAX_F = 64;           // input width (the reference's PCA keeps 50 columns)
 constexpr int MAX_D = 64;           // output dims
@@ -171,16 +168,6 @@ __global__ __launch_bounds__(256) void tsne_normalise(double* __restrict__ P, in
 }
 
 // ---------------------------------------------------------------------------------------------------------- one iteration
-// Rows i0 .. i0 + R - 1 of block b in LDS; each thread takes the points j = tid, tid + 256, ... in order.
-template <int MAXD, int R>
-__device__ inline void load_rows(const double* __restrict__ Y, int64_t n, int d, int64_t i0, double (*yi)[MAXD]) {
-    for (int e = threadIdx.x; e < R * MAXD; e += 256) {
-        const int r = e / MAXD, k = e % MAXD;
-        yi[r][k] = (i0 + r < n && k < d) ? Y[(i0 + r) * d + k] : 0.0;
-    }
-    __syncthreads();
-}
-
 template <int MAXD>
 __device__ inline double num_of(const double* yi, const double* yj, int d) {
     double s = 0.0;
@@ -307,8 +294,6 @@ __global__ __launch_bounds__(256) void tsne_centre(double* __restrict__ Y, int64
 }
 
 // ---------------------------------------------------------------------------------------------------------- host driver
-inline int rows_per_block(int d) { return d <= 4 ? 8 : d <= 16 ? 2 : 1; }
-
 template <int MAXD, int R>
 inline void launch_passes(const double* Y, const double* q, int64_t n, int d, double* part, double* S, int exaggerate, int cost,
                           double* dY, double* cpart) {
@@ -351,17 +336,17 @@ struct State {
         tries = mem.get<int32_t>(size_t(n));
         bad = mem.get<int32_t>(1);
         if (!X || !P || !Y || !iY || !gains || !dY || !part || !S || !cpart || !colpart || !cost || !beta || !tries || !bad) return -2;
-        TSNE_CHECK(hipMemcpy(X, X_in, size_t(n) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
-        TSNE_CHECK(hipMemcpy(Y, Y0, nd * sizeof(double), hipMemcpyHostToDevice));
-        TSNE_CHECK(hipMemset(iY, 0, nd * sizeof(double)));
+        FRISK_HIP_CHECK(hipMemcpy(X, X_in, size_t(n) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(Y, Y0, nd * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemset(iY, 0, nd * sizeof(double)));
         std::vector<double> ones(nd, 1.0);
-        TSNE_CHECK(hipMemcpy(gains, ones.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+        FRISK_HIP_CHECK(hipMemcpy(gains, ones.data(), nd * sizeof(double), hipMemcpyHostToDevice));
         return 0;
     }
 
     // P = q.  Returns 0, -1 (a row's sum P is 0 or not finite) or -2.
     int affinities() {
-        TSNE_CHECK(hipMemset(bad, 0, sizeof(int32_t)));
+        FRISK_HIP_CHECK(hipMemset(bad, 0, sizeof(int32_t)));
         const double logU = std::log(perplexity);
         if (n <= 1024) hipLaunchKernelGGL(tsne_rows<1>, dim3(unsigned(n)), dim3(1024), 0, 0, X, n, f, logU, P, beta, tries, bad);
         else if (n <= 8 * 1024) hipLaunchKernelGGL(tsne_rows<8>, dim3(unsigned(n)), dim3(1024), 0, 0, X, n, f, logU, P, beta, tries, bad);
@@ -373,9 +358,9 @@ struct State {
         hipLaunchKernelGGL(tsne_sum, dim3(1), dim3(256), 0, 0, rowsum, n, S);
         const int64_t count = n * n;
         hipLaunchKernelGGL(tsne_normalise, dim3(unsigned(std::min<int64_t>((count + 255) / 256, 65536))), dim3(256), 0, 0, P, count, S);
-        TSNE_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipGetLastError());
         int32_t flag = 0;
-        TSNE_CHECK(hipMemcpy(&flag, bad, sizeof(int32_t), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipMemcpy(&flag, bad, sizeof(int32_t), hipMemcpyDeviceToHost));
         if (flag) return -1;
         have_p = true;
         return 0;
@@ -387,24 +372,23 @@ struct State {
         for (int t = t0; t < t1; ++t) {
             const int exaggerate = t <= STOP_EXAGGERATION;
             const int with_cost = (t + 1) % 10 == 0;
-            if (d <= 4) launch_passes<4, 8>(Y, P, n, d, part, S, exaggerate, with_cost, dY, cpart);
-            else if (d <= 16) launch_passes<16, 2>(Y, P, n, d, part, S, exaggerate, with_cost, dY, cpart);
-            else launch_passes<MAX_D, 1>(Y, P, n, d, part, S, exaggerate, with_cost, dY, cpart);
+            frisk_proj::for_rows_per_block<MAX_D>(d, [&](auto maxd, auto r) {
+                launch_passes<decltype(maxd)::value, decltype(r)::value>(Y, P, n, d, part, S, exaggerate, with_cost, dY, cpart);
+            });
             if (with_cost) hipLaunchKernelGGL(tsne_sum, dim3(1), dim3(256), 0, 0, cpart, pass_blocks(), cost + (t + 1) / 10 - 1);
             hipLaunchKernelGGL(tsne_update, dim3(unsigned(nrb)), dim3(256), 0, 0, Y, iY, gains, dY, n, d,
                                t < MOMENTUM_SWITCH ? 0.5 : 0.8, colpart);
             hipLaunchKernelGGL(tsne_centre, dim3(unsigned(std::min<int64_t>((n * d + 255) / 256, 1024))), dim3(256), 0, 0, Y, n, d,
                                colpart, nrb);
         }
-        TSNE_CHECK(hipGetLastError());
+        FRISK_HIP_CHECK(hipGetLastError());
         const int c0 = t0 / 10, c1 = t1 / 10;        // cost slots (t + 1) / 10 - 1 of t0 <= t < t1
         if (cost_out && c1 > c0)
-            TSNE_CHECK(hipMemcpy(cost_out, cost + c0, size_t(c1 - c0) * sizeof(double), hipMemcpyDeviceToHost));
-        TSNE_CHECK(hipDeviceSynchronize());
+            FRISK_HIP_CHECK(hipMemcpy(cost_out, cost + c0, size_t(c1 - c0) * sizeof(double), hipMemcpyDeviceToHost));
+        FRISK_HIP_CHECK(hipDeviceSynchronize());
         return 0;
     }
 };
 
 }  // namespace frisk_tsne_impl
 
-#undef TSNE_CHECK

@@ -226,18 +226,9 @@ TSNE_ITERATIONS = 1000              # tsne.py max_iter
 TSNE_MAX_N = 50000                  # the dense n x n affinities: 20 GB at the cap
 
 
-class TSNE:
-    """A t-SNE run on the GPU (frisk_tsne_*): X (n x f, f <= 64) already reduced, Y0 (n x dims) the start.  The state stays on
-    the device between calls; use as a context manager (or call close())."""
-
-    def __init__(self, X, Y0, perplexity=20.0, device=0):
-        X, Y0 = _f64(X, 2), _f64(Y0, 2)
-        if X.shape[0] != Y0.shape[0]:
-            raise ValueError("X has %d rows, Y0 %d" % (X.shape[0], Y0.shape[0]))
-        self.n, self.f = X.shape
-        self.dims = Y0.shape[1]
-        self._h = C.c_void_p()
-        _call("frisk_tsne_create", device, _ptr(X), self.n, self.f, float(perplexity), self.dims, _ptr(Y0), C.byref(self._h))
+class _Handle:
+    """A device-side handle of the library (self._h, made by the subclass's frisk_*_create): a context manager that destroys it once."""
+    _destroy = None
 
     def __enter__(self):
         return self
@@ -247,8 +238,24 @@ class TSNE:
 
     def close(self):
         if self._h:
-            _ffi.lib().frisk_tsne_destroy(self._h)
+            getattr(_ffi.lib(), self._destroy)(self._h)
             self._h = C.c_void_p()
+
+
+class TSNE(_Handle):
+    """A t-SNE run on the GPU (frisk_tsne_*): X (n x f, f <= 64) already reduced, Y0 (n x dims) the start.  The state stays on
+    the device between calls; use as a context manager (or call close())."""
+
+    _destroy = "frisk_tsne_destroy"
+
+    def __init__(self, X, Y0, perplexity=20.0, device=0):
+        X, Y0 = _f64(X, 2), _f64(Y0, 2)
+        if X.shape[0] != Y0.shape[0]:
+            raise ValueError("X has %d rows, Y0 %d" % (X.shape[0], Y0.shape[0]))
+        self.n, self.f = X.shape
+        self.dims = Y0.shape[1]
+        self._h = C.c_void_p()
+        _call("frisk_tsne_create", device, _ptr(X), self.n, self.f, float(perplexity), self.dims, _ptr(Y0), C.byref(self._h))
 
     def affinities(self, q=False):
         """(beta, tries) of every row, plus the n x n q = max(normalised symmetric P, 1e-12 / 4) when q is True."""
@@ -326,9 +333,11 @@ def tsne(X, dims=2, perplexity=20.0, seed=0, initial_dims=50, device=0, log=None
 
 
 # ------------------------------------------------------------------------------------------------ MDS
-class MDS:
+class MDS(_Handle):
     """Metric MDS on the GPU (frisk_mds_*): the dissimilarities of X (n x f, any f >= 1) stay on the device, and each run() is one
     SMACOF start against them.  Use as a context manager (or call close())."""
+
+    _destroy = "frisk_mds_destroy"
 
     def __init__(self, X, dims=2, device=0):
         X = _f64(X, 2)
@@ -336,17 +345,6 @@ class MDS:
         self.dims = int(dims)
         self._h = C.c_void_p()
         _call("frisk_mds_create", device, _ptr(X), self.n, self.f, self.dims, C.byref(self._h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _ffi.lib().frisk_mds_destroy(self._h)
-            self._h = C.c_void_p()
 
     def dissimilarities(self):
         """The n x n D (direct-difference Euclidean distances of the rows of X)."""
@@ -417,13 +415,15 @@ def gen_batches(n, batch_size, min_batch_size=0):
     return out
 
 
-class IncrementalPCA:
+class IncrementalPCA(_Handle):
     """sklearn's IncrementalPCA(n_components=dims, whiten=False) on the GPU (frisk_ipca_*): the fit (rows seen, mean, variance,
     singular values, components) stays on the device between partial_fit calls, so X is only ever needed one batch at a time.
     Per batch the device computes sklearn's mean / variance update and the Gram matrix G = AT A of sklearn's stacked matrix A;
     the right singular vectors of A are the eigenvectors of G (one f x f torch.linalg.eigh on the same device, as pca()), the
     top `dims` in descending order with sklearn's sign rule.  Because only `dims` components survive each batch, a fit of more
     than one batch is not the PCA of X.  Use as a context manager (or call close())."""
+
+    _destroy = "frisk_ipca_destroy"
 
     def __init__(self, f, dims, device=0):
         self.f, self.dims, self.device = int(f), int(dims), device
@@ -435,17 +435,6 @@ class IncrementalPCA:
         self.n_samples_seen_ = 0
         self.explained_variance_ = self.explained_variance_ratio_ = self.noise_variance_ = None
         self.timings = {"stats_ms": 0.0, "gram_ms": 0.0, "eigh_ms": 0.0}       # of the last partial_fit
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _ffi.lib().frisk_ipca_destroy(self._h)
-            self._h = C.c_void_p()
 
     def state(self):
         """(n_samples_seen_, mean_, var_, singular_values_, components_) of the fit on the device; the arrays are None before
@@ -577,10 +566,12 @@ NMF_MAX_DIMS, NMF_MAX_P = 16, 26        # components; columns of one product (d 
 NMF_OVERSAMPLES, NMF_INIT_EPS = 10, 1e-6
 
 
-class NMF:
+class NMF(_Handle):
     """An NMF problem on the GPU (frisk_nmf_*): X (n x f, non-negative) stays on the device with W (n x dims) and H (dims x f).
     The caller drives the iterations: step() is one pass of sklearn's coordinate descent and returns its violation.  Use as a
     context manager (or call close())."""
+
+    _destroy = "frisk_nmf_destroy"
 
     def __init__(self, X, dims=2, device=0):
         X = _f64(X, 2)
@@ -588,17 +579,6 @@ class NMF:
         self.dims = int(dims)
         self._h = C.c_void_p()
         _call("frisk_nmf_create", device, _ptr(X), self.n, self.f, self.dims, C.byref(self._h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _ffi.lib().frisk_nmf_destroy(self._h)
-            self._h = C.c_void_p()
 
     def xq(self, Q):
         """X Q for Q (f x p, p <= 26)."""

@@ -18,6 +18,7 @@ def declared_symbols():
 
 def test_library_exports_every_declared_symbol():
     import __graft_entry__ as g
+    assert sorted(g.HIP_SOURCES) == sorted(f for f in os.listdir(g.CSRC) if f.endswith(".hip")), "a unit that build_hip does not compile"
     g.build_hip()
     from frisk_amd import _ffi
     lib = _ffi.lib()

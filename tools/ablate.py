@@ -7,7 +7,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "frisk_amd", "csrc")
+sys.path.insert(0, ROOT)
+from __graft_entry__ import build_hip
 OUT = os.path.join(ROOT, "gpurun_out", "ablate")
 
 CHILD_K = int(os.environ.get("ABLATE_K", "8"))
@@ -33,9 +34,7 @@ def main():
     for spec in sys.argv[1:]:
         defs = ["-D" + d for d in spec.split(",")]
         lib = os.path.join(OUT, "lib_%s.so" % spec.replace(",", "_").replace("=", ""))
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC",
-                        "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", lib,
-                        os.path.join(CSRC, "frisk_abi.hip"), "-lz"] + defs, check=True)
+        build_hip(force=True, extra_flags=defs, out=lib)
         env = dict(os.environ, FRISK_HIP_LIB=lib)
         out = subprocess.run([sys.executable, "-c", CHILD % (ROOT, scale, CHILD_K, float(os.environ.get("ABLATE_LOWER", "0")), float(os.environ.get("ABLATE_REPEATS", "0")))], env=env, capture_output=True, text=True)
         print(spec, out.stdout.strip().splitlines()[-1] if out.stdout.strip() else out.stderr[-500:], flush=True)

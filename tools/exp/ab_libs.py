@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""(GPU) same-box A/B of two builds of the library: usage ab_libs.py <srcdirA> <srcdirB> [rounds] - each dir holds frisk_amd/csrc and include;
-builds both, then times the bench shard's scan (HIP events, best of 5) with each in turn, `rounds` times."""
+"""(GPU) same-box A/B of two builds of the library: usage ab_libs.py <A> <B> [rounds] - each a checkout (built here by its own
+__graft_entry__.build_hip, whatever its list of units) or a library built before; then times the bench shard's scan (HIP events, best of 5) with each in turn, `rounds` times."""
 import os, subprocess, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(ROOT, "gpurun_out", "ablate"); os.makedirs(OUT, exist_ok=True)
@@ -19,10 +19,11 @@ print(json.dumps({"scan_ms_best": round(min(ts), 4), "scan_ms_last3": [round(t, 
 ''' % ROOT
 libs = []
 for i, d in enumerate(sys.argv[1:3]):
-    lib = os.path.join(OUT, "lib_ab%d.so" % i)
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", "-Wno-pass-failed",
-                    "-I" + os.path.join(d, "include"), "-I" + os.path.join(d, "frisk_amd", "csrc"), "-o", lib,
-                    os.path.join(d, "frisk_amd", "csrc", "frisk_abi.hip"), "-lz"], check=True, stderr=subprocess.DEVNULL)
+    lib = os.path.abspath(d)
+    if os.path.isdir(d):
+        lib = os.path.join(OUT, "lib_ab%d.so" % i)
+        subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; g.build_hip(force=True, out=%r)" % lib], cwd=d, check=True,
+                       stderr=subprocess.DEVNULL)
     libs.append(lib)
 for rnd in range(int(sys.argv[3]) if len(sys.argv) > 3 else 3):
     for name, lib in zip("AB", libs):

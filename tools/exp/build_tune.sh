@@ -1,8 +1,8 @@
 #!/bin/bash
 # usage: build_tune.sh <out.so> [extra -D flags...]
 out=$1; shift
-cd /root/repo
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -shared -fPIC -ffp-contract=off -Wno-pass-failed -DFRISK_TUNE "$@" -Iinclude -Ifrisk_amd/csrc -Rpass-analysis=kernel-resource-usage -o $out frisk_amd/csrc/frisk_abi.hip -lz 2> ${out%.so}.res.txt
+cd "$(dirname "$0")/../.."
+python3 -c "import sys, __graft_entry__ as g; g.build_hip(force=True, extra_flags=['-DFRISK_TUNE'] + sys.argv[2:] + ['-Rpass-analysis=kernel-resource-usage'], out=sys.argv[1])" "$out" "$@" 2> ${out%.so}.res.txt
 rc=$?
 grep -E "error" ${out%.so}.res.txt | head
 python3 - "${out%.so}.res.txt" <<'PY'

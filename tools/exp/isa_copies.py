@@ -1,21 +1,22 @@
 #!/usr/bin/env python3
-"""(CPU) device assembly of the library; for the K = 8 / 4-bit bulk kernels (plain and SIDE) the copies of the scoring loop:
+"""(CPU) device assembly of the unit that holds the 4-bit narrow-counter kernels (scan8_launch4.hip); for the K = 8 / 4-bit bulk kernels (plain and SIDE) the copies of the scoring loop:
 instructions per position and scratch accesses in each.  Usage: python tools/exp/isa_copies.py [extra -D flags]
 (--asm FILE: read that device assembly instead of compiling.)  Behind the runs of positions, the straight-line copies one by one: every
 basic block that scores at least half a lane's positions (the unrolled copies of the K = 8 scoring loop are one block each), with its
 instruction counts by kind for the whole block."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import HIPCC, HIP_FLAGS, CSRC
 os.makedirs(os.path.join(ROOT, "build/isa"), exist_ok=True)
-asm = os.path.join(ROOT, "build/isa/abi.s")
+asm = os.path.join(ROOT, "build/isa/scan8_launch4.s")
 flags = sys.argv[1:]
 given = flags.index("--asm") if "--asm" in flags else -1
 if given >= 0:
     asm, flags = flags[given + 1], flags[:given] + flags[given + 2:]
 else:
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-pass-failed"] + flags +
-                   ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "frisk_amd/csrc"), "--cuda-device-only", "-S", "-o", asm,
-                    os.path.join(ROOT, "frisk_amd/csrc/frisk_abi.hip")], check=True, stderr=subprocess.DEVNULL)
+    subprocess.run([HIPCC] + HIP_FLAGS + flags + ["--cuda-device-only", "-S", "-o", asm, os.path.join(CSRC, "scan8_launch4.hip")],
+                   check=True, stderr=subprocess.DEVNULL)
 L = open(asm).read().split('\n')
 for tag, kern in (('plain', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb0EEv10ScanParams'),
                   ('side', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb1EEv10ScanParams')):

@@ -1,17 +1,21 @@
 #!/bin/bash
-# usage: isa_count.sh [extra -D flags...]   (CPU) - device assembly of the library's translation unit; prints, for the K = 8 / 4-bit
-# bulk kernel, the VALU / SALU / LDS / VMEM instruction counts between consecutive barriers (stage 4 is the long segment)
+# usage: isa_count.sh [extra -D flags...]   (CPU, from the repository root) - device assembly of the two narrow-counter units; prints, for
+# the K = 8 4-bit and 8-bit bulk kernels, the VALU / SALU / LDS / VMEM instruction counts between consecutive barriers (stage 4 is the long segment)
 mkdir -p build/isa
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -Wno-pass-failed "$@" -Iinclude -Ifrisk_amd/csrc \
-    --cuda-device-only -S -o build/isa/abi.s frisk_amd/csrc/frisk_abi.hip 2>/dev/null
+flags=$(python3 -c "import __graft_entry__ as g; print(' '.join(g.HIP_FLAGS))")
+for u in scan8_launch4 scan8_launch; do
+    /opt/rocm/bin/hipcc $flags "$@" --cuda-device-only -S -o build/isa/$u.s frisk_amd/csrc/$u.hip 2>/dev/null &
+done
+wait
+cat build/isa/scan8_launch4.s build/isa/scan8_launch.s > build/isa/abi.s
 python3 - <<'PY'
 import re
-L=open('/root/repo/build/isa/abi.s').read().split('\n')
-for kern in ('_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0EEv10ScanParams', '_Z12scan8_kernelILi8ELi256ELi20ELi8ELi64ELi2ELb0ELi0EEv10ScanParams'):
+L=open('build/isa/abi.s').read().split('\n')
+for kern in ('_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb0EEv10ScanParams', '_Z12scan8_kernelILi8ELi256ELi20ELi8ELi64ELi2ELb0ELi0ELb0EEv10ScanParams'):
     a=next(i for i,l in enumerate(L) if l.startswith(kern+':'))
     b=next(i for i in range(a,len(L)) if 's_endpgm' in L[i])
     K=L[a:b]
-    open('/root/repo/build/isa/'+('k4.s' if 'ELi4ELi64' in kern else 'k8.s'),'w').write('\n'.join(K))
+    open('build/isa/'+('k4.s' if 'ELi4ELi64' in kern else 'k8.s'),'w').write('\n'.join(K))
     bars=[i for i,l in enumerate(K) if 's_barrier' in l]+[len(K)]
     prev=0
     print(kern[:60], 'lines', len(K))
@@ -25,7 +29,7 @@ python3 - <<'PY'
 import re
 # the scoring loop's three copies (orphan list in LDS / <= 4 entries / <= 2): VALU per position in each
 for f in ('k4.s','k8.s'):
-    K=open('/root/repo/build/isa/'+f).read().split('\n')
+    K=open('build/isa/'+f).read().split('\n')
     bars=[i for i,l in enumerate(K) if 's_barrier' in l]
     seg=max(zip(bars,bars[1:]), key=lambda ab: ab[1]-ab[0])
     r=[i for i in range(*seg) if 'v_rcp_f64' in K[i]]
