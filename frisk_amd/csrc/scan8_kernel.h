@@ -38,6 +38,7 @@
 #pragma once
 #include "scan_kernel.h"
 #include "ring_rows.h"              // FRISK8_RING_COLS and the ring's address arithmetic (no HIP there: checked on a CPU as well)
+#include "win_step.h"               // a window's geometry, afresh and from its predecessor; stage 1's sequence addressing (no HIP either)
 
 #define FRISK8_ORPH_CAP 24         // orphan entries kept in LDS (two per invalid run); a window with more goes to the 16-bit form
 #define FRISK8_UNROLL1 2           // unroll factor of the stage-1 position loop
@@ -287,24 +288,13 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     bool ring_next = false;             // ... and so is the ring: the window before this one went through the scoring loop (a window
                                         // that the N filter drops, or that is handed on, parks nothing - its successor gathers afresh)
 
-    // candidate `cand` of the descriptor in `d`: first base, reported coordinates, length (crawlGenome L211-245)
-    auto window_of = [&](int64_t cand, int64_t& st, int64_t& rep_start, int64_t& rep_stop, int& n, bool& jump) {
-        const int64_t j = cand - d.cand0 + d.j0;               // window index inside the scaffold
-        jump = false;
-        if (d.kind == 1) { st = 0; n = int(d.size); rep_start = 1; rep_stop = d.size; }      // L219
-        else {
-            st = j * P.inc;
-            n = P.w;
-            rep_start = st + 1; rep_stop = st + P.w;                                        // L245
-            if (st + P.w > d.size) {                                                        // L230-232
-                jump = true;
-                st = d.size - P.w;
-                rep_start = st; rep_stop = d.size;                                          // L243: 0-based start
-                if (st < 0) { st += d.size; if (st < 0) st = 0; }                           // negative slice start
-                n = int(d.size - st);
-            }
-        }
-    };
+    // THE WINDOW'S GEOMETRY (win_step.h): first base, reported coordinates, length, resident position, place in the ring.  A window
+    // that slides is its predecessor moved on by inc: win_next adds; every other window - the first of a chunk, after a scaffold's
+    // end, a jump-back tail, a whole-scaffold window, a listed one - is computed from its candidate index by win_fresh (crawlGenome
+    // L211-245), with its multiplies, its 64-bit modulo for the ring and the search of the descriptor in front.  Carried from window
+    // to window: st, g0 and the ring's row and column - the rest follows from them.
+    WinGeom wg;
+    wg.st = 0; wg.rep_start = 0; wg.rep_stop = 0; wg.g0 = 0; wg.n = 0; wg.jump = false; wg.rb_q = 0; wg.rb_r = 0;
     // Chunks are dealt by counters when the launcher provides them: a workgroup takes the next chunk when it is done with
     // its last.  Chunks differ a lot in cost (windows that the N filter drops stop after stage 2), and with the static deal -
     // chunk v, v + G, v + 2 G ... - a launch ended with 8 % of its time spent waiting for the unluckiest workgroups.  One
@@ -354,7 +344,9 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
         for (int64_t ci = cb; ci < ce; ++ci) {
             const int64_t cand = listed ? Pk->in_list[ci] : ci;
             // ---- which scaffold / window is this candidate? (uniform; crawlGenome L194-251)
-            if (cand < d.cand0 || cand >= d.cand0 + d.ncand) {
+            // (a window that slides sits in its predecessor's scaffold: slide_next said so)
+            const bool sliding = slide_next;
+            if (!sliding && (cand < d.cand0 || cand >= d.cand0 + d.ncand)) {
                 int lo = 0, hi = P.n_desc - 1;
                 while (lo < hi) {
                     const int mid = (lo + hi + 1) >> 1;
@@ -378,17 +370,18 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             asm volatile("" : "+v"(tid), "+s"(kmin));
             asm volatile("" : "+s"(Pk));            // (kernel arguments used once per window: re-read from their segment, see Pk)
             const int lane = tid & 63;
-            int64_t st, rep_start, rep_stop;
-            int n;
-            bool jump = false;
-            window_of(cand, st, rep_start, rep_stop, n, jump);
-            const int64_t g0 = d.off + (st - d.base0);            // resident position of the window's first base
+            const WinScaf ws = {d.off, d.size, d.base0, d.cand0, d.ncand, d.j0, d.kind};
+            if (sliding) wg = win_next<ITS, FRISK8_RING_COLS>(wg, win_inc<ITS>(P.inc), P.w);
+            else wg = win_fresh<ITS, FRISK8_RING_COLS>(ws, cand, P.w, P.inc);
+            const int64_t st = wg.st, rep_start = wg.rep_start, rep_stop = wg.rep_stop;
+            const int n = wg.n;
+            const bool jump = wg.jump;
+            const int64_t g0 = wg.g0;                             // resident position of the window's first base
             const int64_t row = cand - P.c0;
             // this window slides into the table its predecessor left; its successor - the next candidate of this chunk, in the
             // same scaffold, a full window like this one (no jumpback, L230-232) - will slide into this one's
             // where the window's first base sits in the ring: row rb_r, column rb_q (uniform)
-            const uint32_t ring_base = RING ? uint32_t(uint64_t(st) % uint64_t(ITS * FRISK8_RING_COLS)) : 0u;
-            const uint32_t rb_q = ring_base / uint32_t(ITS), rb_r = ring_base - rb_q * uint32_t(ITS);
+            const uint32_t rb_q = RING ? wg.rb_q : 0u, rb_r = RING ? wg.rb_r : 0u;
             // WHICH positions a lane holds.  Block b = positions [b ITS, (b + 1) ITS) of the window; lane t holds block t.  Dealing
             // the blocks to the four waves in groups of sixteen instead (round 4, FRISK8_DEAL at c34d7fb: measured and NOT taken) - wave
             // w holds the groups w, w + 4, w + 8, w + 12 - shares the entering range of a slid window (the lanes that gather from the
@@ -429,13 +422,11 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             typedef const __attribute__((address_space(1))) double* GlobalDouble;
             GlobalBytes row0_base = ROWS ? (GlobalBytes)(ring + slice_off + ring_row0_base_row(0) * FRISK8_RING_ROW_BYTES) : nullptr;          // (uniform) rows 0..3 at -4096 .. +2048
             const uint32_t row0_lane = ROWS ? ring_off_row0(slice_off, rb_q, uint32_t(tid), 0) : 0u;      // the lane's offset of row 0 from the buffer's base
-            const bool sliding = slide_next;
             // this lane gathers its positions' genome-side values from the table (and parks them in the ring): every lane of a
             // window counted afresh, the lanes that hold a position of the entering range in a window slid into
             const bool lane_new = !sliding || !ring_next || tid * ITS + (ITS - 1) >= P.w - (K - 1) - P.inc;
             ring_next = false;                                  // (true again where this window's scoring loop has run)
-            slide_next = slide_pp > 0 && ci + 1 < ce && d.kind == 0 && !jump && cand + 1 < d.cand0 + d.ncand &&
-                         st + int64_t(P.inc) + P.w <= d.size;
+            slide_next = slide_pp > 0 && ci + 1 < ce && win_has_next(ws, wg, cand, P.w, P.inc);
             if (n > NT * ITS) {
                 // a rescued small scaffold (--scaffoldsAll, L211-221: up to 1.75 w bases) longer than this kernel's lanes cover:
                 // straight to the wider forms - per WINDOW, so that which kernel scores a window never depends on what else
@@ -449,14 +440,19 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
 
             // ---- stage 1: one pass over the window's positions (a lane owns ITS consecutive ones) -----------
             const int j0 = tid * ITS;
-            const int64_t gl = g0 + (j0 < n ? j0 : 0);                       // clamped: loads are unconditional
-            const int64_t wi = gl >> 4, mi = gl >> 5;
-            const int shc = 32 - int(gl & 15) * 2, shm = 32 - int(gl & 31);
+            // (the lane's 32 bases start at g0 + j0 - clamped: loads are unconditional.  The 64-bit part of that - the word that holds
+            //  g0 - is uniform and becomes the loads' scalar base; the lane's word and shifts are 32-bit arithmetic: win_step.h)
+            const SeqBase sb = seq_base(g0);
+            const SeqLane sl = seq_lane(sb, uint32_t(j0 < n ? j0 : 0));
+            const uint32_t* const codes_w = P.codes + 2 * sb.word;
+            const uint32_t* const inv_w = P.inv + sb.word;
+            const uint32_t* const low_w = P.low + sb.word;
+            const int shc = sl.shc, shm = sl.shm;
             // (requesting the NEXT window's words after stage 4, to have them in registers here: measured +-0 at K = 8, -2 % at
             //  K = 6, 7 - with three or four workgroups per CU the other windows' waves already cover these two round trips)
             // (all seven words requested before the first is used: one round trip to L2 / HBM, not two)
-            const uint32_t w0 = P.codes[wi], w1 = P.codes[wi + 1], w2 = P.codes[wi + 2];
-            const uint32_t i0 = P.inv[mi], i1 = P.inv[mi + 1], l0 = P.low[mi], l1 = P.low[mi + 1];
+            const uint32_t w0 = codes_w[sl.cw], w1 = codes_w[sl.cw + 1u], w2 = codes_w[sl.cw + 2u];
+            const uint32_t i0 = inv_w[sl.mw], i1 = inv_w[sl.mw + 1u], l0 = low_w[sl.mw], l1 = low_w[sl.mw + 1u];
             // sliding: the thread's slide_pp positions of the range that leaves (the predecessor's first inc positions) and of
             // the range that enters (the inc positions before this window's last K - 1), requested with the words above
             uint64_t scode = 0, ecode = 0;              // 32 bases from the thread's first position of either range
@@ -464,11 +460,17 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             if (sliding) {
                 const int q0 = tid * slide_pp;
                 const int cnt = P.inc - q0;             // the thread's positions: min(cnt, slide_pp), none if <= 0
-                const int64_t gs = g0 - P.inc + (cnt > 0 ? q0 : 0);
-                const int64_t ge = g0 + (P.w - (K - 1) - P.inc) + (cnt > 0 ? q0 : 0);
-                const int64_t swi = gs >> 4, smi = gs >> 5, ewi = ge >> 4, emi = ge >> 5;
-                const uint32_t s0 = P.codes[swi], s1 = P.codes[swi + 1], s2 = P.codes[swi + 2], si0 = P.inv[smi], si1 = P.inv[smi + 1];
-                const uint32_t e0 = P.codes[ewi], e1 = P.codes[ewi + 1], e2 = P.codes[ewi + 2], ei0 = P.inv[emi], ei1 = P.inv[emi + 1];
+                // (the two ranges start at g0 - inc - the predecessor's first base - and at g0 + w - (K - 1) - inc: uniform bases, the
+                //  lane's offset into either range on top, as above)
+                const uint32_t so = uint32_t(cnt > 0 ? q0 : 0);
+                const SeqBase bs = seq_base(g0 - P.inc), be = seq_base(g0 + (P.w - (K - 1) - P.inc));
+                const SeqLane ls = seq_lane(bs, so), le = seq_lane(be, so);
+                const uint32_t* const scw = P.codes + 2 * bs.word;
+                const uint32_t* const siw = P.inv + bs.word;
+                const uint32_t* const ecw = P.codes + 2 * be.word;
+                const uint32_t* const eiw = P.inv + be.word;
+                const uint32_t s0 = scw[ls.cw], s1 = scw[ls.cw + 1u], s2 = scw[ls.cw + 2u], si0 = siw[ls.mw], si1 = siw[ls.mw + 1u];
+                const uint32_t e0 = ecw[le.cw], e1 = ecw[le.cw + 1u], e2 = ecw[le.cw + 2u], ei0 = eiw[le.mw], ei1 = eiw[le.mw + 1u];
                 auto funnel = [](uint32_t a, uint32_t b, uint32_t c, int sh) -> uint64_t {
                     return (uint64_t(uint32_t(((uint64_t(a) << 32) | b) >> sh)) << 32) | uint32_t(((uint64_t(b) << 32) | c) >> sh);
                 };
@@ -479,10 +481,10 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     const int m = cnt_ < pp ? cnt_ : pp;
                     return m > 0 ? f & uint32_t(0xFFFFFFFF00000000ull >> m) : 0u;
                 };
-                scode = funnel(s0, s1, s2, 32 - int(gs & 15) * 2);
-                ecode = funnel(e0, e1, e2, 32 - int(ge & 15) * 2);
-                sfull = starts(uint32_t(((uint64_t(si0) << 32) | si1) >> (32 - int(gs & 31))), cnt, slide_pp);
-                efull = starts(uint32_t(((uint64_t(ei0) << 32) | ei1) >> (32 - int(ge & 31))), cnt, slide_pp);
+                scode = funnel(s0, s1, s2, ls.shc);
+                ecode = funnel(e0, e1, e2, le.shc);
+                sfull = starts(uint32_t(((uint64_t(si0) << 32) | si1) >> ls.shm), cnt, slide_pp);
+                efull = starts(uint32_t(((uint64_t(ei0) << 32) | ei1) >> le.shm), cnt, slide_pp);
             }
             const uint32_t chi = uint32_t(((uint64_t(w0) << 32) | w1) >> shc);
             const uint32_t clo = uint32_t(((uint64_t(w1) << 32) | w2) >> shc);

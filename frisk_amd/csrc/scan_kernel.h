@@ -190,10 +190,16 @@ __device__ inline double div_exact(double n, double d) {
 // WAVE0_ONLY: only the first wave adds up the per-wave partials (the others return garbage): the caller's scalar tail -
 // two logarithms and a division - then costs one wave's instructions per window instead of every wave's.
 // x + (x of another lane of the same row of 16, chosen by a DPP control): one register move per 32-bit half
+// (CTRL: one of the four controls of wave_sum_exact, row and bank masks 0xF - every lane has a source lane inside its row, so the
+//  move's `old` operand is never read: left undefined.  PRECONDITION: all 64 lanes of the wave are active - a lane whose source lane
+//  is switched off by EXEC would keep `old`, i.e. garbage.  Every caller - wave_sum_exact in scan8_kernel.h's row sums, and through
+//  block_sum3 in scan_kernel.h and scan_big_kernel.h - sums workgroup-uniformly in front of a barrier, with full waves.  A zero `old`
+//  cost a v_mov_b32 in front of every v_mov_b32_dpp: 24 per wave and window in scan8_kernel.h.  The 32-bit sums - dpp_addu - keep their zero: with it v_mov_b32_dpp + v_add_u32 fold into one v_add_u32_dpp.)
 template <int CTRL>
 __device__ inline double dpp_add(double x) {
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, false);
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, false);
+    static_assert(CTRL == 0xB1 || CTRL == 0x4E || CTRL == 0x141 || CTRL == 0x140, "a permutation inside the row: no lane without a source");
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xF, 0xF, false);
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xF, 0xF, false);
     return x + __hiloint2double(hi, lo);
 }
 
