@@ -723,7 +723,8 @@ def nmf(X, dims, seed=0, tol=NMF_TOL, max_iter=NMF_MAX_ITER, device=0):
     """sklearn's NMF(n_components=dims, init=None, solver='cd', tol, max_iter, shuffle=False, random_state=seed).fit(X)
     .transform(X) (L1632-1636).  The start is sklearn's (nmf_init); every iteration of the fit and of the transform (W from zeros,
     H fixed) is one step on the GPU, the stop rule evaluated on the host in double.  Clustering this projection is not offered by
-    the CLI yet (cli.PROJECTIONS_UNCLUSTERED)."""
+    the CLI yet (cli.PROJECTIONS_UNCLUSTERED).  Components that come out of the fit all zero (an all-zero X) raise the ValueError of
+    sklearn's transform."""
     X = _f64(X, 2)
     n, f = X.shape
     dims = int(dims)
@@ -743,6 +744,8 @@ def nmf(X, dims, seed=0, tol=NMF_TOL, max_iter=NMF_MAX_ITER, device=0):
             logging.getLogger(__name__).warning("NMF: maximum number of iterations %d reached. Increase it to improve "
                                                 "convergence.", max_iter)
         _W, H = h.get()
+        if not H.any():                                 # sklearn's transform: _check_init(H, ..., "NMF (input H)")
+            raise ValueError("Array passed to NMF (input H) is full of zeros.")
         t2 = time.perf_counter()
         h.set(W=np.zeros((n, dims)))
         h.transform_prepare()

@@ -34,12 +34,13 @@ LD = np.longdouble
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def golden():
-    return json.load(open(os.path.join(GOLD, "nmf.json")))
+def golden(table="nmf"):
+    """tests/golden/nmf.json, or with table = "nmf_edges" the second table (tools/make_golden_nmf.py --edges)."""
+    return json.load(open(os.path.join(GOLD, table + ".json")))
 
 
 def arrays(g, case):
-    return np.load(os.path.join(GOLD, "nmf", g["cases"][case]["file"]))
+    return np.load(os.path.join(GOLD, g.get("dir", "nmf"), g["cases"][case]["file"]))
 
 
 def gamma(k):
@@ -48,18 +49,30 @@ def gamma(k):
 
 def make_X(spec):
     """Dirichlet-multinomial rows as tools/make_golden_nmf.py draws them (legacy RandomState streams are frozen): per block of
-    `orders` a Dirichlet centre, per row a Dirichlet around it and a multinomial of `depth` draws, turned into proportions."""
+    `orders` a Dirichlet centre, per row a Dirichlet around it and a multinomial of `depth` draws, turned into proportions.
+    Optional fields of the second table: "distinct" (only that many rows are drawn; the n rows are then picked among them, each
+    at least once), "rank1" (the rows are the concatenated centres times a factor in [0.5, 1.5) each: an outer product), "absent"
+    ({"cols": [...], "rows": [...]}, set to zero at the end: k-mers no window contains, and an empty row)."""
     rs = np.random.RandomState(spec["seed"])
     centre = [rs.dirichlet(np.full(w, 2.0)) for w in spec["orders"]]
     rows = []
-    for _ in range(spec["n"]):
+    for _ in range(spec.get("distinct", 0 if spec.get("rank1") else spec["n"])):
         parts = []
         for c in centre:
             pr = rs.dirichlet(c * spec["spread"] + 1e-3)
             k = rs.multinomial(spec["depth"], pr)
             parts.append(k / float(k.sum()))
         rows.append(np.concatenate(parts))
-    return np.array(rows)
+    X = np.array(rows)
+    if "distinct" in spec:
+        m = spec["distinct"]
+        X = X[np.concatenate([np.arange(m), rs.randint(m, size=spec["n"] - m)])[rs.permutation(spec["n"])]]
+    if spec.get("rank1"):
+        X = (0.5 + rs.random_sample(spec["n"]))[:, None] * np.concatenate(centre)[None, :]
+    if "absent" in spec:
+        X[:, spec["absent"]["cols"]] = 0.0
+        X[spec["absent"]["rows"], :] = 0.0
+    return X
 
 
 # ------------------------------------------------------------------------------------------------ products
@@ -144,9 +157,10 @@ def initialize(X, d, seed, how="blas"):
 
 
 # ------------------------------------------------------------------------------------------------ one step
-def sweep(W, G, P, eG=None, eP=None, pre=None):
+def sweep(W, G, P, eG=None, eP=None, pre=None, grad=None):
     """_update_cdnmf_fast(W, HHt = G, XHt = P, identity) on a copy, every row at once, in the dtype of the inputs.  Returns
-    (W', violation) or, with the input bounds eG and eP, (W', violation, dW bound, violation bound).  pre, an m x d array, receives every entry before its max(., 0)."""
+    (W', violation) or, with the input bounds eG and eP, (W', violation, dW bound, violation bound).  pre, an m x d array, receives every entry before its max(., 0)
+    (columns with a zero Hessian are left as they come); grad, m x d, every entry's gradient g."""
     W = W.copy()
     m, d = W.shape
     bound = eG is not None
@@ -158,6 +172,8 @@ def sweep(W, G, P, eG=None, eP=None, pre=None):
             g = g + G[t, r] * W[:, r]
         pg = np.where(W[:, t] == 0, np.minimum(0, g), g)
         viol = viol + np.abs(pg).sum()
+        if grad is not None:
+            grad[:, t] = g
         if bound:
             aW = np.abs(W).astype(np.float64)
             aG = np.abs(G[t]).astype(np.float64)
@@ -178,16 +194,23 @@ def sweep(W, G, P, eG=None, eP=None, pre=None):
     return W, viol
 
 
-def step(X, W, H, update_H=True, how="blas"):
+def step(X, W, H, update_H=True, how="blas", aux=None):
     """One iteration of _fit_coordinate_descent from (W, H): (W', H', violation).  how = "ld" computes everything in long
-    double and returns long doubles."""
+    double and returns long doubles.  aux, a dict, receives sweep's pre and grad of the W sweep ("preW", "gradW", n x d, pre
+    starting from W) and, with update_H, of the H sweep ("preH", "gradH", d x f)."""
     if how == "ld":
         X, W, H = (np.asarray(a, dtype=LD) for a in (X, W, H))
     Ht = np.ascontiguousarray(H.T)
-    W1, v = sweep(W, product(Ht.T, Ht, how), product(X, Ht, how))
+    pre, grad = (W.copy(), np.zeros_like(W)) if aux is not None else (None, None)
+    W1, v = sweep(W, product(Ht.T, Ht, how), product(X, Ht, how), pre=pre, grad=grad)
+    if aux is not None:
+        aux.update(preW=pre, gradW=grad)
     if not update_H:
         return W1, H.copy(), v
-    Ht1, v2 = sweep(Ht, product(W1.T, W1, how), product(X.T, W1, how))
+    pre, grad = (Ht.copy(), np.zeros_like(Ht)) if aux is not None else (None, None)
+    Ht1, v2 = sweep(Ht, product(W1.T, W1, how), product(X.T, W1, how), pre=pre, grad=grad)
+    if aux is not None:
+        aux.update(preH=np.ascontiguousarray(pre.T), gradH=np.ascontiguousarray(grad.T))
     return W1, np.ascontiguousarray(Ht1.T), v + v2
 
 
