@@ -111,6 +111,13 @@ SYMBOLS = [
     ("frisk_nmf_transform_prepare", C.c_int, [_P]),
     ("frisk_nmf_last_ms", C.c_double, [_P, C.c_int]),
     ("frisk_nmf_destroy", None, [_P]),
+    ("frisk_spectral_create", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, C.c_double, C.POINTER(_P)]),
+    ("frisk_spectral_affinity", C.c_int, [_P, _P]),
+    ("frisk_spectral_degrees", C.c_int, [_P, _P, _I64P]),
+    ("frisk_spectral_matrix", C.c_int, [_P, _P]),
+    ("frisk_spectral_mq", C.c_int, [_P, _P, C.c_int32, _P]),
+    ("frisk_spectral_last_ms", C.c_double, [_P, C.c_int]),
+    ("frisk_spectral_destroy", None, [_P]),
     ("frisk_host_alloc", C.c_void_p, [_P, C.c_int64]),
     ("frisk_host_free", None, [_P, _P]),
     ("frisk_last_kernel_ms", C.c_double, [_P, C.c_int]),

@@ -21,8 +21,10 @@ records of the annotation whose type is one of --gffFeatures and that lie within
 featuresIn_thresholded_Anomalies_<basename of gffIn>, and with --hmmKLD those near a State1 / State2 interval of the main track to
 featuresIn_hmm_State1_<basename> / featuresIn_hmm_State2_<basename> - `bedtools window -w gffRange -u` restated on the host
 (frisk_amd.postprocess.window_u); a file is written only when it has a record.  Rank 0, not under --exitAfter; no other output changes.
-Out of scope here: the other projection (SKL-TSNE) and SPECTRAL clustering,
---graphics (seaborn/matplotlib).
+--cluster SPECTRAL (sklearn's SpectralClustering: rbf affinities, normalised Laplacian, k-means on the top --kClusters
+eigenvectors, seeded the same way) runs on the GPU after PCA, PY-TSNE, MDS or IncrementalPCA and, with --dumpPCAdata, writes its
+labels as the pickle anomSPECTRAL; it is still reported as unavailable and writes no cluster GFF3 (CLUSTERINGS_UNWRITTEN).
+Out of scope here: the other projection (SKL-TSNE) and --graphics (seaborn/matplotlib).
 Those options are accepted, as in the reference, and reported as unavailable if used.
 
 Run under `python -m torch.distributed.run --nproc-per-node N -m frisk_amd ...` to shard one job over N GPUs
@@ -109,13 +111,16 @@ def build_parser():
 PROJECTIONS = ("PCA", "PY-TSNE", "MDS", "IncrementalPCA")     # --runProjection methods built here (frisk_amd.projection)
 PROJECTIONS_UNCLUSTERED = ("NMF",)      # built here too, but --cluster on them is still reported as unavailable (see unavailable)
 CLUSTERINGS = ("DBSCAN", "KMEANS")      # --cluster methods built here
+CLUSTERINGS_UNWRITTEN = ("SPECTRAL",)   # built here too, but still reported as unavailable and without a cluster GFF3 (see unavailable)
 
 
 def unavailable(args):
     """(option, reason) of every given option this build accepts but does not run.  --cluster runs only as DBSCAN or KMEANS
     after --runProjection PCA, PY-TSNE, MDS or IncrementalPCA (the reference clusters the projection, L1635-1655).  The NMF
     projection runs (PROJECTIONS_UNCLUSTERED), but clustering it is still reported as unavailable and writes no cluster GFF3:
-    tests/test_projection_cluster_cpu.py pins ("NMF", "DBSCAN") to this warning.  Moving "NMF" into PROJECTIONS lifts that."""
+    tests/test_projection_cluster_cpu.py pins ("NMF", "DBSCAN") to this warning.  Moving "NMF" into PROJECTIONS lifts that.
+    --cluster SPECTRAL runs too after one of PROJECTIONS (CLUSTERINGS_UNWRITTEN: its labels are logged and dumped, not written as
+    a GFF3), and the same tests pin it to this warning; moving "SPECTRAL" into CLUSTERINGS lifts the fence."""
     clustering = args.runProjection in PROJECTIONS and args.cluster in CLUSTERINGS
     out = []
     for opt, why in (("cluster", "sklearn clustering is out of scope"), ("graphics", "plotting is out of scope")):
@@ -278,8 +283,8 @@ def _seed(args):
 
 def _project(args, anomCounts, device, clock):
     """--runProjection PCA (L1612-1613), PY-TSNE (L1622-1623), MDS (L1624-1627), IncrementalPCA (L1629-1631) or NMF (L1632-1636) on
-    the anomalies' k-mer proportions, then --cluster DBSCAN / KMEANS on the projection (L1635-1655), except after NMF.  Returns the
-    cluster labels (None without a clustering this build runs)."""
+    the anomalies' k-mer proportions, then --cluster DBSCAN / KMEANS on the projection (L1635-1655), except after NMF; --cluster SPECTRAL
+    runs there too but returns nothing (_spectral).  Returns the cluster labels (None without a clustering whose GFF3 is written)."""
     from . import projection as P
     if args.runProjection == "PY-TSNE":
         n = anomCounts.shape[0]
@@ -326,10 +331,33 @@ def _project(args, anomCounts, device, clock):
         y_pred = P.dbscan(res.Y, args.epsDBSCAN, device=device)
     elif args.cluster == "KMEANS":
         y_pred = P.kmeans(res.Y, args.kClusters, seed=_seed(args), device=device).labels
+    elif args.cluster in CLUSTERINGS_UNWRITTEN:
+        _spectral(args, res.Y, device, clock)
     if y_pred is not None:
         log.info("%s: %s clusters, %s unclassified", args.cluster, len(set(y_pred.tolist()) - {-1}), int(np.sum(y_pred == -1)))
         clock.lap(args.cluster)
     return y_pred
+
+
+def _spectral(args, Y, device, clock):
+    """--cluster SPECTRAL (L1659-1662) on the projection Y: the labels are logged and, with --dumpPCAdata, pickled as anomSPECTRAL
+    beside anomLabels / anomCounts; no cluster GFF3 follows (CLUSTERINGS_UNWRITTEN).  A --kClusters or a number of windows that
+    spectral() refuses is a warning: the run goes on as it did before this clustering was built."""
+    from . import projection as P
+    try:
+        sp = P.spectral(Y, args.kClusters, seed=_seed(args), device=device)
+    except ValueError as err:
+        log.warning("--cluster SPECTRAL skipped: %s", err)
+        return
+    t = sp.timings
+    log.info("SPECTRAL of %s points: cluster sizes %s; eigenvalues %s, %s iterations (residual %.3g), %s isolated; affinity %.1f ms, "
+             "normalise %.1f ms, products %.1f ms (device) + %.1f ms (host), k-means %.1f ms", len(sp.labels),
+             np.bincount(sp.labels).tolist(), sp.eigenvalues.tolist(), sp.n_iter, float(sp.residuals.max()), sp.n_isolated,
+             t["affinity_ms"], t["normalise_ms"], t["products_ms"], t["host_ms"], t["kmeans_ms"])
+    if args.dumpPCAdata:
+        with open(os.path.join(args.tempDir, "anomSPECTRAL"), "wb") as fh:
+            pickle.dump(sp.labels, fh, protocol=2)
+    clock.lap("SPECTRAL")
 
 
 def _gff_features(args, anomalies, intervals):

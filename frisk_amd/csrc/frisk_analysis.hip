@@ -1,5 +1,5 @@
 // frisk_analysis.hip - the entry points of include/frisk_hip.h that take no frisk_ctx: the host HMM, projection and clustering, the
-// device HMM, and the t-SNE, MDS, incremental PCA and NMF handles.  Host arrays in and out, or a small handle of their own; nothing
+// device HMM, and the t-SNE, MDS, incremental PCA, NMF and spectral-clustering handles.  Host arrays in and out, or a small handle of their own; nothing
 // of the scan is included here.  gfx950 (MI355X) only.  Build: see __graft_entry__.build_hip().
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "mds_kernels.h"
 #include "ipca_kernels.h"
 #include "nmf_kernels.h"
+#include "spectral_kernels.h"
 #include "hmm_kernels.h"
 
 namespace {
@@ -29,7 +30,7 @@ int on_device(int device, F&& f) {
     return f() ? FRISK_E_HIP : FRISK_OK;
 }
 
-// The handles (frisk_tsne, frisk_mds, frisk_ipca, frisk_nmf: one State `s` each, which frees its device memory when it is deleted on
+// The handles (frisk_tsne, frisk_mds, frisk_ipca, frisk_nmf, frisk_spectral: one State `s` each, which frees its device memory when it is deleted on
 // its device).  `make` fills the state's shape and allocates: 0, or the handle is dropped.
 template <typename H, typename Make>
 int create_handle(int device, H** out, Make&& make) {
@@ -418,5 +419,47 @@ int frisk_nmf_transform_prepare(frisk_nmf* h) {
 double frisk_nmf_last_ms(const frisk_nmf* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
 
 void frisk_nmf_destroy(frisk_nmf* h) { destroy_handle(h); }
+
+// ---- spectral clustering (spectral_kernels.h): a handle holding M = D^-1/2 A0 D^-1/2 and dd on its device between products
+struct frisk_spectral {
+    frisk_spectral_impl::State s;
+};
+
+int frisk_spectral_create(int device, const double* Y, int64_t n, int32_t d, double gamma, frisk_spectral** out) {
+    if (!out) return FRISK_E_ARG;
+    *out = nullptr;
+    if (!Y || n < 2 || n > frisk_spectral_impl::MAX_N || d < 1 || d > frisk_proj::MAX_DIMS || !(gamma > 0.0) || !std::isfinite(gamma) ||
+        !all_finite(Y, n * d))
+        return FRISK_E_ARG;
+    return create_handle(device, out, [&](frisk_spectral_impl::State& s) { s.n = n; s.d = d; s.gamma = gamma; return s.create(Y); });
+}
+
+int frisk_spectral_affinity(frisk_spectral* h, double* A0_out) {
+    if (!h || !A0_out) return FRISK_E_ARG;
+    return on_device(h->s.device, [&] { return h->s.affinity(A0_out); });
+}
+
+int frisk_spectral_degrees(frisk_spectral* h, double* dd_out, int64_t* n_isolated) {
+    if (!h || !dd_out || !n_isolated) return FRISK_E_ARG;
+    *n_isolated = h->s.n_isolated;
+    return on_device(h->s.device, [&] {
+        return hipMemcpy(dd_out, h->s.dd, size_t(h->s.n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess;
+    });
+}
+
+int frisk_spectral_matrix(frisk_spectral* h, double* M_out) {
+    if (!h || !M_out) return FRISK_E_ARG;
+    const size_t bytes = size_t(h->s.n) * size_t(h->s.n) * sizeof(double);
+    return on_device(h->s.device, [&] { return hipMemcpy(M_out, h->s.A, bytes, hipMemcpyDeviceToHost) != hipSuccess; });
+}
+
+int frisk_spectral_mq(frisk_spectral* h, const double* Q, int32_t p, double* Z_out) {
+    if (!h || !Q || !Z_out || p < 1 || p > frisk_spectral_impl::SPECTRAL_MAX_P || !all_finite(Q, h->s.n * p)) return FRISK_E_ARG;
+    return on_device(h->s.device, [&] { return h->s.mq(Q, p, Z_out); });
+}
+
+double frisk_spectral_last_ms(const frisk_spectral* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
+
+void frisk_spectral_destroy(frisk_spectral* h) { destroy_handle(h); }
 
 }  // extern "C"

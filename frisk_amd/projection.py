@@ -4,7 +4,10 @@ frisk_kmeans, csrc/proj_kernels.h), and the reference's own exact t-SNE, PY-TSNE
 (frisk_tsne_*, csrc/tsne_kernels.h), sklearn's metric MDS (L1624-1627) on the GPU (frisk_mds_*, csrc/mds_kernels.h) and sklearn's
 IncrementalPCA (L1629-1631) on the GPU, batch by batch with the fit resident on the device (frisk_ipca_*, csrc/ipca_kernels.h),
 and sklearn's NMF (L1632-1636: the coordinate-descent solver from the nndsvda start) with X, W and H resident on the device
-(frisk_nmf_*, csrc/nmf_kernels.h).  sklearn's t-SNE and spectral clustering are not built.
+(frisk_nmf_*, csrc/nmf_kernels.h), and sklearn's SpectralClustering (L1659-1662: rbf affinities, scipy's normalised Laplacian, the
+top eigenvectors, k-means) with the n x n matrix resident on the device (frisk_spectral_*, csrc/spectral_kernels.h): affinities,
+normalisation and every product of the eigen-iteration are kernels, the iteration's QR and Rayleigh-Ritz on matrices at most 26
+columns wide are the host's.  sklearn's t-SNE is not built.
 
 Reference (frisk/__init__.py): computeKmers(sym=True, pcaMode=True) L280-367 counts every valid word AND its
 reverse complement for orders pcaMin..pcaMax; scrubMirrors L797-811 keeps one key of each reverse-complement pair
@@ -192,15 +195,17 @@ class KMeansResult:
         self.labels, self.centers, self.inertia, self.n_iter = labels, centers, inertia, n_iter
 
 
-def kmeans(Y, k, seed=0, n_init=KMEANS_N_INIT, max_iter=KMEANS_MAX_ITER, tol=KMEANS_TOL, device=0):
+def kmeans(Y, k, seed=0, n_init=KMEANS_N_INIT, max_iter=KMEANS_MAX_ITER, tol=KMEANS_TOL, device=0, rs=None):
     """sklearn's KMeans(n_clusters=k, init='k-means++', n_init, max_iter, tol).fit(Y) with random_state=seed: n_init Lloyd runs
     on the GPU from k-means++ seeds drawn in turn from one RandomState(seed); the run of lowest inertia is kept (the earliest on
-    a tie).  Cluster ids are renumbered by first occurrence in row order."""
+    a tie).  Cluster ids are renumbered by first occurrence in row order.  rs, if given, is the RandomState to draw from instead
+    of RandomState(seed) (sklearn's random_state=<instance>: spectral() hands over the one it has already drawn from)."""
     Y = _f64(Y, 2)
     n, d = Y.shape
     if not 1 <= k <= n:
         raise ValueError("n_clusters=%d must be between 1 and n_samples=%d" % (k, n))
-    rs = np.random.RandomState(seed)
+    if rs is None:
+        rs = np.random.RandomState(seed)
     tol_abs = float(np.mean(np.var(Y, axis=0))) * tol          # sklearn's _tolerance
     best = None
     for _ in range(n_init):
@@ -757,3 +762,168 @@ def nmf(X, dims, seed=0, tol=NMF_TOL, max_iter=NMF_MAX_ITER, device=0):
         t3 = time.perf_counter()
     return NMFResult(Y, H, n_iter, t_iter, ratios, W0, H0,
                      {"init_ms": 1e3 * (t1 - t0), "fit_ms": 1e3 * (t2 - t1), "transform_ms": 1e3 * (t3 - t2)})
+
+
+# ------------------------------------------------------------------------------------------------ spectral clustering
+SPECTRAL_GAMMA, SPECTRAL_N_INIT = 1.0, 20       # SpectralClustering(gamma=1.0, affinity='rbf', n_init=20) (L1659-1662)
+SPECTRAL_KMEANS_MAX_ITER = 300                  # sklearn's k_means default, which spectral_clustering leaves alone
+SPECTRAL_MAX_N = 50000                          # the dense n x n matrix: 20 GB at the cap
+SPECTRAL_MAX_K, SPECTRAL_MAX_P, SPECTRAL_GUARD = 16, 26, 10     # clusters; columns of one product = k + the guard columns
+# The stop rule of spectral_embedding: every one of the first k Ritz pairs (theta, v) of M + I has |(M + I) v - theta v|_2 <= tol.
+# With residuals r the computed invariant subspace is within sin(angle) <= r sqrt(k) / gap_k of the true one (Davis-Kahan), so
+# at the smallest gap the goldens allow, 0.1, tol = 1e-10 pins it to 4e-9: far below anything k-means can see, and useful as a
+# test bound.  The floor is the rounding of one product, about n eps64 |M| |Q| = 1.1e-11 at the cap n = 50 000 (rows of |M| |Q| are
+# at most 1): tol sits a factor 9 above it, so the iteration cannot stall short of the rule.
+SPECTRAL_TOL = 1e-10
+# Subspace iteration on M + I (eigenvalues in [0, 2]) contracts the k-th Ritz vector's error by (1 + lambda_{p+1}) / (1 + lambda_k)
+# per step.  Worst case: the guard columns buy nothing (lambda_{p+1} = lambda_{k+1}), the gap is the smallest allowed,
+# lambda_k - lambda_{k+1} = 0.1, and lambda_k = 1 (the rate 1 - 0.1 / (1 + lambda_k) is largest there): 1.9 / 2 = 0.95 per step,
+# so from an error of order 1 to 1e-10 takes ln(1e10) / -ln(0.95) = 449 steps.  500 leaves a tenth in hand.
+SPECTRAL_MAX_ITER = 500
+
+
+class Spectral(_Handle):
+    """The dense part of spectral clustering on the GPU (frisk_spectral_*): from Y (n x d, d <= 64) the rbf affinities, scipy's
+    normalisation and M = D^-1/2 A0 D^-1/2, which stays on the device; each mq() is one product against it.  Use as a context
+    manager (or call close())."""
+
+    _destroy = "frisk_spectral_destroy"
+
+    def __init__(self, Y, gamma=SPECTRAL_GAMMA, device=0):
+        Y = _f64(Y, 2)
+        self.n, self.d = Y.shape
+        self.gamma = float(gamma)
+        self.timings = {"products": 0, "product_ms": 0.0, "product_wall_ms": 0.0, "host_ms": 0.0}   # of the last spectral_embedding
+        self._h = C.c_void_p()
+        _call("frisk_spectral_create", device, _ptr(Y), self.n, self.d, self.gamma, C.byref(self._h))
+
+    def affinity(self):
+        """The n x n A0 = exp(-gamma |y_i - y_j|^2) with a zero diagonal (recomputed; M is restored afterwards)."""
+        A = np.empty((self.n, self.n))
+        _call("frisk_spectral_affinity", self._h, _ptr(A))
+        return A
+
+    def degrees(self):
+        """(dd, n_isolated): dd = sqrt(column sums of A0), a zero sum replaced by 1, and the number of such points."""
+        dd, iso = np.empty(self.n), C.c_int64()
+        _call("frisk_spectral_degrees", self._h, _ptr(dd), C.byref(iso))
+        return dd, iso.value
+
+    def matrix(self):
+        """The n x n M = (A0 / dd) / dd[:, None], exactly symmetric."""
+        M = np.empty((self.n, self.n))
+        _call("frisk_spectral_matrix", self._h, _ptr(M))
+        return M
+
+    def mq(self, Q):
+        """M Q for Q (n x p, p <= 26)."""
+        Q = _f64(Q, 2)
+        if Q.shape[0] != self.n:
+            raise ValueError("expected %d rows, got shape %s" % (self.n, Q.shape))
+        Z = np.empty((self.n, Q.shape[1]))
+        _call("frisk_spectral_mq", self._h, _ptr(Q), Q.shape[1], _ptr(Z))
+        return Z
+
+    def last_ms(self):
+        """Device ms: (the last affinity computation, degrees + normalisation, the last product)."""
+        ms = _ffi.lib().frisk_spectral_last_ms
+        return ms(self._h, 0), ms(self._h, 1), ms(self._h, 2)
+
+
+def spectral_embedding(h, k, seed=0, tol=SPECTRAL_TOL, max_iter=SPECTRAL_MAX_ITER):
+    """sklearn.manifold.spectral_embedding(affinity, n_components=k, norm_laplacian=True, drop_first=False) on the handle h: the k
+    eigenpairs of M of largest ALGEBRAIC eigenvalue, by block subspace iteration with Rayleigh-Ritz on M + I.  (M has zero trace
+    and eigenvalues down to -1 - two mutually close points far from the rest give +-1 - so unshifted iteration would find the
+    largest magnitudes; M + I is positive semi-definite.)  p = min(k + 10, n) columns from Q0 = qr(RandomState(seed).uniform(-1, 1,
+    (n, p))).  Each step is one product on the GPU, Z = M Q + Q, and on the host, on matrices p wide: B = QT Z symmetrised, its
+    eigenpairs (theta, S) in descending order, V = Q S, R = Z S - V theta; stop when the largest 2-norm of the first k columns of
+    R is <= tol, else Q = qr(Z S).  At max_iter a warning is logged and the current Ritz pairs are returned.  Then sklearn's steps:
+    each vector divided by dd, its entry of largest absolute value made positive (_deterministic_vector_sign_flip), transposed.
+    Returns (E n x k, eigenvalues of M (k, descending), residuals (k), iterations); h.timings has the device time of the products,
+    their wall-clock with the transfers, and the host's linear algebra."""
+    n = h.n
+    k = int(k)
+    if not 1 <= k <= min(SPECTRAL_MAX_K, n):
+        raise ValueError("n_components=%d must be between 1 and min(%d, n_samples=%d)" % (k, SPECTRAL_MAX_K, n))
+    p = min(k + SPECTRAL_GUARD, n)
+    t = {"products": 0, "product_ms": 0.0, "product_wall_ms": 0.0, "host_ms": 0.0}
+    t0 = time.perf_counter()
+    Q = np.linalg.qr(np.random.RandomState(seed).uniform(-1, 1, (n, p)))[0]
+    it = 0
+    while True:
+        it += 1
+        t1 = time.perf_counter()
+        t["host_ms"] += 1e3 * (t1 - t0)
+        Z = h.mq(Q)
+        t0 = time.perf_counter()
+        t["products"] += 1
+        t["product_wall_ms"] += 1e3 * (t0 - t1)
+        t["product_ms"] += h.last_ms()[2]
+        MQ = Z
+        Z = MQ + Q
+        B = Q.T @ Z
+        theta, S = np.linalg.eigh(0.5 * (B + B.T))
+        theta, S = theta[::-1], S[:, ::-1]
+        ZS = Z @ S
+        V = Q @ S
+        res = np.sqrt(np.sum((ZS - V * theta) ** 2, axis=0))[:k]
+        if res.max() <= tol:
+            break
+        if it >= max_iter:
+            logging.getLogger(__name__).warning("spectral embedding: residual %.3g above %.3g after %d iterations; the current "
+                                                "Ritz vectors are used.", res.max(), tol, it)
+            break
+        Q = np.linalg.qr(ZS)[0]
+    # the eigenvalues of M as Rayleigh quotients of the Ritz vectors against M itself (theta - 1 carries the rounding of the shift)
+    lam = np.sum(V[:, :k] * (MQ @ S[:, :k]), axis=0) / np.sum(V[:, :k] * V[:, :k], axis=0)
+    dd, _iso = h.degrees()
+    E = V[:, :k].T / dd
+    big = np.argmax(np.abs(E), axis=1)
+    E *= np.sign(E[np.arange(k), big])[:, None]
+    t["host_ms"] += 1e3 * (time.perf_counter() - t0)
+    h.timings = t
+    return np.ascontiguousarray(E.T), lam, res, it
+
+
+class SpectralResult:
+    """labels (n, renumbered by first occurrence), embedding (n x k), eigenvalues of M (k, descending), residuals (k), n_iter,
+    n_isolated, timings in ms (affinity and normalise: device; products: device, products_wall with the transfers, host: the
+    iteration's linear algebra; embedding and kmeans: wall-clock)."""
+
+    def __init__(self, labels, embedding, eigenvalues, residuals, n_iter, n_isolated, timings):
+        self.labels, self.embedding, self.eigenvalues, self.residuals = labels, embedding, eigenvalues, residuals
+        self.n_iter, self.n_isolated, self.timings = n_iter, n_isolated, timings
+
+
+def spectral(Y, k, seed=0, gamma=SPECTRAL_GAMMA, n_init=SPECTRAL_N_INIT, device=0):
+    """sklearn's SpectralClustering(n_clusters=k, eigen_solver=None, n_init, gamma, affinity='rbf', eigen_tol=0.0, assign_labels=
+    'kmeans', random_state=seed).fit_predict(Y) (L1659-1662): affinities, normalisation and every product of the eigen-iteration
+    on the GPU (Spectral, spectral_embedding), then k_means(embedding, k, n_init, max_iter=300) on the GPU.  One rs = RandomState(
+    seed) serves as in sklearn: the n draws ARPACK's start vector takes there are discarded, then k-means draws from the same rs.
+    The eigenvectors are ARPACK's up to a rotation among (nearly) equal eigenvalues, which k-means cannot see.  A point whose every
+    affinity underflows to 0 (n_isolated > 0) certainly disconnects the graph and logs sklearn's warning; connectivity proper
+    (sklearn's _graph_is_connected) is not tested, so a graph disconnected by exact zeros between groups of points goes unwarned."""
+    Y = _f64(Y, 2)
+    n = Y.shape[0]
+    k = int(k)
+    if not 2 <= n <= SPECTRAL_MAX_N:
+        raise ValueError("SPECTRAL needs between 2 and %d samples, got %d" % (SPECTRAL_MAX_N, n))
+    if not (1 <= k <= SPECTRAL_MAX_K and k < n):
+        raise ValueError("n_clusters=%d must be between 1 and %d and below n_samples=%d" % (k, SPECTRAL_MAX_K, n))
+    rs = np.random.RandomState(seed)
+    rs.uniform(-1, 1, n)                                # sklearn's _init_arpack_v0
+    t0 = time.perf_counter()
+    with Spectral(Y, gamma, device) as h:
+        _dd, n_isolated = h.degrees()
+        aff_ms, norm_ms, _ = h.last_ms()
+        if n_isolated:
+            logging.getLogger(__name__).warning("Graph is not fully connected, spectral embedding may not work as expected.")
+        E, lam, res, n_iter = spectral_embedding(h, k, seed)
+        t = dict(h.timings)
+    t1 = time.perf_counter()
+    km = kmeans(E, k, n_init=n_init, max_iter=SPECTRAL_KMEANS_MAX_ITER, device=device, rs=rs)
+    t2 = time.perf_counter()
+    return SpectralResult(km.labels, E, lam, res, n_iter, n_isolated,
+                          {"affinity_ms": aff_ms, "normalise_ms": norm_ms, "products_ms": t["product_ms"],
+                           "products_wall_ms": t["product_wall_ms"], "host_ms": t["host_ms"], "embedding_ms": 1e3 * (t1 - t0),
+                           "kmeans_ms": 1e3 * (t2 - t1)})

@@ -424,6 +424,33 @@ int  frisk_nmf_transform_prepare(frisk_nmf* h);
 double frisk_nmf_last_ms(const frisk_nmf* h, int which);
 void frisk_nmf_destroy(frisk_nmf* h);
 
+/* Spectral clustering of the reference's --cluster SPECTRAL (sklearn.cluster.SpectralClustering(affinity='rbf', gamma,
+ * assign_labels='kmeans')): the dense n x n part, FP64 on `device`.  The handle keeps ONE n x n buffer on the device: the
+ * affinities A0_ij = exp(-gamma sum_c (y_ic - y_jc)^2) (direct differences, c in order; the diagonal exactly 0, A0 exactly
+ * symmetric), normalised in place as scipy.sparse.csgraph.laplacian(normed=True) does: w_j = sum_i A0_ij (the rows in fixed
+ * ranges, the ranges in order), w == 0 replaced by 1, dd = sqrt(w), M_ij = (A0_ij / dd_j) / dd_i.  scipy's entry (j, i) divides
+ * in the other order and can differ in the last two roundings; each entry here is the mean of the two, so M is exactly symmetric and
+ * within 1 ulp of scipy's entry on either side.  The caller drives the eigen-iteration with products against M (block subspace
+ * iteration with Rayleigh-Ritz: frisk_amd.projection.spectral_embedding); the host parts are at most 26 columns wide.
+ * frisk_spectral_create: Y[n][d]; computes A0, dd and M.  FRISK_E_ARG, with nothing allocated, unless 2 <= n <= 50 000,
+ *   1 <= d <= 64, gamma is finite and > 0 and every entry of Y is finite.  Device memory: 8 n^2 bytes plus O(n * (256 + 52 + d)).
+ * frisk_spectral_affinity: A0_out[n][n], before normalisation: recomputed into the buffer on request (the same bits), copied out,
+ *   and the buffer normalised again from the kept dd (the same M).
+ * frisk_spectral_degrees: dd_out[n], and *n_isolated = the number of points whose w was 0 (every affinity underflowed).
+ * frisk_spectral_matrix: M_out[n][n].
+ * frisk_spectral_mq: Z_out[n][p] = M Q for Q[n][p].  FRISK_E_ARG unless 1 <= p <= 26 and Q is finite.
+ * frisk_spectral_last_ms: device time in ms of the last affinity computation (which = 0), degrees + normalisation at create (1),
+ *   and the last product (2); else -1.
+ * Every entry point returns FRISK_E_ARG for a null pointer.  Every result is bit-identical from run to run. */
+typedef struct frisk_spectral frisk_spectral;
+int  frisk_spectral_create(int device, const double* Y, int64_t n, int32_t d, double gamma, frisk_spectral** out);
+int  frisk_spectral_affinity(frisk_spectral* h, double* A0_out);
+int  frisk_spectral_degrees(frisk_spectral* h, double* dd_out, int64_t* n_isolated);
+int  frisk_spectral_matrix(frisk_spectral* h, double* M_out);
+int  frisk_spectral_mq(frisk_spectral* h, const double* Q, int32_t p, double* Z_out);
+double frisk_spectral_last_ms(const frisk_spectral* h, int which);
+void frisk_spectral_destroy(frisk_spectral* h);
+
 /* Page-locked host memory for result buffers: D2H copies into it are asynchronous and run at PCIe rate
  * (pageable buffers work too, at a fraction of it).  Free with frisk_host_free before frisk_destroy. */
 void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);
