@@ -95,6 +95,31 @@ __device__ inline double log_tab_n(double x, const double2* tab) {
     return __builtin_fma(double(k), 0.69314718055994530942, e.y) + __builtin_fma(r * r, p, r);
 }
 
+// log_tab_n in two halves - the same operations on the same operands, so the same bits: exponent, mantissa and the bin's entry
+// requested from LDS; then, with other work behind the read, the polynomial and the sum (the K = 8 scoring loop in groups of two).
+struct LogHalf {
+    double m;
+    double2 e;
+    int k;
+};
+template <int N>
+__device__ inline LogHalf log_tab_front(double x, const double2* tab) {
+    LogHalf h;
+    h.k = __builtin_amdgcn_frexp_exp(x);
+    h.m = __builtin_amdgcn_frexp_mant(x);
+    const uint32_t off = (uint32_t(__double2hiint(h.m)) >> ((N == 128 ? 13 : (N == 64 ? 14 : 15)) - 4)) & (uint32_t(N - 1) << 4);
+    h.e = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(tab) + off);
+    return h;
+}
+template <int DEG>
+__device__ inline double log_tab_back(const LogHalf& h) {
+    const double r = __builtin_fma(h.m, h.e.x, -1.0);
+    double p = (DEG & 1) ? 1.0 / DEG : -1.0 / DEG;
+#pragma unroll
+    for (int d = DEG - 1; d >= 2; --d) p = __builtin_fma(r, p, (d & 1) ? 1.0 / d : -1.0 / d);
+    return __builtin_fma(double(h.k), 0.69314718055994530942, h.e.y) + __builtin_fma(r * r, p, r);
+}
+
 template <int CTRL>
 __device__ inline uint32_t dpp_addu(uint32_t x) {
     return x + uint32_t(__builtin_amdgcn_update_dpp(0, int(x), CTRL, 0xF, 0xF, false));
@@ -1139,8 +1164,11 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             // One position, its counts known.  `sel`: the position's index into the {1/c, c^2 r_K} table - its top count, or 0
             // where it starts no max-mer: such a position scores the stand-in code (a real max-mer of this window: finite values)
             // with weight 0 and adds exactly +0.0 to every sum, so no term needs a mask.
-            auto score_one = [&](const Fetched& f, uint32_t c8, uint32_t c7, uint32_t c6, uint32_t sel, bool on)
-                                 __attribute__((always_inline)) {
+            struct Scored {                     // Iw / Ig, and the position's shares of Ig and Iw
+                double ratio, Igr, Iwr;
+            };
+            auto score_ratio = [&](const Fetched& f, uint32_t c8, uint32_t c7, uint32_t c6, uint32_t sel, bool on)
+                                   __attribute__((always_inline)) -> Scored {
                 double2 rs;                                                   // {1/c8 (1.0 for the 19 in 20 max-mers seen once), c8^2 r8}
                 if constexpr (BITS == 4) rs = rstab[sel & (SIDE ? 255u : 15u)];            // (SIDE, beyond 15: the 8-bit form's values)
                 else {
@@ -1171,10 +1199,34 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                 const double ratio = A * rr;
                 const double Igr = f.Ig * rs.x;                               // this position's share of Ig ...
                 const double Iwr = ratio * Igr;                               // ... and of Iw
-                const double ln = log_tab_n<LOGN, LOGDEG>(ratio, logtab);
-                sw += Iwr;
-                sg += Igr;
-                stt = __builtin_fma(Iwr, ln, stt);
+                return Scored{ratio, Igr, Iwr};
+            };
+            auto score_one = [&](const Fetched& f, uint32_t c8, uint32_t c7, uint32_t c6, uint32_t sel, bool on)
+                                 __attribute__((always_inline)) {
+                const Scored s = score_ratio(f, c8, c7, c6, sel, on);
+                const double ln = log_tab_n<LOGN, LOGDEG>(s.ratio, logtab);
+                sw += s.Iwr;
+                sg += s.Igr;
+                stt = __builtin_fma(s.Iwr, ln, stt);
+            };
+            // The same position in two halves, for the loop in groups of two: everything up to the request for the logarithm table's
+            // entry, and - behind the NEXT group's front halves - the polynomial and the two sums that need it.  Each of Sw, Sg and T
+            // still takes its terms in position order: the same bits.  (score_one waits for the entry three or four vector
+            // instructions behind its request, 20 times per lane and window; with the halves apart there are 28 .. 63 in between.)
+            struct ScoreHalf {
+                LogHalf lg;
+                double Iwr;
+            };
+            auto score_front = [&](const Fetched& f, uint32_t c8, uint32_t c7, uint32_t c6, uint32_t sel, bool on)
+                                   __attribute__((always_inline)) -> ScoreHalf {
+                const Scored s = score_ratio(f, c8, c7, c6, sel, on);
+                sg += s.Igr;
+                return ScoreHalf{log_tab_front<LOGN>(s.ratio, logtab), s.Iwr};
+            };
+            auto score_back = [&](const ScoreHalf& h) __attribute__((always_inline)) {
+                const double ln = log_tab_back<LOGDEG>(h.lg);
+                sw += h.Iwr;
+                stt = __builtin_fma(h.Iwr, ln, stt);
             };
             // the lane's codes and flags again, opaque to the optimiser: without this it keeps every position's pre-shifted
             // code variants of stage 1 alive across the whole window (60 registers) instead of re-deriving them here
@@ -1214,8 +1266,15 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                 auto code4_at = [&](int it) -> uint32_t {      // the position's max-mer, or the stand-in where it starts none
                     return on_at(it) ? raw4_at(it) : safe_code;
                 };
-                // a group of GR positions: counts from the table, plus the orphans
-                auto score_group = [&](Fetched (&f)[GR], int g, auto check_c) __attribute__((always_inline)) {
+                // SPLIT: the unrolled loop in groups of two scores a position in two halves (score_front, score_back) - group g's back
+                // halves run behind group g + 1's front halves.  Measured on the whole C5 shape, same-box A/B, three rounds: 43.92 ..
+                // 44.10 ms against 44.62 .. 44.77; the halves of ONE group apart (front, front, back, back): 44.36 .. 44.42 - the
+                // compiler then sinks both requests to the fence between them.  Groups of one (the side table's form, the 8-bit form)
+                // keep score_one: in halves across the group boundary they measured 7.21 .. 7.23 ms against 7.19 .. 7.22 on the
+                // repeat-rich shard.
+                constexpr bool SPLIT = GR > 1 && !ROLLED;
+                // a group of GR positions: counts from the table, plus the orphans (SPLIT: the front halves, into `half`)
+                auto score_group = [&](Fetched (&f)[GR], int g, auto check_c, ScoreHalf* half) __attribute__((always_inline)) {
                     constexpr bool CHECK = decltype(check_c)::value;         // (the unrolled form's last group may be short)
                     uint32_t c8[GR], c7[GR], c6[GR];
 #pragma unroll
@@ -1244,9 +1303,14 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                         if (!CHECK || g + k < ITS) {
                             // (the value this position used, into the ring for the windows to come: 1.0 where it starts no max-mer)
                             if constexpr (PARK) *reinterpret_cast<double*>(ring + f[k].roff) = on_at(g + k) ? f[k].Ig : 1.0;
-                            score_one(f[k], c8[k], c7[k], c6[k], on_at(g + k) ? c8[k] : 0u, on_at(g + k));
+                            if constexpr (SPLIT) half[k] = score_front(f[k], c8[k], c7[k], c6[k], on_at(g + k) ? c8[k] : 0u, on_at(g + k));
+                            else score_one(f[k], c8[k], c7[k], c6[k], on_at(g + k) ? c8[k] : 0u, on_at(g + k));
                         }
                     }
+                };
+                auto group_back = [&](const ScoreHalf* half, int g) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int k = 0; k < GR; ++k) if (g + k < ITS) score_back(half[k]);
                 };
                 // software pipeline: the reads of group g+1 are issued before the arithmetic of group g.
                 // The rolled form: two groups per trip, ping-pong buffers (ITS is a multiple of 2 GR for GR = 1, 2); it needs
@@ -1260,17 +1324,18 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     for (int g = 0; g < ITS; g += 2 * GR) {
 #pragma unroll
                         for (int k = 0; k < GR; ++k) bufB[k] = fetch(code4_at(g + GR + k), g + GR + k, FMODE);
-                        score_group(bufA, g, std::false_type{});
+                        score_group(bufA, g, std::false_type{}, nullptr);
                         __builtin_amdgcn_sched_barrier(0);
                         const int gn = g + 2 * GR < ITS ? g + 2 * GR : 0;       // (the last trip fetches group 0 again, unused)
 #pragma unroll
                         for (int k = 0; k < GR; ++k) bufA[k] = fetch(code4_at(gn + k), gn + k, FMODE);
-                        score_group(bufB, g + GR, std::false_type{});
+                        score_group(bufB, g + GR, std::false_type{}, nullptr);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     return;
                 }
                 Fetched buf[2][GR];
+                ScoreHalf half[2][GR];              // (SPLIT) the front halves of this group and of the one before
 #pragma unroll
                 for (int k = 0; k < GR; ++k) if (k < ITS) buf[0][k] = fetch(code4_at(k), k, FMODE);
 #pragma unroll
@@ -1278,8 +1343,17 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
                     const int cur = (g / GR) & 1;
 #pragma unroll
                     for (int k = 0; k < GR; ++k) if (g + GR + k < ITS) buf[cur ^ 1][k] = fetch(code4_at(g + GR + k), g + GR + k, FMODE);
-                    score_group(buf[cur], g, std::true_type{});
+                    score_group(buf[cur], g, std::true_type{}, half[cur]);
+                    if constexpr (SPLIT) {
+                        // (the fence keeps the back halves, whose table entries arrived long ago, from moving up in front of these front halves)
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (g > 0) group_back(half[cur ^ 1], g - GR);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (SPLIT) {
+                    constexpr int LAST = (ITS - 1) / GR * GR;
+                    group_back(half[(LAST / GR) & 1], LAST);
                 }
             };
             constexpr uint32_t ALL_MINE = uint32_t(0xFFFFFFFF00000000ull >> ITS);

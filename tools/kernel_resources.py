@@ -17,10 +17,17 @@ def main():
     tmp = tempfile.mkdtemp(prefix="frisk_res_")
     fat = os.path.join(tmp, "fat.bin")
     subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-    co = os.path.join(tmp, "gfx950.co")
-    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+    # (one bundle per translation unit of the library, one behind the other in the section)
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    blob = open(fat, "rb").read()
+    starts = [i for i in range(len(blob)) if blob.startswith(magic, i)]
+    notes = ""
+    for n, (a, b) in enumerate(zip(starts, starts[1:] + [len(blob)])):
+        part, co = os.path.join(tmp, "fat%d.bin" % n), os.path.join(tmp, "gfx950_%d.co" % n)
+        open(part, "wb").write(blob[a:b])
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+        notes += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
     demangle = lambda n: subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip()  # noqa: E731
     rows = []
     for block in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
