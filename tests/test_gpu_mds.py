@@ -158,6 +158,13 @@ def test_widths_and_dims(f, d):
     _oracle_steps(_blobs(70, f, 100 * f + d), d, 3, d)
 
 
+@pytest.mark.parametrize("n,d", [(257, 17), (513, 5), (2049, 2), (2048, 2)])
+def test_reductions_past_256_partials(n, d):
+    """257, 257, 257 and 256 per-block partials for mds_sum_parts (1, 2 and 8 rows per block): the stress of a sum over more
+    than 256 blocks against the oracle's."""
+    _oracle_steps(_blobs(n, 9, n + d), d, 3, n)
+
+
 def test_abi_rejects_bad_input():
     from frisk_amd import _ffi
     L = _ffi.lib()
