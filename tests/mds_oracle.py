@@ -13,6 +13,10 @@ below cover both against the exact values:
   stress    from the step bound b_i of each row: sum_ij |e_ij| (b_i + b_j + g_ij) + (b_i + b_j + g_ij)^2, halved, with
             e_ij = dist_ij - D_ij, g_ij = C_D_GRAM eps s_ij / dist_ij + 4 eps dist_ij, plus a relative 1e-13.
 The constants are calibrated on the goldens (tests/test_mds_cpu.py reports the worst measured ratio to each bound).
+
+These bounds relate the device to sklearn's Gram form and grow with |x|.  To compare the device with the exact value use
+tests/mds_oracle_hp.py (long double, units without a Gram term; tests/test_gpu_mds_edges.py), for which direct_D, step and stress
+here serve as the float64 model.
 """
 import numpy as np
 
