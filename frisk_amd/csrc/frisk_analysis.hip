@@ -12,6 +12,7 @@
 
 #include "frisk_hip.h"
 #include "hmm_host.h"
+#include "analysis_common.h"
 #include "proj_kernels.h"
 #include "tsne_kernels.h"
 #include "mds_kernels.h"
@@ -25,7 +26,7 @@ namespace {
 // switch to `device`, run f there, and map its non-zero result to FRISK_E_HIP
 template <typename F>
 int on_device(int device, F&& f) {
-    frisk_proj::OnDevice on(device);
+    frisk_common::OnDevice on(device);
     if (!on.ok) return FRISK_E_HIP;
     return f() ? FRISK_E_HIP : FRISK_OK;
 }
@@ -34,7 +35,7 @@ int on_device(int device, F&& f) {
 // its device).  `make` fills the state's shape and allocates: 0, or the handle is dropped.
 template <typename H, typename Make>
 int create_handle(int device, H** out, Make&& make) {
-    frisk_proj::OnDevice on(device);
+    frisk_common::OnDevice on(device);
     if (!on.ok) return FRISK_E_HIP;
     H* h = new (std::nothrow) H;
     if (!h) return FRISK_E_HIP;
@@ -50,8 +51,19 @@ int create_handle(int device, H** out, Make&& make) {
 template <typename H>
 void destroy_handle(H* h) {
     if (!h) return;
-    frisk_proj::OnDevice on(h->s.device);
+    frisk_common::OnDevice on(h->s.device);
     delete h;
+}
+
+// ms[which] of a handle's last timed call (the *_last_ms entries), -1 for no handle or no such slot
+template <typename H>
+double last_ms(const H* h, int which) {
+    return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0;
+}
+
+// copy `bytes` between a host array the caller may have left out (null: nothing to do) and the device; true when the copy fails
+bool copy_fails(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    return dst && src && hipMemcpy(dst, src, bytes, kind) != hipSuccess;
 }
 
 }  // namespace
@@ -162,7 +174,7 @@ int frisk_hmm_fit_gpu(int device, const double* x, int64_t n, int32_t n_iter, do
                       double* means, double* covars, double* startprob, double* transmat, double* loglik, int32_t* iters) {
     if (!x || n < 1 || n > (int64_t(1) << 40) || n_iter < 0 || !means || !covars || !startprob || !transmat || !all_finite(x, n))
         return FRISK_E_ARG;
-    frisk_proj::OnDevice on(device);
+    frisk_common::OnDevice on(device);
     if (!on.ok) return FRISK_E_HIP;
     frisk_hmm::Fit F;
     if (frisk_hmm_gpu::fit(x, n, n_iter, tol, min_covar, covars_prior, F)) return FRISK_E_HIP;
@@ -208,24 +220,23 @@ int frisk_tsne_create(int device, const double* X, int64_t n, int32_t f, double 
 
 int frisk_tsne_affinities(frisk_tsne* h, double* beta_out, int32_t* tries_out, double* q_out) {
     if (!h) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
+    frisk_common::OnDevice on(h->s.device);
     if (!on.ok) return FRISK_E_HIP;
     const int64_t n = h->s.n;
     if (!h->s.have_p) {
         const int e = h->s.affinities();
         if (e) return e == -1 ? FRISK_E_ARG : FRISK_E_HIP;
     }
-    if (beta_out && hipMemcpy(beta_out, h->s.beta, size_t(n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return FRISK_E_HIP;
-    if (tries_out && hipMemcpy(tries_out, h->s.tries, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return FRISK_E_HIP;
-    if (q_out && hipMemcpy(q_out, h->s.P, size_t(n) * size_t(n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    if (copy_fails(beta_out, h->s.beta, size_t(n) * sizeof(double), hipMemcpyDeviceToHost) ||
+        copy_fails(tries_out, h->s.tries, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost) ||
+        copy_fails(q_out, h->s.P, size_t(n) * size_t(n) * sizeof(double), hipMemcpyDeviceToHost))
         return FRISK_E_HIP;
     return FRISK_OK;
 }
 
 int frisk_tsne_run(frisk_tsne* h, int32_t iter_begin, int32_t iter_end, double* cost_out) {
     if (!h || iter_begin < 0 || iter_end < iter_begin || iter_end > frisk_tsne_impl::MAX_ITER) return FRISK_E_ARG;
-    frisk_proj::OnDevice on(h->s.device);
+    frisk_common::OnDevice on(h->s.device);
     if (!on.ok) return FRISK_E_HIP;
     if (!h->s.have_p) {
         const int e = h->s.affinities();
@@ -238,9 +249,9 @@ int frisk_tsne_get(frisk_tsne* h, double* Y, double* iY, double* gains) {
     if (!h) return FRISK_E_ARG;
     const size_t bytes = size_t(h->s.n) * size_t(h->s.d) * sizeof(double);
     return on_device(h->s.device, [&] {
-        return (Y && hipMemcpy(Y, h->s.Y, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
-               (iY && hipMemcpy(iY, h->s.iY, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
-               (gains && hipMemcpy(gains, h->s.gains, bytes, hipMemcpyDeviceToHost) != hipSuccess);
+        return copy_fails(Y, h->s.Y, bytes, hipMemcpyDeviceToHost) ||
+               copy_fails(iY, h->s.iY, bytes, hipMemcpyDeviceToHost) ||
+               copy_fails(gains, h->s.gains, bytes, hipMemcpyDeviceToHost);
     });
 }
 
@@ -250,9 +261,9 @@ int frisk_tsne_set(frisk_tsne* h, const double* Y, const double* iY, const doubl
     if ((Y && !all_finite(Y, nd)) || (iY && !all_finite(iY, nd)) || (gains && !all_finite(gains, nd))) return FRISK_E_ARG;
     const size_t bytes = size_t(nd) * sizeof(double);
     return on_device(h->s.device, [&] {
-        return (Y && hipMemcpy(h->s.Y, Y, bytes, hipMemcpyHostToDevice) != hipSuccess) ||
-               (iY && hipMemcpy(h->s.iY, iY, bytes, hipMemcpyHostToDevice) != hipSuccess) ||
-               (gains && hipMemcpy(h->s.gains, gains, bytes, hipMemcpyHostToDevice) != hipSuccess);
+        return copy_fails(h->s.Y, Y, bytes, hipMemcpyHostToDevice) ||
+               copy_fails(h->s.iY, iY, bytes, hipMemcpyHostToDevice) ||
+               copy_fails(h->s.gains, gains, bytes, hipMemcpyHostToDevice);
     });
 }
 
@@ -316,10 +327,10 @@ int frisk_ipca_get(frisk_ipca* h, int64_t* n_seen, double* mean, double* var, do
     if (!h->s.fitted) return FRISK_E_STATE;
     const size_t fb = size_t(h->s.f) * sizeof(double), db = size_t(h->s.d) * sizeof(double);
     return on_device(h->s.device, [&] {
-        return (mean && hipMemcpy(mean, h->s.mean, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
-               (var && hipMemcpy(var, h->s.var, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
-               (S && hipMemcpy(S, h->s.S, db, hipMemcpyDeviceToHost) != hipSuccess) ||
-               (Vt && hipMemcpy(Vt, h->s.Vt, size_t(h->s.d) * fb, hipMemcpyDeviceToHost) != hipSuccess);
+        return copy_fails(mean, h->s.mean, fb, hipMemcpyDeviceToHost) ||
+               copy_fails(var, h->s.var, fb, hipMemcpyDeviceToHost) ||
+               copy_fails(S, h->s.S, db, hipMemcpyDeviceToHost) ||
+               copy_fails(Vt, h->s.Vt, size_t(h->s.d) * fb, hipMemcpyDeviceToHost);
     });
 }
 
@@ -337,7 +348,7 @@ int frisk_ipca_transform(frisk_ipca* h, const double* X, int64_t n, double* Y_ou
     return on_device(h->s.device, [&] { return h->s.transform(X, n, Y_out); });
 }
 
-double frisk_ipca_last_ms(const frisk_ipca* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
+double frisk_ipca_last_ms(const frisk_ipca* h, int which) { return last_ms(h, which); }
 
 void frisk_ipca_destroy(frisk_ipca* h) { destroy_handle(h); }
 
@@ -355,7 +366,7 @@ bool all_finite_nonneg(const double* x, int64_t count) {
 // H[d][f] (host) <-> Ht[f][d] (device)
 int nmf_put_H(frisk_nmf_impl::State& s, const double* H) {
     std::vector<double> t(size_t(s.f) * size_t(s.d));
-    frisk_proj::transpose(H, s.d, s.f, t.data());
+    frisk_common::transpose(H, s.d, s.f, t.data());
     s.frozen = false;
     return hipMemcpy(s.Ht, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? 0 : -2;
 }
@@ -363,7 +374,7 @@ int nmf_put_H(frisk_nmf_impl::State& s, const double* H) {
 int nmf_take_H(frisk_nmf_impl::State& s, double* H) {
     std::vector<double> t(size_t(s.f) * size_t(s.d));
     if (hipMemcpy(t.data(), s.Ht, t.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -2;
-    frisk_proj::transpose(t.data(), s.f, s.d, H);
+    frisk_common::transpose(t.data(), s.f, s.d, H);
     return 0;
 }
 }  // namespace
@@ -389,7 +400,7 @@ int frisk_nmf_set(frisk_nmf* h, const double* W, const double* H) {
     if (!h) return FRISK_E_ARG;
     if ((W && !all_finite(W, h->s.n * h->s.d)) || (H && !all_finite(H, int64_t(h->s.d) * h->s.f))) return FRISK_E_ARG;
     return on_device(h->s.device, [&] {
-        return (W && hipMemcpy(h->s.W, W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) ||
+        return copy_fails(h->s.W, W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyHostToDevice) ||
                (H && nmf_put_H(h->s, H));
     });
 }
@@ -397,7 +408,7 @@ int frisk_nmf_set(frisk_nmf* h, const double* W, const double* H) {
 int frisk_nmf_get(frisk_nmf* h, double* W, double* H) {
     if (!h) return FRISK_E_ARG;
     return on_device(h->s.device, [&] {
-        return (W && hipMemcpy(W, h->s.W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        return copy_fails(W, h->s.W, size_t(h->s.n) * size_t(h->s.d) * sizeof(double), hipMemcpyDeviceToHost) ||
                (H && nmf_take_H(h->s, H));
     });
 }
@@ -405,7 +416,7 @@ int frisk_nmf_get(frisk_nmf* h, double* W, double* H) {
 int frisk_nmf_step(frisk_nmf* h, double* W_inout, double* H_inout, int32_t update_H, double* violation) {
     if (!h || !violation) return FRISK_E_ARG;
     if (int e = frisk_nmf_set(h, W_inout, H_inout)) return e;
-    frisk_proj::OnDevice on(h->s.device);
+    frisk_common::OnDevice on(h->s.device);
     if (!on.ok) return FRISK_E_HIP;
     if (h->s.step(update_H ? 1 : 0, violation)) return FRISK_E_HIP;
     return frisk_nmf_get(h, W_inout, H_inout);
@@ -416,7 +427,7 @@ int frisk_nmf_transform_prepare(frisk_nmf* h) {
     return on_device(h->s.device, [&] { return h->s.prepare(); });
 }
 
-double frisk_nmf_last_ms(const frisk_nmf* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
+double frisk_nmf_last_ms(const frisk_nmf* h, int which) { return last_ms(h, which); }
 
 void frisk_nmf_destroy(frisk_nmf* h) { destroy_handle(h); }
 
@@ -458,7 +469,7 @@ int frisk_spectral_mq(frisk_spectral* h, const double* Q, int32_t p, double* Z_o
     return on_device(h->s.device, [&] { return h->s.mq(Q, p, Z_out); });
 }
 
-double frisk_spectral_last_ms(const frisk_spectral* h, int which) { return (h && which >= 0 && which < 3) ? h->s.ms[which] : -1.0; }
+double frisk_spectral_last_ms(const frisk_spectral* h, int which) { return last_ms(h, which); }
 
 void frisk_spectral_destroy(frisk_spectral* h) { destroy_handle(h); }
 

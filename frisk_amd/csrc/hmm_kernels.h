@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "hmm_host.h"
-#include "proj_kernels.h"      // DevMem, OnDevice
+#include "analysis_common.h"    // DevMem, FRISK_HIP_CHECK
 
 namespace frisk_hmm_gpu {
 
@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(64) hmm_covar_walk(const double* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------- host: fit
 // the device arrays of one sequence: allocated once, used by every round
 struct Work {
-    frisk_proj::DevMem mem;
+    frisk_common::DevMem mem;
     int P = 0, C = 0;
     double* dx = nullptr;
     double2 *B = nullptr, *A = nullptr;
@@ -502,7 +502,7 @@ __global__ void __launch_bounds__(64) hmm_vit_backtrack(const int64_t* __restric
 
 // sequences [off[s], off[s + 1]) of x into path (both indexed as off[] says); returns 0 or -2
 inline int viterbi_segments(const double* x, const int64_t* off, int32_t n_seg, const frisk_hmm::Model& m, int8_t* path) {
-    using frisk_proj::DevMem;
+    using frisk_common::DevMem;
     const int64_t base = off[0], n = off[n_seg] - off[0];
     if (n <= 0) return 0;
     std::vector<int64_t> pa, pb, seg_piece(size_t(n_seg) + 1);

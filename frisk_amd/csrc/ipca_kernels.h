@@ -2,7 +2,7 @@
 //
 // The state (rows seen, column mean and variance, singular values S and components V) stays on the device between batches.
 // One batch of b rows goes through
-//   statistics   column sums of the batch (proj_colsum_part + ipca_colsum), then sum(x - T) and sum (x - T)^2 per column with
+//   statistics   column sums of the batch (colsum_part + ipca_colsum), then sum(x - T) and sum (x - T)^2 per column with
 //                T the batch mean (ipca_dev_part), then sklearn's _incremental_mean_and_var merge, operation for operation,
 //                one thread per column (ipca_merge);
 //   stack        the zero-padded A: first batch the batch minus the new mean; later batches the d rows S_i V_i, the batch minus
@@ -11,17 +11,22 @@
 // The right singular vectors of A are the eigenvectors of G and S^2 its eigenvalues; the caller decomposes G and hands S and V
 // back (commit), which also installs the batch's mean, variance and row count.
 // Every reduction has a fixed order that depends on the shape only, and there is no floating-point atomic: every output is
-// bit-identical from run to run.  Included from frisk_analysis.hip after proj_kernels.h.
+// bit-identical from run to run.  Included from frisk_analysis.hip; it launches PCA's centring, covariance and transform kernels
+// (proj_kernels.h) and the column sums of analysis_common.h over PCA's ranges.
 #pragma once
 
+#include "analysis_common.h"
 #include "proj_kernels.h"
 
 namespace frisk_ipca_impl {
 
+using frisk_common::Buf;
+using frisk_common::round_up;
+using frisk_common::RowSplits;
 using frisk_proj::COV_KSTEP;
 using frisk_proj::COV_T;
 using frisk_proj::MEAN_SPLITS;
-using frisk_proj::round_up;
+using frisk_proj::MEAN_UNROLL;
 
 // sum[c] = the split partials of column c in split order; T[c] = sum[c] / b (numpy's mean: the sum divided by the count)
 __global__ __launch_bounds__(256) void ipca_colsum(const double* __restrict__ part, int nsplit, int64_t b, int64_t f,
@@ -103,24 +108,6 @@ __global__ __launch_bounds__(256) void ipca_stack(const double* __restrict__ X, 
     }
 }
 
-// A device buffer that grows and is never shrunk; freed with its owner.
-struct Buf {
-    double* p = nullptr;
-    size_t cap = 0;
-    ~Buf() { if (p) (void)hipFree(p); }
-    double* ensure(size_t count) {
-        if (count <= cap) return p;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        void* q = nullptr;
-        if (hipMalloc(&q, (count ? count : 1) * sizeof(double)) != hipSuccess) return nullptr;
-        p = static_cast<double*>(q);
-        cap = count;
-        return p;
-    }
-};
-
 constexpr int64_t TRANSFORM_PIECE = int64_t(1) << 23;       // doubles of padded rows per transform piece (64 MB)
 
 // Device state of one incremental fit (the C handle frisk_ipca).
@@ -131,16 +118,12 @@ struct State {
     int64_t seen = 0;                   // rows of the committed batches
     int64_t pending_b = 0;              // rows of the batch whose Gram matrix is out and not committed yet (0: none)
     bool fitted = false;                // S and V hold a committed decomposition
-    frisk_proj::DevMem mem;
+    frisk_common::DevMem mem;
     double *mean = nullptr, *var = nullptr, *mean_new = nullptr, *var_new = nullptr, *S = nullptr, *Vt = nullptr, *Vfd = nullptr;
     double *bsum = nullptr, *T = nullptr, *G = nullptr;
     Buf X, A, part, covpart, Y;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    frisk_common::EventTimer<4> timer;
     double ms[3] = {0.0, 0.0, 0.0};     // of the last gram(): upload, statistics + stack, Gram
-
-    ~State() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
 
     int create() {
         f_pad = round_up(f, COV_T);
@@ -149,8 +132,7 @@ struct State {
         S = mem.get<double>(sd); Vt = mem.get<double>(sd * sf); Vfd = mem.get<double>(sd * sf);
         bsum = mem.get<double>(sf); T = mem.get<double>(sf); G = mem.get<double>(sf * sf);
         if (!mean || !var || !mean_new || !var_new || !S || !Vt || !Vfd || !bsum || !T || !G) return -2;
-        for (hipEvent_t& e : ev) FRISK_HIP_CHECK(hipEventCreate(&e));
-        return 0;
+        return timer.create();
     }
 
     // Statistics, stack and Gram matrix of one batch; G_out[f * f].  Nothing of the committed state changes.  Returns 0 or -2.
@@ -158,8 +140,9 @@ struct State {
         pending_b = 0;
         const int64_t rows = seen ? int64_t(d) + b + 1 : b;
         const int64_t rows_pad = round_up(rows, COV_KSTEP);
-        const int64_t rows_per = (b + MEAN_SPLITS - 1) / MEAN_SPLITS;
-        const int nsplit = int((b + rows_per - 1) / rows_per);
+        const RowSplits sp(b, MEAN_SPLITS);
+        const int64_t rows_per = sp.rows_per;
+        const int nsplit = int(sp.count);
         const int Tn = int(f_pad / COV_T);
         const int ntile = Tn * (Tn + 1) / 2;
         const auto [ksplit, k_per] = frisk_proj::cov_ksplit(rows_pad, ntile);
@@ -168,11 +151,11 @@ struct State {
         double* dpart = part.ensure(2 * size_t(nsplit) * size_t(f));
         double* dcov = covpart.ensure(size_t(ksplit) * size_t(ntile) * COV_T * COV_T);
         if (!dX || !dA || !dpart || !dcov) return -2;
-        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(timer.record(0));
         FRISK_HIP_CHECK(hipMemcpy(dX, X_in, size_t(b) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
-        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(timer.record(1));
         const unsigned gf = unsigned((f + 255) / 256);
-        hipLaunchKernelGGL(frisk_proj::proj_colsum_part, dim3(gf, unsigned(nsplit)), dim3(256), 0, 0, dX, b, f, rows_per, dpart);
+        hipLaunchKernelGGL(frisk_common::colsum_part<MEAN_UNROLL>, dim3(gf, unsigned(nsplit)), dim3(256), 0, 0, dX, b, f, rows_per, dpart);
         hipLaunchKernelGGL(ipca_colsum, dim3(gf), dim3(256), 0, 0, dpart, nsplit, b, f, bsum, T);
         hipLaunchKernelGGL(ipca_dev_part, dim3(gf, unsigned(nsplit)), dim3(256), 0, 0, dX, T, b, f, rows_per, nsplit, dpart);
         hipLaunchKernelGGL(ipca_merge, dim3(gf), dim3(256), 0, 0, dpart, nsplit, bsum, mean, var, seen, b, f, mean_new, var_new);
@@ -181,18 +164,15 @@ struct State {
         const unsigned gs = unsigned(std::min<int64_t>((total + 255) / 256, 65536));
         hipLaunchKernelGGL(ipca_stack, dim3(gs), dim3(256), 0, 0, dX, T, mean_new, mean, S, Vt, seen, b, f, d, coef, rows_pad, f_pad,
                            dA);
-        FRISK_HIP_CHECK(hipEventRecord(ev[2], 0));
+        FRISK_HIP_CHECK(timer.record(2));
         hipLaunchKernelGGL(frisk_proj::proj_cov_part, dim3(unsigned(ntile), unsigned(ksplit)), dim3(256), 0, 0, dA, f_pad, rows_pad,
                            k_per, Tn, ntile, dcov);
         hipLaunchKernelGGL(frisk_proj::proj_cov_reduce, dim3(unsigned(ntile)), dim3(256), 0, 0, dcov, int(ksplit), Tn, ntile, f, 1.0, G);
-        FRISK_HIP_CHECK(hipEventRecord(ev[3], 0));
+        FRISK_HIP_CHECK(timer.record(3));
         FRISK_HIP_CHECK(hipGetLastError());
         FRISK_HIP_CHECK(hipMemcpy(G_out, G, size_t(f) * size_t(f) * sizeof(double), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 3; ++k) {
-            float t = 0.f;
-            FRISK_HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-            ms[k] = double(t);
-        }
+        for (int k = 0; k < 3; ++k)
+            if (timer.elapsed(k, k + 1, ms[k])) return -2;
         pending_b = b;
         return 0;
     }
@@ -200,7 +180,7 @@ struct State {
     // S[d], Vt[d][f] (host) become the decomposition; Vfd is its transpose for the transform kernel.
     int upload_sv(const double* S_in, const double* Vt_in) {
         std::vector<double> vfd(size_t(f) * size_t(d));
-        frisk_proj::transpose(Vt_in, d, f, vfd.data());
+        frisk_common::transpose(Vt_in, d, f, vfd.data());
         FRISK_HIP_CHECK(hipMemcpy(S, S_in, size_t(d) * sizeof(double), hipMemcpyHostToDevice));
         FRISK_HIP_CHECK(hipMemcpy(Vt, Vt_in, size_t(d) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
         FRISK_HIP_CHECK(hipMemcpy(Vfd, vfd.data(), vfd.size() * sizeof(double), hipMemcpyHostToDevice));

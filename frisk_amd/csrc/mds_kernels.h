@@ -14,84 +14,35 @@
 //                    row i of B X without its cancelling diagonal; X_{t+1} = (1 / n) that sum.  Per-thread sums, block_sum
 //                    per entry, per-block stress partials summed in block order by one block.
 // One pass on X_t yields stress(X_t) and X_{t+1}; the host driver evaluates sklearn's stop rule in double after each pass.
-// Included from frisk_analysis.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
+// Included from frisk_analysis.hip; the C entry points there are thin wrappers of the driver below.  The tile kernel of the
+// dissimilarities is analysis_common.h's pair_tile, shared with the spectral affinities; block_sum and load_rows are shared with t-SNE.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <vector>
 
-#include "proj_kernels.h"
+#include "analysis_common.h"
 
 namespace frisk_mds_impl {
 
-using frisk_proj::block_sum;
-using frisk_proj::load_rows;
-using frisk_proj::rows_per_block;
+using frisk_common::block_sum;
+using frisk_common::load_rows;
+using frisk_common::rows_per_block;
 
 constexpr int MAX_D = 64;           // output dims
 constexpr int64_t MAX_N = 50000;    // dense n x n FP64 dissimilarities: 20 GB at the cap
 constexpr double ZERO_DIST = 1e-5;  // sklearn: distances[distances == 0] = 1e-5
-constexpr int DIS_T = 64;           // dissimilarity tile (rows and columns)
-constexpr int DIS_KC = 16;          // input columns per LDS chunk
+constexpr int DIS_T = frisk_common::PAIR_T;         // dissimilarity tile (rows and columns)
+constexpr int DIS_KC = frisk_common::PAIR_KC;       // input columns per LDS chunk
 
 // ---------------------------------------------------------------------------------------------------------- dissimilarities
-// Block (bx, by), bx >= by, 256 threads: the tile of rows r0 = 64 by, columns c0 = 64 bx.  Thread (ty, tx) = (tid / 16, tid % 16)
-// owns rows r0 + ty + 16 a and columns c0 + tx + 16 b (a, b < 4).  The sums are written to D[r][c] and D[c][r] through one LDS
-// transpose, so both halves come from the same value.
-__global__ __launch_bounds__(256) void mds_dissimilarities(const double* __restrict__ X, int64_t n, int64_t f,
-                                                           double* __restrict__ D) {
-    if (blockIdx.x < blockIdx.y) return;
-    __shared__ double A[DIS_KC][DIS_T + 1], B[DIS_KC][DIS_T + 1];
-    __shared__ double T[DIS_T][DIS_T + 1];
-    const int64_t r0 = int64_t(blockIdx.y) * DIS_T, c0 = int64_t(blockIdx.x) * DIS_T;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    double s[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
-    for (int64_t k0 = 0; k0 < f; k0 += DIS_KC) {
-        for (int e = threadIdx.x; e < DIS_T * DIS_KC; e += 256) {
-            const int r = e / DIS_KC, k = e % DIS_KC;
-            const bool kin = k0 + k < f;
-            A[k][r] = (kin && r0 + r < n) ? X[(r0 + r) * f + k0 + k] : 0.0;
-            B[k][r] = (kin && c0 + r < n) ? X[(c0 + r) * f + k0 + k] : 0.0;
-        }
-        __syncthreads();
-        const int kc = int(f - k0 < DIS_KC ? f - k0 : DIS_KC);
-        for (int k = 0; k < kc; ++k) {
-            double xa[4], xb[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) xa[a] = A[k][ty + 16 * a];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) xb[b] = B[k][tx + 16 * b];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const double t = xa[a] - xb[b];
-                    s[a][b] += t * t;
-                }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int u = ty + 16 * a, v = tx + 16 * b;
-            T[u][v] = (r0 + u == c0 + v) ? 0.0 : sqrt(s[a][b]);
-        }
-    __syncthreads();
-    for (int e = threadIdx.x; e < DIS_T * DIS_T; e += 256) {
-        const int u = e / DIS_T, v = e % DIS_T;
-        if (r0 + u < n && c0 + v < n) D[(r0 + u) * n + c0 + v] = T[u][v];       // the tile, row by row
-        if (c0 + u < n && r0 + v < n) D[(c0 + u) * n + r0 + v] = T[v][u];       // its mirror, row by row
-    }
-}
+// pair_tile's value of a pair from its sum of squared differences: D_ij = sqrt(s)
+struct Distance {
+    __device__ double operator()(double s) const { return sqrt(s); }
+};
 
 // ---------------------------------------------------------------------------------------------------------- one SMACOF step
 // From X_t = Y: part[2 b] = sum over the block's rows i and all j of (dist_ij - D_ij)^2, part[2 b + 1] = of dist_ij^2; with
@@ -180,7 +131,7 @@ struct State {
     int device = 0;
     int64_t n = 0, f = 0;
     int d = 0;
-    frisk_proj::DevMem mem;
+    frisk_common::DevMem mem;
     double *D = nullptr, *Ya = nullptr, *Yb = nullptr, *part = nullptr, *sums = nullptr;
 
     int64_t step_blocks() const { return (n + rows_per_block(d) - 1) / rows_per_block(d); }
@@ -197,7 +148,7 @@ struct State {
         if (!D || !Ya || !Yb || !part || !sums || !X) return -2;
         FRISK_HIP_CHECK(hipMemcpy(X, X_in, size_t(n) * size_t(f) * sizeof(double), hipMemcpyHostToDevice));
         const unsigned T = unsigned((n + DIS_T - 1) / DIS_T);
-        hipLaunchKernelGGL(mds_dissimilarities, dim3(T, T), dim3(256), 0, 0, X, n, f, D);
+        hipLaunchKernelGGL((frisk_common::pair_tile<Distance, int64_t>), dim3(T, T), dim3(256), 0, 0, X, n, f, Distance(), D);
         FRISK_HIP_CHECK(hipGetLastError());
         FRISK_HIP_CHECK(hipDeviceSynchronize());
         return 0;
@@ -206,7 +157,7 @@ struct State {
     // One pass from Y: stress and sum of squared distances of Y to the host (sums_out[2]); with guttman, Ynext = the next state.
     int step(const double* Y, double* Ynext, int guttman, double* sums_out) {
         const unsigned nb = unsigned(step_blocks());
-        frisk_proj::for_rows_per_block<MAX_D>(d, [&](auto maxd, auto r) {
+        frisk_common::for_rows_per_block<MAX_D>(d, [&](auto maxd, auto r) {
             hipLaunchKernelGGL((mds_step<decltype(maxd)::value, decltype(r)::value>), dim3(nb), dim3(256), 0, 0, Y, D, n, d, guttman, Ynext, part);
         });
         hipLaunchKernelGGL(mds_sum_parts, dim3(1), dim3(256), 0, 0, part, int64_t(nb), sums);

@@ -15,21 +15,22 @@
 //                                      block_sum per block, the blocks in index order by one thread (nmf_sum_parts).
 // The two products serve the coordinate descent (p = d) and the range finder of the initialisation (p up to d + 10).  They are
 // plain VALU: each is bound by reading X once (DESIGN.md section 9.4 has the measured fraction of the HBM rate).
-// Included from frisk_analysis.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
+// Included from frisk_analysis.hip before spectral_kernels.h; the C entry points there are thin wrappers of the driver below.  The
+// sums, the row split, the width dispatch and the event timer are analysis_common.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <vector>
 
-#include "proj_kernels.h"
+#include "analysis_common.h"
 
 namespace frisk_nmf_impl {
 
-using frisk_proj::block_sum;
-using frisk_proj::wave_sum;
+using frisk_common::block_sum;
+using frisk_common::for_width;
+using frisk_common::wave_sum;
 
 constexpr int NMF_MAX_D = 16;       // components
 constexpr int NMF_MAX_P = 26;       // columns of a product: d plus the range finder's 10 oversamples
@@ -182,22 +183,14 @@ struct State {
     int64_t n = 0, f = 0;
     int d = 0;
     bool frozen = false;                // HHt and XHt hold the products of the current Ht (transform_prepare)
-    frisk_proj::DevMem mem;
+    frisk_common::DevMem mem;
     double *X = nullptr, *W = nullptr, *Ht = nullptr, *XHt = nullptr, *XtW = nullptr, *G = nullptr;
     double *Qn = nullptr, *Qf = nullptr;        // a product's right factor and result: n x NMF_MAX_P, f x NMF_MAX_P
     double *xpart = nullptr, *vpart = nullptr, *viol = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    frisk_common::EventTimer<5> timer;
     double ms[3] = {0.0, 0.0, 0.0};     // of the last call: X Q (or X Ht), XT Q' (or XT W), the whole step
 
-    ~State() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-
-    int64_t xtq_rows_per() const {
-        const int64_t nsplit = std::min<int64_t>(XTQ_SPLITS, (n + XTQ_MIN_ROWS - 1) / XTQ_MIN_ROWS);
-        return (n + nsplit - 1) / nsplit;
-    }
-    int64_t xtq_splits() const { return (n + xtq_rows_per() - 1) / xtq_rows_per(); }
+    frisk_common::RowSplits xtq_splits() const { return {n, XTQ_SPLITS, XTQ_MIN_ROWS}; }
     int64_t sweep_blocks(int64_t m) const { return (m + 255) / 256; }
 
     int create(const double* X_in) {
@@ -210,11 +203,11 @@ struct State {
         G = mem.get<double>(sd * sd);
         Qn = mem.get<double>(sn * NMF_MAX_P);
         Qf = mem.get<double>(sf * NMF_MAX_P);
-        xpart = mem.get<double>(size_t(xtq_splits()) * sf * NMF_MAX_P);
+        xpart = mem.get<double>(size_t(xtq_splits().count) * sf * NMF_MAX_P);
         vpart = mem.get<double>(size_t(sweep_blocks(std::max(n, f))));
         viol = mem.get<double>(2);
         if (!X || !W || !Ht || !XHt || !XtW || !G || !Qn || !Qf || !xpart || !vpart || !viol) return -2;
-        for (hipEvent_t& e : ev) FRISK_HIP_CHECK(hipEventCreate(&e));
+        if (timer.create()) return -2;
         FRISK_HIP_CHECK(hipMemcpy(X, X_in, sn * sf * sizeof(double), hipMemcpyHostToDevice));
         FRISK_HIP_CHECK(hipMemset(W, 0, sn * sd * sizeof(double)));
         FRISK_HIP_CHECK(hipMemset(Ht, 0, sf * sd * sizeof(double)));
@@ -223,62 +216,52 @@ struct State {
 
     // Y (n x p, device) = X Q (Q f x p, device)
     void launch_xq(const double* Q, int p, double* Y) {
-        auto grid = [&](int R) { return dim3(unsigned((n + 4 * R - 1) / (4 * R))); };
-        if (p <= 2) hipLaunchKernelGGL((nmf_xq<2, 4>), grid(4), dim3(256), 0, 0, X, Q, n, f, p, Y);
-        else if (p <= 8) hipLaunchKernelGGL((nmf_xq<8, 4>), grid(4), dim3(256), 0, 0, X, Q, n, f, p, Y);
-        else if (p <= 16) hipLaunchKernelGGL((nmf_xq<16, 2>), grid(2), dim3(256), 0, 0, X, Q, n, f, p, Y);
-        else hipLaunchKernelGGL((nmf_xq<NMF_MAX_P, 1>), grid(1), dim3(256), 0, 0, X, Q, n, f, p, Y);
+        for_width<2, 8, 16, NMF_MAX_P>(p, [&](auto pmax) {
+            constexpr int PMAX = decltype(pmax)::value, R = PMAX <= 8 ? 4 : PMAX <= 16 ? 2 : 1;         // rows per wave
+            hipLaunchKernelGGL((nmf_xq<PMAX, R>), dim3(unsigned((n + 4 * R - 1) / (4 * R))), dim3(256), 0, 0, X, Q, n, f, p, Y);
+        });
     }
 
     // Z (f x p, device) = XT Q (Q n x p, device)
     void launch_xtq(const double* Q, int p, double* Z) {
-        const int64_t rows_per = xtq_rows_per();
-        const dim3 grid(unsigned((f + 63) / 64), unsigned(xtq_splits()));
-        if (p <= 2) hipLaunchKernelGGL((nmf_xtq_part<2>), grid, dim3(64), 0, 0, X, Q, n, f, p, rows_per, xpart);
-        else if (p <= 8) hipLaunchKernelGGL((nmf_xtq_part<8>), grid, dim3(64), 0, 0, X, Q, n, f, p, rows_per, xpart);
-        else if (p <= 16) hipLaunchKernelGGL((nmf_xtq_part<16>), grid, dim3(64), 0, 0, X, Q, n, f, p, rows_per, xpart);
-        else hipLaunchKernelGGL((nmf_xtq_part<NMF_MAX_P>), grid, dim3(64), 0, 0, X, Q, n, f, p, rows_per, xpart);
+        const frisk_common::RowSplits sp = xtq_splits();
+        const dim3 grid(unsigned((f + 63) / 64), unsigned(sp.count));
+        for_width<2, 8, 16, NMF_MAX_P>(p, [&](auto pmax) {
+            hipLaunchKernelGGL((nmf_xtq_part<decltype(pmax)::value>), grid, dim3(64), 0, 0, X, Q, n, f, p, sp.rows_per, xpart);
+        });
         const int64_t total = f * p;
-        hipLaunchKernelGGL(nmf_xtq_reduce, dim3(unsigned((total + 255) / 256)), dim3(256), 0, 0, xpart, int(xtq_splits()), total, Z);
+        hipLaunchKernelGGL(nmf_xtq_reduce, dim3(unsigned((total + 255) / 256)), dim3(256), 0, 0, xpart, int(sp.count), total, Z);
     }
 
     // One sweep over the m rows of A (m x d) against the Gram matrix in G and the product P (m x d); its violation to out.
     void launch_sweep(double* A, const double* P, int64_t m, double* out) {
         const unsigned nb = unsigned(sweep_blocks(m));
-        if (d <= 2) hipLaunchKernelGGL((nmf_sweep<2>), dim3(nb), dim3(256), 0, 0, A, G, P, m, d, vpart);
-        else if (d <= 4) hipLaunchKernelGGL((nmf_sweep<4>), dim3(nb), dim3(256), 0, 0, A, G, P, m, d, vpart);
-        else if (d <= 8) hipLaunchKernelGGL((nmf_sweep<8>), dim3(nb), dim3(256), 0, 0, A, G, P, m, d, vpart);
-        else hipLaunchKernelGGL((nmf_sweep<NMF_MAX_D>), dim3(nb), dim3(256), 0, 0, A, G, P, m, d, vpart);
+        for_width<2, 4, 8, NMF_MAX_D>(d, [&](auto dmax) {
+            hipLaunchKernelGGL((nmf_sweep<decltype(dmax)::value>), dim3(nb), dim3(256), 0, 0, A, G, P, m, d, vpart);
+        });
         hipLaunchKernelGGL(nmf_sum_parts, dim3(1), dim3(64), 0, 0, vpart, int64_t(nb), out);
-    }
-
-    int elapsed(int k, int a, int b) {
-        float t = 0.f;
-        FRISK_HIP_CHECK(hipEventElapsedTime(&t, ev[a], ev[b]));
-        ms[k] = double(t);
-        return 0;
     }
 
     // Y_out[n][p] = X Q_in[f][p] (host buffers)
     int xq(const double* Q_in, int p, double* Y_out) {
         FRISK_HIP_CHECK(hipMemcpy(Qf, Q_in, size_t(f) * size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(timer.record(0));
         launch_xq(Qf, p, Qn);
-        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(timer.record(1));
         FRISK_HIP_CHECK(hipGetLastError());
         FRISK_HIP_CHECK(hipMemcpy(Y_out, Qn, size_t(n) * size_t(p) * sizeof(double), hipMemcpyDeviceToHost));
-        return elapsed(0, 0, 1);
+        return timer.elapsed(0, 1, ms[0]);
     }
 
     // Z_out[f][p] = XT Q_in[n][p] (host buffers)
     int xtq(const double* Q_in, int p, double* Z_out) {
         FRISK_HIP_CHECK(hipMemcpy(Qn, Q_in, size_t(n) * size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(timer.record(0));
         launch_xtq(Qn, p, Qf);
-        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(timer.record(1));
         FRISK_HIP_CHECK(hipGetLastError());
         FRISK_HIP_CHECK(hipMemcpy(Z_out, Qf, size_t(f) * size_t(p) * sizeof(double), hipMemcpyDeviceToHost));
-        return elapsed(1, 0, 1);
+        return timer.elapsed(0, 1, ms[1]);
     }
 
     // HHt (in G) and X Ht of the current Ht; they stay valid until Ht changes.
@@ -292,20 +275,20 @@ struct State {
 
     // One iteration of _fit_coordinate_descent: the W sweep, then with update_H the Ht sweep on XT.  violation = the sum of both.
     int step(int update_H, double* violation) {
-        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(timer.record(0));
         if (!frozen) {
             hipLaunchKernelGGL(nmf_gram, dim3(unsigned(d * d)), dim3(256), 0, 0, Ht, f, d, G);
             launch_xq(Ht, d, XHt);
         }
-        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(timer.record(1));
         launch_sweep(W, XHt, n, viol);
         frozen = !update_H;             // without update_H, G and XHt stay those of the unchanged Ht
         if (update_H) hipLaunchKernelGGL(nmf_gram, dim3(unsigned(d * d)), dim3(256), 0, 0, W, n, d, G);
-        FRISK_HIP_CHECK(hipEventRecord(ev[2], 0));
+        FRISK_HIP_CHECK(timer.record(2));
         if (update_H) launch_xtq(W, d, XtW);
-        FRISK_HIP_CHECK(hipEventRecord(ev[3], 0));
+        FRISK_HIP_CHECK(timer.record(3));
         if (update_H) launch_sweep(Ht, XtW, f, viol + 1);
-        FRISK_HIP_CHECK(hipEventRecord(ev[4], 0));
+        FRISK_HIP_CHECK(timer.record(4));
         FRISK_HIP_CHECK(hipGetLastError());
         double v[2] = {0.0, 0.0};
         FRISK_HIP_CHECK(hipMemcpy(v, viol, (update_H ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost));
@@ -313,8 +296,8 @@ struct State {
         total += v[0];
         if (update_H) total += v[1];
         *violation = total;
-        if (elapsed(0, 0, 1) || elapsed(1, 2, 3)) return -2;
-        return elapsed(2, 0, 4);
+        if (timer.elapsed(0, 1, ms[0]) || timer.elapsed(2, 3, ms[1])) return -2;
+        return timer.elapsed(0, 4, ms[2]);
     }
 };
 

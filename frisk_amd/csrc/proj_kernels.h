@@ -2,13 +2,15 @@
 // PCA (column mean, centring, covariance, transform), DBSCAN and Lloyd's k-means, FP64 throughout.
 //
 // Every reduction has a fixed order and no floating-point atomic, so every output is bit-identical from run to run:
-//   column sums   per-split partials over fixed row ranges, summed split 0, 1, ... by one thread per column;
+//   column sums   per-split partials over fixed row ranges (frisk_common::colsum_part), summed split 0, 1, ... by one thread per
+//                 column;
 //   covariance    v_mfma_f64_16x16x4_f64 over fixed row ranges (one per split), partial tiles summed in split order;
 //   transform     one wave per row, lanes over features in stride order, then a fixed xor butterfly;
 //   DBSCAN        integer counts; union-find whose result does not depend on the order of the unions (see dbscan below);
 //   k-means       per-block partials (fixed wave butterfly + waves in order), blocks summed in order by one thread per value;
 //                 empty clusters take the farthest points by exact comparisons (descending distance, lowest index on a tie).
-// Included from frisk_analysis.hip; the C entry points there are thin wrappers of the drivers below.
+// Included from frisk_analysis.hip; the C entry points there are thin wrappers of the drivers below.  What the other analysis
+// headers share with this one (device memory, the fixed-order sums, the column-sum kernel, the dispatches) is analysis_common.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,36 +18,29 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <type_traits>
 #include <vector>
 
-// every host driver of the analysis headers returns 0 or -2 (a HIP call failed)
-#define FRISK_HIP_CHECK(call)                               \
-    do {                                                    \
-        if ((call) != hipSuccess) return -2;                \
-    } while (0)
+#include "analysis_common.h"
 
 namespace frisk_proj {
+
+using frisk_common::block_sum;
+using frisk_common::colsum_part;
+using frisk_common::DevMem;
+using frisk_common::for_width;
+using frisk_common::round_up;
+using frisk_common::RowSplits;
+using frisk_common::wave_sum;
 
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
 constexpr int COV_T = 64;           // covariance output tile (4 waves of 32 x 32, each 2 x 2 MFMA tiles of 16 x 16)
 constexpr int COV_KSTEP = 16;       // rows per unrolled step of the K loop; padded row count and split length are multiples
 constexpr int MEAN_SPLITS = 64;     // row ranges of the column sums
+constexpr int MEAN_UNROLL = 1;      // ... whose row loop is not unrolled (what the compiler does with it unasked)
 
 // ---------------------------------------------------------------------------------------------------------- PCA
-// part[s][c] = sum of X[r][c] over the rows r of split s, in row order
-__global__ __launch_bounds__(256) void proj_colsum_part(const double* __restrict__ X, int64_t n, int64_t f, int64_t rows_per,
-                                                        double* __restrict__ part) {
-    const int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (c >= f) return;
-    const int64_t r0 = int64_t(blockIdx.y) * rows_per;
-    const int64_t r1 = r0 + rows_per < n ? r0 + rows_per : n;
-    double s = 0.0;
-    for (int64_t r = r0; r < r1; ++r) s += X[r * f + c];
-    part[int64_t(blockIdx.y) * f + c] = s;
-}
-
+// mean[c] = (the range partials of column c, frisk_common::colsum_part, in range order) / n
 __global__ __launch_bounds__(256) void proj_colmean(const double* __restrict__ part, int nsplit, int64_t n, int64_t f,
                                                     double* __restrict__ mean) {
     const int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x;
@@ -126,12 +121,6 @@ __global__ __launch_bounds__(256) void proj_cov_reduce(const double* __restrict_
         cov[i * f + j] = s;
         cov[j * f + i] = s;
     }
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 // Y[r][q] = sum_c Xc[r][c] V[c][q]: one wave per row, lane l takes features l, l + 64, ... in order
@@ -246,35 +235,6 @@ __global__ __launch_bounds__(256) void db_compress(int64_t n, const int32_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------------------- k-means
-// sum of v over the block, in a fixed order: xor butterfly inside each wave, then the four waves in order
-__device__ inline double block_sum(double v, double* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return s;
-}
-
-// Rows i0 .. i0 + R - 1 of a block in LDS, zero beyond n and beyond d (t-SNE's passes, MDS's step: each thread then takes the
-// points j = tid, tid + 256, ... in order).
-template <int MAXD, int R>
-__device__ inline void load_rows(const double* __restrict__ Y, int64_t n, int d, int64_t i0, double (*yi)[MAXD]) {
-    for (int e = threadIdx.x; e < R * MAXD; e += 256) {
-        const int r = e / MAXD, k = e % MAXD;
-        yi[r][k] = (i0 + r < n && k < d) ? Y[(i0 + r) * d + k] : 0.0;
-    }
-    __syncthreads();
-}
-// ... how many rows that is at output dimension d, and the instantiation that goes with it: f(MAXD, R) as integral constants
-inline int rows_per_block(int d) { return d <= 4 ? 8 : d <= 16 ? 2 : 1; }
-template <int MAX_D, typename F>
-inline void for_rows_per_block(int d, F&& f) {
-    if (d <= 4) f(std::integral_constant<int, 4>(), std::integral_constant<int, 8>());
-    else if (d <= 16) f(std::integral_constant<int, 16>(), std::integral_constant<int, 2>());
-    else f(std::integral_constant<int, MAX_D>(), std::integral_constant<int, 1>());
-}
-
 // One Lloyd step, first half: nearest centre of each point (lowest index on a tie), whether any label changed, dist[i] = the
 // squared distance of point i to that centre, and per block part[b][c (d+1) + q] = sum of coordinate q (q = d: the count) of the
 // block's points of centre c, part[b][k (d+1)] = their squared distances.
@@ -437,33 +397,6 @@ __global__ __launch_bounds__(256) void km_update(const double* __restrict__ part
 }
 
 // ---------------------------------------------------------------------------------------------------------- host drivers
-// Device memory of one call, freed on every return path.
-struct DevMem {
-    std::vector<void*> ptrs;
-    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
-    template <typename T>
-    T* get(size_t count) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (count ? count : 1) * sizeof(T)) != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-};
-
-// The calling thread's current device is restored on return.
-struct OnDevice {
-    int prev = -1;
-    bool ok = false;
-    explicit OnDevice(int device) {
-        int ndev = 0;
-        if (hipGetDevice(&prev) != hipSuccess || hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return;
-        ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~OnDevice() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
 // Centred, zero-padded copy of X on the device; mean (length f) on the device.  Returns 0 or -2.
 struct Centred {
     double* Xc = nullptr;
@@ -483,12 +416,11 @@ inline int upload_centred(DevMem& mem, const double* X, int64_t n, int64_t f, co
     if (mean_in) {
         FRISK_HIP_CHECK(hipMemcpy(out.mean, mean_in, size_t(f) * sizeof(double), hipMemcpyHostToDevice));
     } else {
-        const int64_t rows_per = (n + MEAN_SPLITS - 1) / MEAN_SPLITS;
-        const int nsplit = int((n + rows_per - 1) / rows_per);
-        double* part = mem.get<double>(size_t(nsplit) * size_t(f));
+        const RowSplits sp(n, MEAN_SPLITS);
+        double* part = mem.get<double>(size_t(sp.count) * size_t(f));
         if (!part) return -2;
-        hipLaunchKernelGGL(proj_colsum_part, dim3(gf, unsigned(nsplit)), dim3(256), 0, 0, dX, n, f, rows_per, part);
-        hipLaunchKernelGGL(proj_colmean, dim3(gf), dim3(256), 0, 0, part, nsplit, n, f, out.mean);
+        hipLaunchKernelGGL(colsum_part<MEAN_UNROLL>, dim3(gf, unsigned(sp.count)), dim3(256), 0, 0, dX, n, f, sp.rows_per, part);
+        hipLaunchKernelGGL(proj_colmean, dim3(gf), dim3(256), 0, 0, part, int(sp.count), n, f, out.mean);
     }
     const int64_t total = out.n_pad * out.f_pad;
     const unsigned gc = unsigned(std::min<int64_t>((total + 255) / 256, 65536));
@@ -507,12 +439,6 @@ inline KSplit cov_ksplit(int64_t n_pad, int ntile) {
     nsplit = std::min<int64_t>(nsplit, n_pad / COV_KSTEP);
     const int64_t rows_per = round_up((n_pad + nsplit - 1) / nsplit, COV_KSTEP);
     return {(n_pad + rows_per - 1) / rows_per, rows_per};
-}
-
-// dst[cols][rows] = the transpose of src[rows][cols], on the host (H and Vt arrive as [d][f]; the kernels read [f][d])
-inline void transpose(const double* src, int64_t rows, int64_t cols, double* dst) {
-    for (int64_t r = 0; r < rows; ++r)
-        for (int64_t c = 0; c < cols; ++c) dst[size_t(c) * size_t(rows) + size_t(r)] = src[size_t(r) * size_t(cols) + size_t(c)];
 }
 
 // mean_out[f], cov_out[f*f] = XcT Xc / (n - 1) (n = 1: / 1).  Returns 0 or -2.
@@ -556,9 +482,9 @@ constexpr int MAX_DIMS = 64;        // largest point dimension of dbscan / kmean
 template <int MODE>
 inline void db_launch(int d, unsigned grid, const double* Y, int64_t n, double eps, int32_t ms, int32_t* cnt, int32_t* P, int32_t* lab) {
     const double lo = eps * eps * (1.0 - 4e-15), hi = eps * eps * (1.0 + 4e-15);
-    if (d <= 4) hipLaunchKernelGGL((db_pairs<4, MODE>), dim3(grid), dim3(256), 0, 0, Y, n, d, eps, lo, hi, ms, cnt, P, lab);
-    else if (d <= 16) hipLaunchKernelGGL((db_pairs<16, MODE>), dim3(grid), dim3(256), 0, 0, Y, n, d, eps, lo, hi, ms, cnt, P, lab);
-    else hipLaunchKernelGGL((db_pairs<MAX_DIMS, MODE>), dim3(grid), dim3(256), 0, 0, Y, n, d, eps, lo, hi, ms, cnt, P, lab);
+    for_width<4, 16, MAX_DIMS>(d, [&](auto maxd) {
+        hipLaunchKernelGGL((db_pairs<decltype(maxd)::value, MODE>), dim3(grid), dim3(256), 0, 0, Y, n, d, eps, lo, hi, ms, cnt, P, lab);
+    });
 }
 
 // labels_out[n]: cluster ids 0, 1, ... in increasing order of their smallest core index; -1 = noise.  Returns 0 or -2.
@@ -612,10 +538,10 @@ inline int kmeans(const double* Y, int64_t n, int d, int k, const double* init_c
     FRISK_HIP_CHECK(hipMemcpy(C, init_centers, size_t(k) * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
     FRISK_HIP_CHECK(hipMemset(lab, 0xff, size_t(n) * sizeof(int32_t)));          // -1: every label changes in the first step
     auto step = [&](double* from, double* to) {
-        if (d <= 4) hipLaunchKernelGGL(km_assign<4>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, dist, part);
-        else if (d <= 16)
-            hipLaunchKernelGGL(km_assign<16>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, dist, part);
-        else hipLaunchKernelGGL(km_assign<MAX_DIMS>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed, dist, part);
+        for_width<4, 16, MAX_DIMS>(d, [&](auto maxd) {
+            hipLaunchKernelGGL(km_assign<decltype(maxd)::value>, dim3(unsigned(nblocks)), dim3(256), 0, 0, dY, n, d, k, from, lab, changed,
+                               dist, part);
+        });
         hipLaunchKernelGGL(km_update, dim3(1), dim3(256), 0, 0, part, nblocks, dY, n, d, k, lab, dist, from, to, S, W, emp, far, res);
     };
     int32_t it = 0;

@@ -10,7 +10,7 @@
 //              thread a 4 x 4 micro-tile; the tile and its mirror are written from the same values, so A0 is exactly symmetric, and
 //              the diagonal is exactly 0 (scipy drops it).
 //   degrees    w_j = sum_i A0_ij: one lane per column, the rows in `splits` contiguous ranges, each in row order
-//              (spec_colsum_part); the ranges summed in range order, w == 0 replaced by 1 and counted, dd = sqrt(w) (spec_degrees).
+//              (colsum_part); the ranges summed in range order, w == 0 replaced by 1 and counted, dd = sqrt(w) (spec_degrees).
 //   normalise  scipy divides twice, m /= dd (per column) then m /= dd[:, None] (per row): r = (A0_ij / dd_j) / dd_i.  Its mirror
 //              entry is r' = (A0_ji / dd_i) / dd_j, the same value but for the last two roundings, up to 2 ulps away.  Every entry is
 //              written as (r + r') / 2, which is symmetric in (i, j), lies between r and r', and is r itself wherever r' == r: M is
@@ -19,100 +19,39 @@
 //              butterfly - the order of frisk_nmf_impl::nmf_xq, and the same bits - with Q staged through LDS per block.  Plain
 //              VALU: bound by reading M once (DESIGN.md section 9.5 has the measured fraction of the HBM rate).
 // The eigen-iteration itself (QR and Rayleigh-Ritz on matrices at most 26 wide) is the host's: frisk_amd/projection.py.
-// Included from frisk_analysis.hip after nmf_kernels.h; the C entry points there are thin wrappers of the driver below.
+// Included from frisk_analysis.hip after nmf_kernels.h; the C entry points there are thin wrappers of the driver below.  The tile
+// kernel of the affinities (pair_tile, shared with MDS), the column sums of the degrees (colsum_part, shared with PCA), wave_sum,
+// the row split, the width dispatch and the event timer are analysis_common.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
-#include "proj_kernels.h"
+#include "analysis_common.h"
 
 namespace frisk_spectral_impl {
 
 constexpr int64_t MAX_N = 50000;        // the dense n x n FP64 buffer: 20 GB at the cap
 constexpr int SPECTRAL_MAX_K = 16;      // clusters = eigenvectors
 constexpr int SPECTRAL_MAX_P = 26;      // columns of a product: k plus the 10 guard columns of the subspace iteration
-constexpr int AFF_T = 64;               // affinity tile (rows and columns)
-constexpr int AFF_KC = 16;              // columns of Y per LDS chunk
+constexpr int AFF_T = frisk_common::PAIR_T;         // affinity tile (rows and columns)
+constexpr int AFF_KC = frisk_common::PAIR_KC;       // columns of Y per LDS chunk
 constexpr int DEG_SPLITS = 256;         // most row ranges of the column sums
 constexpr int DEG_MIN_ROWS = 32;        // fewest rows per range (but for the last)
+constexpr int DEG_UNROLL = 4;           // rows per unrolled step of a range's sum
 
 // ---------------------------------------------------------------------------------------------------------- affinity
-// Block (bx, by), bx >= by, 256 threads: the tile of rows r0 = 64 by, columns c0 = 64 bx.  Thread (ty, tx) = (tid / 16, tid % 16)
-// owns rows r0 + ty + 16 a and columns c0 + tx + 16 b (a, b < 4).  The values are written to A[r][c] and A[c][r] through one LDS
-// transpose, so both halves come from the same value.
-__global__ __launch_bounds__(256) void spec_affinity(const double* __restrict__ Y, int64_t n, int d, double gamma,
-                                                     double* __restrict__ A) {
-    if (blockIdx.x < blockIdx.y) return;
-    __shared__ double P[AFF_KC][AFF_T + 1], Q[AFF_KC][AFF_T + 1];
-    __shared__ double T[AFF_T][AFF_T + 1];
-    const int64_t r0 = int64_t(blockIdx.y) * AFF_T, c0 = int64_t(blockIdx.x) * AFF_T;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    double s[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s[a][b] = 0.0;
-    for (int k0 = 0; k0 < d; k0 += AFF_KC) {
-        for (int e = threadIdx.x; e < AFF_T * AFF_KC; e += 256) {
-            const int r = e / AFF_KC, k = e % AFF_KC;
-            const bool kin = k0 + k < d;
-            P[k][r] = (kin && r0 + r < n) ? Y[(r0 + r) * d + k0 + k] : 0.0;
-            Q[k][r] = (kin && c0 + r < n) ? Y[(c0 + r) * d + k0 + k] : 0.0;
-        }
-        __syncthreads();
-        const int kc = d - k0 < AFF_KC ? d - k0 : AFF_KC;
-        for (int k = 0; k < kc; ++k) {
-            double ya[4], yb[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) ya[a] = P[k][ty + 16 * a];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) yb[b] = Q[k][tx + 16 * b];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const double t = ya[a] - yb[b];
-                    s[a][b] += t * t;
-                }
-        }
-        __syncthreads();
-    }
-    const double minus_gamma = -gamma;          // sklearn: K *= -gamma; exp(K)
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int u = ty + 16 * a, v = tx + 16 * b;
-            T[u][v] = (r0 + u == c0 + v) ? 0.0 : exp(minus_gamma * s[a][b]);
-        }
-    __syncthreads();
-    for (int e = threadIdx.x; e < AFF_T * AFF_T; e += 256) {
-        const int u = e / AFF_T, v = e % AFF_T;
-        if (r0 + u < n && c0 + v < n) A[(r0 + u) * n + c0 + v] = T[u][v];       // the tile, row by row
-        if (c0 + u < n && r0 + v < n) A[(c0 + u) * n + r0 + v] = T[v][u];       // its mirror, row by row
-    }
-}
+// pair_tile's value of a pair from its sum of squared differences: sklearn's K *= -gamma; exp(K)
+struct Rbf {
+    double minus_gamma;
+    __device__ double operator()(double s) const { return exp(minus_gamma * s); }
+};
 
 // ---------------------------------------------------------------------------------------------------------- degrees
-// part[s][j] = sum over the rows i of range s, in order, of A[i][j].  Block (bx, s): columns 256 bx .. 256 bx + 255.
-__global__ __launch_bounds__(256) void spec_colsum_part(const double* __restrict__ A, int64_t n, int64_t rows_per,
-                                                        double* __restrict__ part) {
-    const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (j >= n) return;
-    const int64_t i0 = int64_t(blockIdx.y) * rows_per;
-    const int64_t i1 = i0 + rows_per < n ? i0 + rows_per : n;
-    double s = 0.0;
-#pragma unroll 4
-    for (int64_t i = i0; i < i1; ++i) s += A[i * n + j];
-    part[int64_t(blockIdx.y) * n + j] = s;
-}
-
-// w_j = the range partials of column j in range order; w == 0 -> 1 (scipy's isolated node), counted in *n_isolated (an integer
-// atomic: exact in any order); dd_j = sqrt(w_j).
+// w_j = the range partials of column j (frisk_common::colsum_part over A0, n x n) in range order; w == 0 -> 1 (scipy's isolated
+// node), counted in *n_isolated (an integer atomic: exact in any order); dd_j = sqrt(w_j).
 __global__ __launch_bounds__(256) void spec_degrees(const double* __restrict__ part, int nsplit, int64_t n, double* __restrict__ dd,
                                                     unsigned long long* __restrict__ n_isolated) {
     const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
@@ -197,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void spec_mq(const double* __restrict__ M, 
 #pragma unroll
         for (int q = 0; q < PMAX; ++q) {
             if (r0 + a < n && q < p) {                      // uniform over the wave
-                const double s = frisk_proj::wave_sum(acc[a][q]);
+                const double s = frisk_common::wave_sum(acc[a][q]);
                 if (lane == 0) Z[(r0 + a) * p + q] = s;
             }
         }
@@ -212,57 +151,43 @@ struct State {
     int d = 0;
     double gamma = 1.0;
     int64_t n_isolated = 0;
-    frisk_proj::DevMem mem;
+    frisk_common::DevMem mem;
     double *Y = nullptr, *A = nullptr, *dd = nullptr, *part = nullptr, *Q = nullptr, *Z = nullptr;
     unsigned long long* iso = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    frisk_common::EventTimer<2> timer;
     double ms[3] = {0.0, 0.0, 0.0};     // of the last call of each kind: affinity, degrees + normalise, a product
 
-    ~State() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-
-    int64_t rows_per() const {
-        const int64_t nsplit = std::min<int64_t>(DEG_SPLITS, (n + DEG_MIN_ROWS - 1) / DEG_MIN_ROWS);
-        return (n + nsplit - 1) / nsplit;
-    }
-    int64_t splits() const { return (n + rows_per() - 1) / rows_per(); }
-
-    int elapsed(int k) {
-        float t = 0.f;
-        FRISK_HIP_CHECK(hipEventSynchronize(ev[1]));
-        FRISK_HIP_CHECK(hipEventElapsedTime(&t, ev[0], ev[1]));
-        ms[k] = double(t);
-        return 0;
-    }
+    frisk_common::RowSplits splits() const { return {n, DEG_SPLITS, DEG_MIN_ROWS}; }
 
     // A <- A0 of Y
     int launch_affinity() {
         const unsigned T = unsigned((n + AFF_T - 1) / AFF_T);
-        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
-        hipLaunchKernelGGL(spec_affinity, dim3(T, T), dim3(256), 0, 0, Y, n, d, gamma, A);
-        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(timer.record(0));
+        hipLaunchKernelGGL((frisk_common::pair_tile<Rbf, int>), dim3(T, T), dim3(256), 0, 0, Y, n, d, Rbf{-gamma}, A);
+        FRISK_HIP_CHECK(timer.record(1));
         FRISK_HIP_CHECK(hipGetLastError());
-        return elapsed(0);
+        return timer.elapsed(0, 1, ms[0]);
     }
 
     // A0 -> M in place; with_degrees: dd and the isolated count from A0 first (they are kept for the life of the handle)
     int launch_normalise(bool with_degrees) {
         const unsigned gx = unsigned((n + 255) / 256);
-        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
+        FRISK_HIP_CHECK(timer.record(0));
         if (with_degrees) {
             FRISK_HIP_CHECK(hipMemsetAsync(iso, 0, sizeof(unsigned long long), 0));
-            hipLaunchKernelGGL(spec_colsum_part, dim3(gx, unsigned(splits())), dim3(256), 0, 0, A, n, rows_per(), part);
-            hipLaunchKernelGGL(spec_degrees, dim3(gx), dim3(256), 0, 0, part, int(splits()), n, dd, iso);
+            const frisk_common::RowSplits sp = splits();
+            hipLaunchKernelGGL(frisk_common::colsum_part<DEG_UNROLL>, dim3(gx, unsigned(sp.count)), dim3(256), 0, 0, A, n, n, sp.rows_per,
+                               part);
+            hipLaunchKernelGGL(spec_degrees, dim3(gx), dim3(256), 0, 0, part, int(sp.count), n, dd, iso);
         }
         hipLaunchKernelGGL(spec_normalise, dim3(gx, unsigned(n)), dim3(256), 0, 0, A, dd, n);
-        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(timer.record(1));
         FRISK_HIP_CHECK(hipGetLastError());
         if (with_degrees) {
             unsigned long long c = 0;
             FRISK_HIP_CHECK(hipMemcpy(&c, iso, sizeof(c), hipMemcpyDeviceToHost));
             n_isolated = int64_t(c);
-            return elapsed(1);
+            return timer.elapsed(0, 1, ms[1]);
         }
         FRISK_HIP_CHECK(hipDeviceSynchronize());
         return 0;
@@ -274,12 +199,12 @@ struct State {
         A = mem.get<double>(sn * sn);
         Y = mem.get<double>(sn * size_t(d));
         dd = mem.get<double>(sn);
-        part = mem.get<double>(size_t(splits()) * sn);
+        part = mem.get<double>(size_t(splits().count) * sn);
         Q = mem.get<double>(sn * SPECTRAL_MAX_P);
         Z = mem.get<double>(sn * SPECTRAL_MAX_P);
         iso = mem.get<unsigned long long>(1);
         if (!A || !Y || !dd || !part || !Q || !Z || !iso) return -2;
-        for (hipEvent_t& e : ev) FRISK_HIP_CHECK(hipEventCreate(&e));
+        if (timer.create()) return -2;
         FRISK_HIP_CHECK(hipMemcpy(Y, Y_in, sn * size_t(d) * sizeof(double), hipMemcpyHostToDevice));
         if (launch_affinity()) return -2;
         return launch_normalise(true);
@@ -295,16 +220,15 @@ struct State {
     // Z_out[n][p] = M Q_in[n][p] (host buffers)
     int mq(const double* Q_in, int p, double* Z_out) {
         FRISK_HIP_CHECK(hipMemcpy(Q, Q_in, size_t(n) * size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-        auto grid = [&](int R) { return dim3(unsigned((n + 4 * R - 1) / (4 * R))); };
-        FRISK_HIP_CHECK(hipEventRecord(ev[0], 0));
-        if (p <= 4) hipLaunchKernelGGL((spec_mq<4, 4>), grid(4), dim3(256), 0, 0, A, Q, n, p, Z);
-        else if (p <= 8) hipLaunchKernelGGL((spec_mq<8, 4>), grid(4), dim3(256), 0, 0, A, Q, n, p, Z);
-        else if (p <= 16) hipLaunchKernelGGL((spec_mq<16, 4>), grid(4), dim3(256), 0, 0, A, Q, n, p, Z);
-        else hipLaunchKernelGGL((spec_mq<SPECTRAL_MAX_P, 2>), grid(2), dim3(256), 0, 0, A, Q, n, p, Z);
-        FRISK_HIP_CHECK(hipEventRecord(ev[1], 0));
+        FRISK_HIP_CHECK(timer.record(0));
+        frisk_common::for_width<4, 8, 16, SPECTRAL_MAX_P>(p, [&](auto pmax) {
+            constexpr int PMAX = decltype(pmax)::value, R = PMAX <= 16 ? 4 : 2;         // rows per wave
+            hipLaunchKernelGGL((spec_mq<PMAX, R>), dim3(unsigned((n + 4 * R - 1) / (4 * R))), dim3(256), 0, 0, A, Q, n, p, Z);
+        });
+        FRISK_HIP_CHECK(timer.record(1));
         FRISK_HIP_CHECK(hipGetLastError());
         FRISK_HIP_CHECK(hipMemcpy(Z_out, Z, size_t(n) * size_t(p) * sizeof(double), hipMemcpyDeviceToHost));
-        return elapsed(2);
+        return timer.elapsed(0, 1, ms[2]);
     }
 };
 

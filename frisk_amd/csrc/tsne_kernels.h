@@ -11,21 +11,24 @@
 //               pass B: dY_i = sum_j (P_ij - Q_ij) num_ij (y_i - y_j) for R rows per block (each thread keeps its points in
 //               registers and its rows' sums in order, block_sum per entry), and on cost iterations sum P log(P / Q);
 //               update: gains, iY, Y per entry, per-block column sums; centring: every block sums the partials in order.
-// Included from frisk_analysis.hip after proj_kernels.h; the C entry points there are thin wrappers of the driver below.
+// Included from frisk_analysis.hip; the C entry points there are thin wrappers of the driver below.  block_sum, load_rows and the
+// dispatches are analysis_common.h's, shared with MDS.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
-#include "proj_kernels.h"
+#include "analysis_common.h"
 
 namespace frisk_tsne_impl {
 
-using frisk_proj::block_sum;
-using frisk_proj::load_rows;
-using frisk_proj::rows_per_block;
+using frisk_common::block_sum;
+using frisk_common::load_rows;
+using frisk_common::rows_per_block;
 
 constexpr int MAX_F = 64;           // input width (the reference's PCA keeps 50 columns)
 constexpr int MAX_D = 64;           // output dims
@@ -41,19 +44,7 @@ constexpr int SYM_T = 32;           // symmetrisation tile
 constexpr int ROW_REGS = int((MAX_N + 1023) / 1024);    // distances per thread of the affinity kernel at the largest n
 
 // ---------------------------------------------------------------------------------------------------------- affinities
-// sum of v over a 1024-thread block in a fixed order: xor butterfly inside each wave, then the 16 waves in order
-__device__ inline double block_sum_1024(double v, double* red) {
-    v = frisk_proj::wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
-
-// One 1024-thread block per row i: D_ij = sum_k (x_ik - x_jk)^2 for j = tid + 1024 c (c < C) kept in registers, the bisection of
+// One 1024-thread block per row i (its sums: block_sum<16>, the 16 waves in order): D_ij = sum_k (x_ik - x_jk)^2 for j = tid + 1024 c (c < C) kept in registers, the bisection of
 // x2p on beta_i (Hbeta without a max-shift: P = exp(-D beta), H = log(sum P) + beta sum(D P) / sum P over j != i), then row i of P
 // = p_j|i (0 on the diagonal).  The row is read from X once, whatever the number of tries.  bad is set when the final sum P is
 // not a positive finite number (the reference's row would be NaN).
@@ -90,8 +81,8 @@ __global__ __launch_bounds__(1024) void tsne_rows(const double* __restrict__ X, 
                 sdp += D[c] * p;
             }
         }
-        sumP = block_sum_1024(sp, red);
-        sdp = block_sum_1024(sdp, red);
+        sumP = block_sum<16>(sp, red);
+        sdp = block_sum<16>(sdp, red);
         H = log(sumP) + b * sdp / sumP;
     };
     double beta = 1.0, betamin = -INFINITY, betamax = INFINITY;
@@ -310,7 +301,7 @@ struct State {
     int f = 0, d = 0;
     double perplexity = 0.0;
     bool have_p = false;
-    frisk_proj::DevMem mem;
+    frisk_common::DevMem mem;
     double *X = nullptr, *P = nullptr, *Y = nullptr, *iY = nullptr, *gains = nullptr, *dY = nullptr;
     double *part = nullptr, *S = nullptr, *cpart = nullptr, *colpart = nullptr, *cost = nullptr, *beta = nullptr;
     int32_t *tries = nullptr, *bad = nullptr;
@@ -348,9 +339,9 @@ struct State {
     int affinities() {
         FRISK_HIP_CHECK(hipMemset(bad, 0, sizeof(int32_t)));
         const double logU = std::log(perplexity);
-        if (n <= 1024) hipLaunchKernelGGL(tsne_rows<1>, dim3(unsigned(n)), dim3(1024), 0, 0, X, n, f, logU, P, beta, tries, bad);
-        else if (n <= 8 * 1024) hipLaunchKernelGGL(tsne_rows<8>, dim3(unsigned(n)), dim3(1024), 0, 0, X, n, f, logU, P, beta, tries, bad);
-        else hipLaunchKernelGGL(tsne_rows<ROW_REGS>, dim3(unsigned(n)), dim3(1024), 0, 0, X, n, f, logU, P, beta, tries, bad);
+        frisk_common::for_width<1, 8, ROW_REGS>(int((n + 1023) / 1024), [&](auto c) {
+            hipLaunchKernelGGL(tsne_rows<decltype(c)::value>, dim3(unsigned(n)), dim3(1024), 0, 0, X, n, f, logU, P, beta, tries, bad);
+        });
         const unsigned T = unsigned((n + SYM_T - 1) / SYM_T);
         hipLaunchKernelGGL(tsne_symmetrise, dim3(T, T), dim3(256), 0, 0, P, n);
         double* rowsum = dY;            // n entries are free here only if d >= 1: dY holds n * d >= n
@@ -372,7 +363,7 @@ struct State {
         for (int t = t0; t < t1; ++t) {
             const int exaggerate = t <= STOP_EXAGGERATION;
             const int with_cost = (t + 1) % 10 == 0;
-            frisk_proj::for_rows_per_block<MAX_D>(d, [&](auto maxd, auto r) {
+            frisk_common::for_rows_per_block<MAX_D>(d, [&](auto maxd, auto r) {
                 launch_passes<decltype(maxd)::value, decltype(r)::value>(Y, P, n, d, part, S, exaggerate, with_cost, dY, cpart);
             });
             if (with_cost) hipLaunchKernelGGL(tsne_sum, dim3(1), dim3(256), 0, 0, cpart, pass_blocks(), cost + (t + 1) / 10 - 1);

@@ -41,13 +41,13 @@ DEG_SPLITS, DEG_MIN_ROWS = 256, 32      # spectral_kernels.h
 
 
 def rows_per(n):
-    """State::rows_per: rows per range of the column sums."""
+    """State::splits().rows_per (RowSplits of analysis_common.h): rows per range of the column sums."""
     nsplit = min(DEG_SPLITS, -(-n // DEG_MIN_ROWS))
     return -(-n // nsplit)
 
 
 def splits(n):
-    """State::splits: the ranges that rows_per() leaves, which is what `part` is sized by and the grid's y."""
+    """State::splits().count: the ranges that rows_per leaves, which is what `part` is sized by and the grid's y."""
     return -(-n // rows_per(n))
 
 

@@ -91,7 +91,7 @@ def test_driver_edges(n, d):
 
 # ------------------------------------------------------------------------------------------------ determinism
 def test_second_calls_are_bit_identical():
-    """One case per kernel: mds_dissimilarities, the three mds_step instantiations, mds_sum_parts past 256 partials."""
+    """One case per kernel: the dissimilarities (pair_tile), the three mds_step instantiations, mds_sum_parts past 256 partials."""
     from frisk_amd.projection import MDS
     c = K.DIS_BY_ID["close/n129_f9"]
     with MDS(c.X(), 2) as h1, MDS(c.X(), 2) as h2:

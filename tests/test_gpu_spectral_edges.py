@@ -93,7 +93,7 @@ def test_row_counts_at_edges(n):
       63, 64 | 65      the 64-tile of the affinity and the 64 lanes of a product: lanes without a column | a second tile
       127, 128 | 129   MQ_C, the 128 columns of an LDS stage: no zero-filled tail at 128 | a second stage of one column
       191, 192 | 193   three tiles; a second stage exactly half full at 192 (its second half-stage all zeros)
-      255, 256 | 257   the 256-column blocks of spec_colsum_part / spec_degrees / spec_normalise | a second block of one column
+      255, 256 | 257   the 256-column blocks of colsum_part / spec_degrees / spec_normalise | a second block of one column
       511, 512 | 513   two column blocks, four stages, 16 ranges | 17 ranges
       1025             33 ranges (more than any golden's 21), 17 x 17 tiles, 9 stages, 5 column blocks"""
     common("rows-n%d" % n)

@@ -21,7 +21,7 @@ def test_shapes_cover_every_form():
     for edge in (255, 256, 257):
         assert any(n == edge for n, _, _ in SHAPES) and any(f == edge for _, f, _ in SHAPES)
     assert max((n + 255) // 256 for n, _, _ in SHAPES if n < 2000) == 5
-    splits = lambda n: -(-n // -(-n // min(256, -(-n // 32))))      # noqa: E731  State::xtq_splits
+    splits = lambda n: -(-n // -(-n // min(256, -(-n // 32))))      # noqa: E731  State::xtq_splits().count
     assert splits(8161) == 256 and splits(8160) == 255 and splits(8193) == 249 and (8161, 5, 3) in SHAPES
     assert len({EC.case_id(s, st, u) for s in SHAPES for st, u in EC.cases(s)}) == 8 * (len(SHAPES) - 1) + 1
 
