@@ -118,6 +118,16 @@ SYMBOLS = [
     ("frisk_spectral_mq", C.c_int, [_P, _P, C.c_int32, _P]),
     ("frisk_spectral_last_ms", C.c_double, [_P, C.c_int]),
     ("frisk_spectral_destroy", None, [_P]),
+    ("frisk_skltsne_create", C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("frisk_skltsne_affinities", C.c_int, [_P, _P, _P]),
+    ("frisk_skltsne_p_dense", C.c_int, [_P, _P]),
+    ("frisk_skltsne_neighbours", C.c_int, [_P, _P, _P]),
+    ("frisk_skltsne_set_p", C.c_int, [_P, _P, _P, _P, C.c_int64]),
+    ("frisk_skltsne_get", C.c_int, [_P, _P, _P, _P]),
+    ("frisk_skltsne_set", C.c_int, [_P, _P, _P, _P]),
+    ("frisk_skltsne_run", C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("frisk_skltsne_last_ms", C.c_double, [_P, C.c_int]),
+    ("frisk_skltsne_destroy", None, [_P]),
     ("frisk_host_alloc", C.c_void_p, [_P, C.c_int64]),
     ("frisk_host_free", None, [_P, _P]),
     ("frisk_last_kernel_ms", C.c_double, [_P, C.c_int]),

@@ -24,8 +24,14 @@ featuresIn_hmm_State1_<basename> / featuresIn_hmm_State2_<basename> - `bedtools 
 --cluster SPECTRAL (sklearn's SpectralClustering: rbf affinities, normalised Laplacian, k-means on the top --kClusters
 eigenvectors, seeded the same way) runs on the GPU after PCA, PY-TSNE, MDS or IncrementalPCA and, with --dumpPCAdata, writes its
 labels as the pickle anomSPECTRAL; it is still reported as unavailable and writes no cluster GFF3 (CLUSTERINGS_UNWRITTEN).
-Out of scope here: the other projection (SKL-TSNE) and --graphics (seaborn/matplotlib).
-Those options are accepted, as in the reference, and reported as unavailable if used.
+--runProjection SKL-TSNE (sklearn 1.7's TSNE with the reference's parameters, --tsneGradient barnes_hut | exact and --tsneInitPCA
+random | pca, seeded the same way) runs on the GPU and logs its iterations, KL divergence and timings; with --dumpPCAdata it writes
+the embedding as the pickle anomSKLTSNE.  barnes_hut keeps sklearn's nearest-neighbour affinities but sums the repulsive term over
+all pairs: sklearn's angle -> 0 limit, not its angle = 0.5 tree approximation; pca starts from the exact PCA, not sklearn's
+randomized one.  --cluster after SKL-TSNE is still reported as unavailable and writes no cluster GFF3
+(PROJECTIONS_DUMPED).
+Out of scope here: --graphics (seaborn/matplotlib).
+That option is accepted, as in the reference, and reported as unavailable if used.
 
 Run under `python -m torch.distributed.run --nproc-per-node N -m frisk_amd ...` to shard one job over N GPUs
 (frisk_amd.distributed): rank 0 writes the outputs.
@@ -83,8 +89,7 @@ def build_parser():
     p.add_argument("--peakCRI", type=float, default=1.0)
     p.add_argument("--minPI", type=float, default=1.0)
     p.add_argument("--maxSI", type=float, default=1.0)
-    # projection / clustering (PCA, PY-TSNE, MDS, IncrementalPCA, NMF, DBSCAN and KMEANS built; the other methods accepted, not available
-    # in this build)
+    # projection / clustering (every projection, DBSCAN and KMEANS built; SPECTRAL runs but writes no GFF3)
     p.add_argument("--runProjection", default=None, choices=[None, "PCA", "PY-TSNE", "SKL-TSNE", "IncrementalPCA", "NMF", "MDS"])
     p.add_argument("--projectionDims", type=int, default=2)
     p.add_argument("--dimReduce", default="windows", choices=["features", "windows"])
@@ -110,6 +115,7 @@ def build_parser():
 
 PROJECTIONS = ("PCA", "PY-TSNE", "MDS", "IncrementalPCA")     # --runProjection methods built here (frisk_amd.projection)
 PROJECTIONS_UNCLUSTERED = ("NMF",)      # built here too, but --cluster on them is still reported as unavailable (see unavailable)
+PROJECTIONS_DUMPED = ("SKL-TSNE",)      # built here too and treated like PROJECTIONS_UNCLUSTERED: logged, dumped with --dumpPCAdata, unclustered
 CLUSTERINGS = ("DBSCAN", "KMEANS")      # --cluster methods built here
 CLUSTERINGS_UNWRITTEN = ("SPECTRAL",)   # built here too, but still reported as unavailable and without a cluster GFF3 (see unavailable)
 
@@ -120,7 +126,8 @@ def unavailable(args):
     projection runs (PROJECTIONS_UNCLUSTERED), but clustering it is still reported as unavailable and writes no cluster GFF3:
     tests/test_projection_cluster_cpu.py pins ("NMF", "DBSCAN") to this warning.  Moving "NMF" into PROJECTIONS lifts that.
     --cluster SPECTRAL runs too after one of PROJECTIONS (CLUSTERINGS_UNWRITTEN: its labels are logged and dumped, not written as
-    a GFF3), and the same tests pin it to this warning; moving "SPECTRAL" into CLUSTERINGS lifts the fence."""
+    a GFF3), and the same tests pin it to this warning; moving "SPECTRAL" into CLUSTERINGS lifts the fence.  The SKL-TSNE projection
+    runs as well (PROJECTIONS_DUMPED) and, like NMF, leaves --cluster reported here."""
     clustering = args.runProjection in PROJECTIONS and args.cluster in CLUSTERINGS
     out = []
     for opt, why in (("cluster", "sklearn clustering is out of scope"), ("graphics", "plotting is out of scope")):
@@ -282,8 +289,9 @@ def _seed(args):
 
 
 def _project(args, anomCounts, device, clock):
-    """--runProjection PCA (L1612-1613), PY-TSNE (L1622-1623), MDS (L1624-1627), IncrementalPCA (L1629-1631) or NMF (L1632-1636) on
-    the anomalies' k-mer proportions, then --cluster DBSCAN / KMEANS on the projection (L1635-1655), except after NMF; --cluster SPECTRAL
+    """--runProjection PCA (L1612-1613), PY-TSNE (L1622-1623), MDS (L1624-1627), IncrementalPCA (L1629-1631), NMF (L1632-1636) or
+    SKL-TSNE (L1606-1621: sklearn's TSNE; its barnes_hut gradient is the all-pairs angle -> 0 limit, not the angle = 0.5 tree) on
+    the anomalies' k-mer proportions, then --cluster DBSCAN / KMEANS on the projection (L1635-1655), except after NMF and SKL-TSNE; --cluster SPECTRAL
     runs there too but returns nothing (_spectral).  Returns the cluster labels (None without a clustering whose GFF3 is written)."""
     from . import projection as P
     if args.runProjection == "PY-TSNE":
@@ -318,6 +326,22 @@ def _project(args, anomCounts, device, clock):
         if args.dumpPCAdata:                                                # the projection itself, beside anomLabels / anomCounts
             with open(os.path.join(args.tempDir, "anomNMF"), "wb") as fh:
                 pickle.dump(res.Y, fh, protocol=2)
+    elif args.runProjection == "SKL-TSNE":
+        # a perplexity, --projectionDims or number of windows that skl_tsne refuses is a warning: the run goes on as it did before
+        # this projection was built
+        try:
+            res = P.skl_tsne(anomCounts, args.projectionDims, args.perplexity, seed=_seed(args), method=args.tsneGradient,
+                             init=args.tsneInitPCA, device=device)
+        except ValueError as err:
+            log.warning("--runProjection SKL-TSNE skipped: %s", err)
+            return None
+        log.info("SKL-TSNE (%s, init %s) of %s x %s k-mer proportions: %s iterations, KL divergence %s; affinities %.1f ms, "
+                 "start %.1f ms, iterations %.1f ms", args.tsneGradient, args.tsneInitPCA, anomCounts.shape[0], anomCounts.shape[1],
+                 res.n_iter + 1, res.kl_divergence, res.timings["affinities_ms"], res.timings["init_ms"],
+                 res.timings["iterations_ms"])
+        if args.dumpPCAdata:                                                # the embedding itself, beside anomLabels / anomCounts
+            with open(os.path.join(args.tempDir, "anomSKLTSNE"), "wb") as fh:
+                pickle.dump(res.Y, fh, protocol=2)
     else:
         res = P.pca(anomCounts, args.projectionDims, device=device)
         log.info("PCA of %s x %s k-mer proportions: explained variance %s; covariance %.1f ms, eigh %.1f ms, transform %.1f ms",
@@ -325,7 +349,7 @@ def _project(args, anomCounts, device, clock):
                  res.timings["eigh_ms"], res.timings["transform_ms"])
     clock.lap(args.runProjection)
     y_pred = None
-    if args.runProjection in PROJECTIONS_UNCLUSTERED:
+    if args.runProjection in PROJECTIONS_UNCLUSTERED + PROJECTIONS_DUMPED:
         return None
     if args.cluster == "DBSCAN":
         y_pred = P.dbscan(res.Y, args.epsDBSCAN, device=device)
@@ -423,7 +447,7 @@ def _main(argv=None):
     clustering = projection and args.cluster in CLUSTERINGS
     # NMF runs, but every file written under --runProjection NMF before it was built stays as it was: the merged anomalies in
     # --gffOutfile and no cluster GFF3.  Both follow PROJECTIONS, so moving "NMF" there switches them together.
-    projected_only = args.runProjection in PROJECTIONS_UNCLUSTERED
+    projected_only = args.runProjection in PROJECTIONS_UNCLUSTERED + PROJECTIONS_DUMPED
     for opt, why in unavailable(args):
         log.warning("--%s is not available in this build: %s", opt, why)
     update = bool(args.updateHMM)

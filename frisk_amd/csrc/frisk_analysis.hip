@@ -19,6 +19,7 @@
 #include "ipca_kernels.h"
 #include "nmf_kernels.h"
 #include "spectral_kernels.h"
+#include "skltsne_kernels.h"
 #include "hmm_kernels.h"
 
 namespace {
@@ -472,5 +473,113 @@ int frisk_spectral_mq(frisk_spectral* h, const double* Q, int32_t p, double* Z_o
 double frisk_spectral_last_ms(const frisk_spectral* h, int which) { return last_ms(h, which); }
 
 void frisk_spectral_destroy(frisk_spectral* h) { destroy_handle(h); }
+
+// ---- sklearn's t-SNE (skltsne_kernels.h): a handle whose affinities and float32 state stay on its device between calls
+struct frisk_skltsne {
+    frisk_skltsne_impl::State s;
+};
+
+namespace {
+bool all_finite32(const float* x, int64_t count) {
+    for (int64_t e = 0; e < count; ++e) if (!std::isfinite(x[e])) return false;
+    return true;
+}
+}  // namespace
+
+int frisk_skltsne_create(int device, const double* X, int64_t n, int64_t f, double perplexity, int32_t dims, int32_t method,
+                         frisk_skltsne** out) {
+    namespace I = frisk_skltsne_impl;
+    if (!out) return FRISK_E_ARG;
+    *out = nullptr;
+    if (!X || n < 2 || n > I::MAX_N || f < 1 || (method != I::METHOD_EXACT && method != I::METHOD_BARNES_HUT) || dims < 1 ||
+        dims > (method == I::METHOD_EXACT ? I::MAX_D : I::MAX_D_BH) || !(perplexity > 0.0) || !(perplexity < double(n)) ||
+        !all_finite(X, n * f))
+        return FRISK_E_ARG;
+    return create_handle(device, out, [&](I::State& s) {
+        s.n = n; s.f = f; s.d = dims; s.method = method; s.perplexity = perplexity;
+        return s.create(X);
+    });
+}
+
+int frisk_skltsne_affinities(frisk_skltsne* h, double* beta_out, int32_t* steps_out) {
+    if (!h) return FRISK_E_ARG;
+    frisk_common::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    if (h->s.affinities()) return FRISK_E_HIP;
+    const size_t n = size_t(h->s.n);
+    if (copy_fails(beta_out, h->s.beta, n * sizeof(double), hipMemcpyDeviceToHost) ||
+        copy_fails(steps_out, h->s.steps, n * sizeof(int32_t), hipMemcpyDeviceToHost))
+        return FRISK_E_HIP;
+    return FRISK_OK;
+}
+
+int frisk_skltsne_p_dense(frisk_skltsne* h, double* P_out) {
+    if (!h || !P_out) return FRISK_E_ARG;
+    if (h->s.method != frisk_skltsne_impl::METHOD_EXACT || !h->s.have_aff) return FRISK_E_STATE;
+    const size_t bytes = size_t(h->s.n) * size_t(h->s.n) * sizeof(double);
+    return on_device(h->s.device, [&] { return hipMemcpy(P_out, h->s.P, bytes, hipMemcpyDeviceToHost) != hipSuccess; });
+}
+
+int frisk_skltsne_neighbours(frisk_skltsne* h, int32_t* indices_out, double* cond_out) {
+    if (!h) return FRISK_E_ARG;
+    if (h->s.method != frisk_skltsne_impl::METHOD_BARNES_HUT || !h->s.have_aff) return FRISK_E_STATE;
+    const size_t nk = size_t(h->s.n) * size_t(h->s.k);
+    return on_device(h->s.device, [&] {
+        return copy_fails(indices_out, h->s.idx, nk * sizeof(int32_t), hipMemcpyDeviceToHost) ||
+               copy_fails(cond_out, h->s.cond, nk * sizeof(double), hipMemcpyDeviceToHost);
+    });
+}
+
+int frisk_skltsne_set_p(frisk_skltsne* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t nnz) {
+    if (!h || !indptr || nnz < 0 || (nnz && (!indices || !values))) return FRISK_E_ARG;
+    if (h->s.method != frisk_skltsne_impl::METHOD_BARNES_HUT) return FRISK_E_STATE;
+    const int64_t n = h->s.n;
+    if (indptr[0] != 0 || indptr[n] != nnz) return FRISK_E_ARG;
+    for (int64_t i = 0; i < n; ++i) if (indptr[i + 1] < indptr[i]) return FRISK_E_ARG;
+    for (int64_t e = 0; e < nnz; ++e) if (indices[e] < 0 || indices[e] >= n) return FRISK_E_ARG;
+    if (!all_finite32(values, nnz)) return FRISK_E_ARG;
+    return on_device(h->s.device, [&] { return h->s.set_p(indptr, indices, values, nnz); });
+}
+
+int frisk_skltsne_get(frisk_skltsne* h, float* Y, float* update, float* gains) {
+    if (!h) return FRISK_E_ARG;
+    const size_t bytes = size_t(h->s.n) * size_t(h->s.d) * sizeof(float);
+    return on_device(h->s.device, [&] {
+        return copy_fails(Y, h->s.Y, bytes, hipMemcpyDeviceToHost) ||
+               copy_fails(update, h->s.U, bytes, hipMemcpyDeviceToHost) ||
+               copy_fails(gains, h->s.G, bytes, hipMemcpyDeviceToHost);
+    });
+}
+
+int frisk_skltsne_set(frisk_skltsne* h, const float* Y, const float* update, const float* gains) {
+    if (!h) return FRISK_E_ARG;
+    const int64_t nd = h->s.n * h->s.d;
+    if ((Y && !all_finite32(Y, nd)) || (update && !all_finite32(update, nd)) || (gains && !all_finite32(gains, nd))) return FRISK_E_ARG;
+    const size_t bytes = size_t(nd) * sizeof(float);
+    return on_device(h->s.device, [&] {
+        return copy_fails(h->s.Y, Y, bytes, hipMemcpyHostToDevice) ||
+               copy_fails(h->s.U, update, bytes, hipMemcpyHostToDevice) ||
+               copy_fails(h->s.G, gains, bytes, hipMemcpyHostToDevice) || (Y && h->s.refresh());
+    });
+}
+
+int frisk_skltsne_run(frisk_skltsne* h, int32_t iter_begin, int32_t iter_end, double momentum, double exaggeration, double* error,
+                      double* grad_norm) {
+    if (!h || !error || !grad_norm || iter_begin < 0 || iter_end <= iter_begin || iter_end > frisk_skltsne_impl::MAX_ITER ||
+        !std::isfinite(momentum) || !std::isfinite(exaggeration) || !(exaggeration > 0.0))
+        return FRISK_E_ARG;
+    frisk_common::OnDevice on(h->s.device);
+    if (!on.ok) return FRISK_E_HIP;
+    if (h->s.method == frisk_skltsne_impl::METHOD_BARNES_HUT) {
+        if (!h->s.have_p) return FRISK_E_STATE;         // the symmetrised CSR comes from the caller (frisk_skltsne_set_p)
+    } else if (h->s.affinities()) {
+        return FRISK_E_HIP;
+    }
+    return h->s.run(iter_begin, iter_end, momentum, exaggeration, error, grad_norm) ? FRISK_E_HIP : FRISK_OK;
+}
+
+double frisk_skltsne_last_ms(const frisk_skltsne* h, int which) { return last_ms(h, which); }
+
+void frisk_skltsne_destroy(frisk_skltsne* h) { destroy_handle(h); }
 
 }  // extern "C"

@@ -7,7 +7,9 @@ and sklearn's NMF (L1632-1636: the coordinate-descent solver from the nndsvda st
 (frisk_nmf_*, csrc/nmf_kernels.h), and sklearn's SpectralClustering (L1659-1662: rbf affinities, scipy's normalised Laplacian, the
 top eigenvectors, k-means) with the n x n matrix resident on the device (frisk_spectral_*, csrc/spectral_kernels.h): affinities,
 normalisation and every product of the eigen-iteration are kernels, the iteration's QR and Rayleigh-Ritz on matrices at most 26
-columns wide are the host's.  sklearn's t-SNE is not built.
+columns wide are the host's.  sklearn's TSNE, SKL-TSNE (L1606-1621), runs on the GPU too (frisk_skltsne_*, csrc/skltsne_kernels.h):
+both of its methods, the float32 state resident on the device, the stop rule on the host; its barnes_hut method sums the repulsive
+term over all pairs (sklearn's angle -> 0 limit) instead of walking a tree at angle = 0.5.
 
 Reference (frisk/__init__.py): computeKmers(sym=True, pcaMode=True) L280-367 counts every valid word AND its
 reverse complement for orders pcaMin..pcaMax; scrubMirrors L797-811 keeps one key of each reverse-complement pair
@@ -927,3 +929,218 @@ def spectral(Y, k, seed=0, gamma=SPECTRAL_GAMMA, n_init=SPECTRAL_N_INIT, device=
                           {"affinity_ms": aff_ms, "normalise_ms": norm_ms, "products_ms": t["product_ms"],
                            "products_wall_ms": t["product_wall_ms"], "host_ms": t["host_ms"], "embedding_ms": 1e3 * (t1 - t0),
                            "kmeans_ms": 1e3 * (t2 - t1)})
+
+
+# ------------------------------------------------------------------------------------------------ SKL-TSNE
+# TSNE(n_components=dims, perplexity, early_exaggeration=4.0, learning_rate=1000.0, n_iter=1000, n_iter_without_progress=30,
+#      min_grad_norm=1e-07, metric='euclidean', init, random_state=None, method, angle=0.5) (L1606-1621)
+SKLTSNE_MAX_N = 50000                   # the dense n x n affinities of the exact method: 20 GB at the cap
+SKLTSNE_MAX_ITER, SKLTSNE_EXPLORATION = 1000, 250       # max_iter; TSNE._EXPLORATION_MAX_ITER (stage 1, and its n_iter_without_progress)
+SKLTSNE_N_ITER_CHECK, SKLTSNE_N_ITER_WITHOUT_PROGRESS, SKLTSNE_MIN_GRAD_NORM = 50, 30, 1e-7
+SKLTSNE_EXAGGERATION = 4.0
+SKLTSNE_METHODS = ("exact", "barnes_hut")       # the C ABI's method numbers
+SKLTSNE_INITS = ("random", "pca")
+
+
+class SKLTSNE(_Handle):
+    """sklearn's TSNE on the GPU (frisk_skltsne_*): X (n x f, any f), the affinities and the float32 state (Y, update, gains) stay
+    on the device.  method 'exact': dense joint probabilities; 'barnes_hut': the k = min(n - 1, int(3 perplexity + 1)) nearest
+    neighbours of each row, whose conditionals the caller symmetrises (skl_tsne_joint_nn) and hands back with set_p().  Y starts at
+    0; set the start with set().  Use as a context manager (or call close())."""
+
+    _destroy = "frisk_skltsne_destroy"
+
+    def __init__(self, X, dims=2, perplexity=20.0, method="barnes_hut", device=0):
+        X = _f64(X, 2)
+        self.n, self.f = X.shape
+        self.dims, self.method = int(dims), method
+        self.k = min(self.n - 1, int(3.0 * perplexity + 1))
+        self._h = C.c_void_p()
+        _call("frisk_skltsne_create", device, _ptr(X), self.n, self.f, float(perplexity), self.dims, SKLTSNE_METHODS.index(method),
+              C.byref(self._h))
+
+    def affinities(self):
+        """(beta, steps) of every row: the beta its probabilities belong to and the bisection step that met the tolerance (100:
+        none).  Computed once."""
+        beta, steps = np.empty(self.n), np.empty(self.n, dtype=np.int32)
+        _call("frisk_skltsne_affinities", self._h, _ptr(beta), _ptr(steps))
+        return beta, steps
+
+    def p_dense(self):
+        """exact: the n x n joint P = max((C + CT) / max(sum, eps), eps), 0 on the diagonal."""
+        P = np.empty((self.n, self.n))
+        _call("frisk_skltsne_p_dense", self._h, _ptr(P))
+        return P
+
+    def neighbours(self):
+        """barnes_hut: (indices n x k int32 in ascending column order, conditional p_j|i n x k)."""
+        idx, cond = np.empty((self.n, self.k), dtype=np.int32), np.empty((self.n, self.k))
+        _call("frisk_skltsne_neighbours", self._h, _ptr(idx), _ptr(cond))
+        return idx, cond
+
+    def set_p(self, P):
+        """barnes_hut: the joint probabilities as a scipy CSR matrix (n x n); the values go up as float32, as sklearn passes them."""
+        P = P.tocsr()
+        if P.shape != (self.n, self.n):
+            raise ValueError("expected a %d x %d matrix, got %s" % (self.n, self.n, P.shape))
+        indptr = np.ascontiguousarray(P.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(P.indices, dtype=np.int32)
+        values = np.ascontiguousarray(P.data, dtype=np.float32)
+        _call("frisk_skltsne_set_p", self._h, _ptr(indptr), _ptr(indices), _ptr(values), int(values.size))
+
+    def get(self):
+        """(Y, update, gains), each n x dims float32."""
+        out = [np.empty((self.n, self.dims), dtype=np.float32) for _ in range(3)]
+        _call("frisk_skltsne_get", self._h, *[_ptr(a) for a in out])
+        return tuple(out)
+
+    def set(self, Y=None, update=None, gains=None):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (Y, update, gains)]
+        for a in arrs:
+            if a is not None and a.shape != (self.n, self.dims):
+                raise ValueError("expected shape %s, got %s" % ((self.n, self.dims), a.shape))
+        _call("frisk_skltsne_set", self._h, *[None if a is None else _ptr(a) for a in arrs])
+
+    def run(self, begin, end, momentum, exaggeration=1.0):
+        """Iterations begin .. end - 1 with P x exaggeration: (KL divergence, |grad * gains|) of the last of them."""
+        err, norm = C.c_double(), C.c_double()
+        _call("frisk_skltsne_run", self._h, int(begin), int(end), float(momentum), float(exaggeration), C.byref(err), C.byref(norm))
+        return err.value, norm.value
+
+    def last_ms(self):
+        """Device ms: (the affinities, the last run)."""
+        ms = _ffi.lib().frisk_skltsne_last_ms
+        return ms(self._h, 0), ms(self._h, 1)
+
+
+def skl_tsne_joint_nn(indices, cond):
+    """sklearn's _joint_probabilities_nn from the conditionals of the kept neighbours (n x k each, columns ascending): P + PT on the
+    union of the two patterns, divided by max(sum, eps).  A scipy CSR matrix (float64) with sorted column indices; n k entries is
+    small, so this is the host's."""
+    from scipy.sparse import csr_matrix
+    n, k = indices.shape
+    P = csr_matrix((np.asarray(cond, dtype=np.float64).ravel(), np.asarray(indices).ravel(), np.arange(0, n * k + 1, k)), shape=(n, n))
+    P = P + P.T
+    P /= np.maximum(P.sum(), np.finfo(np.double).eps)
+    P = P.tocsr()
+    P.sort_indices()
+    return P
+
+
+def skl_tsne_descent(h, max_iter=SKLTSNE_MAX_ITER, exploration=SKLTSNE_EXPLORATION, n_iter_check=SKLTSNE_N_ITER_CHECK,
+                     n_iter_without_progress=SKLTSNE_N_ITER_WITHOUT_PROGRESS, min_grad_norm=SKLTSNE_MIN_GRAD_NORM,
+                     exaggeration=SKLTSNE_EXAGGERATION):
+    """The control flow of sklearn's TSNE._tsne and _gradient_descent on a handle h whose run(begin, end, momentum, exaggeration)
+    performs iterations and returns (error, grad norm) of the last: stage 1 runs iterations 0 .. exploration - 1 with momentum 0.5
+    and P x exaggeration (its n_iter_without_progress is `exploration`), stage 2 from the iteration after stage 1's last up to
+    max_iter with momentum 0.8 and P as it is.  Every n_iter_check iterations the error and the norm are read: the stage stops when
+    the error did not improve and i - best_iter > n_iter_without_progress, or when the norm is <= min_grad_norm; best_error restarts
+    with each stage.  Returns (kl_divergence, n_iter, checks): the error of the last iteration run, its number (sklearn's n_iter_),
+    and (iteration, error, norm) of every check."""
+    checks = []
+
+    def stage(it, stop_at, momentum, ex, patience):
+        error = best_error = np.finfo(float).max
+        best_iter = i = it
+        nxt = it
+        while nxt < stop_at:
+            last = min(nxt + (n_iter_check - 1 - nxt % n_iter_check), stop_at - 1)     # the next check, or the last iteration
+            error, norm = h.run(nxt, last + 1, momentum, ex)
+            i = last
+            if (i + 1) % n_iter_check == 0:
+                checks.append((i, error, norm))
+                if error < best_error:
+                    best_error, best_iter = error, i
+                elif i - best_iter > patience:
+                    break
+                if norm <= min_grad_norm:
+                    break
+            nxt = last + 1
+        return error, i
+
+    kl, it = stage(0, exploration, 0.5, exaggeration, exploration)
+    if it < exploration or max_iter - exploration > 0:
+        kl, it = stage(it + 1, max_iter, 0.8, 1.0, n_iter_without_progress)
+    return kl, it, checks
+
+
+class SKLTSNEResult:
+    """Y (n x dims float32), kl_divergence and n_iter (sklearn's kl_divergence_ and n_iter_), errors and grad_norms (of every check,
+    with check_iters their iterations), beta and steps of the perplexity search (n each), Y0 (the start); timings in ms."""
+
+    def __init__(self, Y, kl_divergence, n_iter, checks, beta, steps, Y0, timings):
+        self.Y, self.kl_divergence, self.n_iter = Y, kl_divergence, n_iter
+        self.check_iters = np.array([c[0] for c in checks], dtype=np.int64)
+        self.errors = np.array([c[1] for c in checks])
+        self.grad_norms = np.array([c[2] for c in checks])
+        self.beta, self.steps, self.Y0, self.timings = beta, steps, Y0, timings
+
+
+def skl_tsne_check(n, f, dims, perplexity, method, init):
+    """The argument errors of skl_tsne, sklearn's where it has one, raised before any device call."""
+    if method not in SKLTSNE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (SKLTSNE_METHODS, method))
+    if init not in SKLTSNE_INITS:
+        raise ValueError("init must be one of %s, got %r" % (SKLTSNE_INITS, init))
+    if not 2 <= n <= SKLTSNE_MAX_N:
+        raise ValueError("SKL-TSNE needs between 2 and %d samples, got %d" % (SKLTSNE_MAX_N, n))
+    if not perplexity > 0:
+        raise ValueError("perplexity must be positive, got %r" % (perplexity,))
+    if perplexity >= n:
+        raise ValueError("perplexity must be less than n_samples")
+    if dims < 1:
+        raise ValueError("n_components=%d must be at least 1" % dims)
+    if method == "barnes_hut" and dims > 3:
+        raise ValueError("'n_components' should be inferior to 4 for the barnes_hut algorithm as it relies on quad-tree or oct-tree.")
+    if dims > 64:
+        raise ValueError("n_components=%d must be at most 64" % dims)
+    if init == "pca" and dims > min(n, f):
+        raise ValueError("n_components=%d must be between 1 and min(n_samples, n_features)=%d with init='pca'" % (dims, min(n, f)))
+
+
+def skl_tsne_start(X, dims, rs, init="random", device=0):
+    """The start of the embedding, float32: 'random' is sklearn's 1e-4 * rs.standard_normal((n, dims)).astype(float32); 'pca' is the
+    exact PCA of this module (pca(): covariance and transform on the GPU, the same svd_flip sign rule) where sklearn runs
+    PCA(svd_solver='randomized') from the same random state, then sklearn's cast to float32, division by std(column 0) and scaling
+    by 1e-4.  The two PCAs agree up to the randomized solver's approximation error."""
+    n = X.shape[0]
+    if init == "pca":
+        Y0 = pca(X, dims, device).Y.astype(np.float32, copy=False)
+        return np.ascontiguousarray(Y0 / np.std(Y0[:, 0]) * 1e-4, dtype=np.float32)
+    return np.ascontiguousarray(1e-4 * rs.standard_normal(size=(n, dims)).astype(np.float32), dtype=np.float32)
+
+
+def skl_tsne(X, dims=2, perplexity=20.0, seed=0, method="barnes_hut", init="random", device=0):
+    """sklearn 1.7's TSNE(n_components=dims, perplexity, early_exaggeration=4.0, learning_rate=1000.0, max_iter=1000,
+    n_iter_without_progress=30, min_grad_norm=1e-07, metric='euclidean', init, random_state=seed, method, angle=0.5)
+    .fit_transform(X) (L1606-1621; the reference's random_state=None becomes RandomState(seed)) on the GPU.  Affinities, every
+    gradient and every update are kernels on a float32 state that stays on the device; the stop rule (skl_tsne_descent) reads two
+    scalars every 50 iterations, so the run usually ends long before iteration 1000, as sklearn's does.
+    Two departures from sklearn, both deliberate: (1) method='barnes_hut' keeps sklearn's sparse affinities (k nearest neighbours)
+    but sums the repulsive term over ALL pairs instead of walking a quad-/oct-tree at angle = 0.5; that is what sklearn's own code
+    computes as angle -> 0, so the result is sklearn's angle = 0 limit, not its angle = 0.5 approximation (which deviates from it by
+    0.2 - 0.6 % of the largest gradient entry).  (2) init='pca' starts from this module's exact pca() instead of sklearn's
+    randomized PCA (skl_tsne_start).  The trajectory is chaotic: the result matches sklearn's step by step and in its KL divergence
+    and stopping iteration, not in its final coordinates.  Raises ValueError, before any device call, for sklearn's argument errors
+    (perplexity >= n_samples; dims >= 4 with barnes_hut) and for n outside 2 .. 50 000."""
+    X = _f64(X, 2)
+    n, f = X.shape
+    dims = int(dims)
+    skl_tsne_check(n, f, dims, perplexity, method, init)
+    rs = np.random.RandomState(seed)
+    t0 = time.perf_counter()
+    with SKLTSNE(X, dims, perplexity, method, device) as h:
+        beta, steps = h.affinities()
+        if method == "barnes_hut":
+            h.set_p(skl_tsne_joint_nn(*h.neighbours()))
+        t1 = time.perf_counter()
+        Y0 = skl_tsne_start(X, dims, rs, init, device)
+        t2 = time.perf_counter()
+        h.set(Y=Y0)
+        kl, n_iter, checks = skl_tsne_descent(h)
+        Y = h.get()[0]
+        t3 = time.perf_counter()
+        aff_ms = h.last_ms()[0]
+    return SKLTSNEResult(Y, kl, n_iter, checks, beta, steps, Y0,
+                         {"affinities_ms": 1e3 * (t1 - t0), "affinities_device_ms": aff_ms, "init_ms": 1e3 * (t2 - t1),
+                          "iterations_ms": 1e3 * (t3 - t2)})

@@ -451,6 +451,44 @@ int  frisk_spectral_mq(frisk_spectral* h, const double* Q, int32_t p, double* Z_
 double frisk_spectral_last_ms(const frisk_spectral* h, int which);
 void frisk_spectral_destroy(frisk_spectral* h);
 
+/* sklearn 1.7's TSNE of the reference's --runProjection SKL-TSNE (TSNE(early_exaggeration=4, learning_rate=1000, max_iter=1000,
+ * n_iter_without_progress=30, min_grad_norm=1e-7, angle=0.5), method 0 = 'exact', 1 = 'barnes_hut').  The handle keeps X, the
+ * affinities and the float32 state (Y, update, gains) on `device`; the caller drives the descent 50 iterations at a time and applies
+ * sklearn's stop rule (frisk_amd.projection.skl_tsne_descent).  Squared distances by direct differences in FP64, rounded to float32;
+ * _binary_search_perplexity as written (beta from 1, at most 100 steps, tolerance (float)1e-5).  The gradient, the normaliser and the
+ * error are accumulated in FP64, the gradient rounded to float32 once, the update with gains done in float32 in sklearn's order.
+ * barnes_hut keeps the k = min(n - 1, (int)(3 perplexity + 1)) nearest neighbours of each row and sums the repulsive term over ALL
+ * pairs: sklearn's own result in the limit angle -> 0, not its angle = 0.5 tree approximation.
+ * frisk_skltsne_create: X[n][f], any f >= 1.  FRISK_E_ARG, with nothing allocated, unless 2 <= n <= 50 000, 0 < perplexity < n,
+ *   1 <= dims <= 64 (exact) or 3 (barnes_hut) and X is finite.  Y starts at 0, update at 0, gains at 1.  Device memory: exact
+ *   8 n^2 bytes, barnes_hut 12 n k bytes, plus 8 n f and O(n dims).
+ * frisk_skltsne_affinities: computes the affinities once (later calls only copy).  beta_out[n]: the beta each row's probabilities
+ *   were computed with; steps_out[n]: the bisection step that met the tolerance (0 .. 99), 100 when none did.  Both nullable.
+ * frisk_skltsne_p_dense (exact, after affinities): P_out[n][n] = max((C + CT) / max(sum, eps), eps), 0 on the diagonal.
+ * frisk_skltsne_neighbours (barnes_hut, after affinities): indices_out[n][k], each row's neighbours in ascending column order (the
+ *   k smallest float32 distances, ties to the lower column), and cond_out[n][k], their p_j|i.  Both nullable.
+ * frisk_skltsne_set_p (barnes_hut): the symmetrised, normalised joint probabilities as CSR (indptr[n + 1], indices[nnz] in [0, n),
+ *   float32 values[nnz]), which the caller builds from the conditionals as sklearn's _joint_probabilities_nn does.
+ * frisk_skltsne_get / frisk_skltsne_set: the state Y, update, gains (each float[n][dims], each nullable); set rejects non-finite values.
+ * frisk_skltsne_run: iterations iter_begin .. iter_end - 1 (0 <= iter_begin < iter_end <= 1000) with P multiplied by `exaggeration`,
+ *   no host synchronisation inside.  *error = the KL divergence and *grad_norm = |grad * gains|_2 of the last of them.
+ *   FRISK_E_STATE for barnes_hut before frisk_skltsne_set_p; exact computes its affinities first if need be.
+ * frisk_skltsne_last_ms: device time in ms of the affinities (which = 0) and of the last run (1); else -1.
+ * Every entry point returns FRISK_E_ARG for a null handle.  Every result is bit-identical from run to run. */
+typedef struct frisk_skltsne frisk_skltsne;
+int  frisk_skltsne_create(int device, const double* X, int64_t n, int64_t f, double perplexity, int32_t dims, int32_t method,
+                          frisk_skltsne** out);
+int  frisk_skltsne_affinities(frisk_skltsne* h, double* beta_out, int32_t* steps_out);
+int  frisk_skltsne_p_dense(frisk_skltsne* h, double* P_out);
+int  frisk_skltsne_neighbours(frisk_skltsne* h, int32_t* indices_out, double* cond_out);
+int  frisk_skltsne_set_p(frisk_skltsne* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t nnz);
+int  frisk_skltsne_get(frisk_skltsne* h, float* Y, float* update, float* gains);
+int  frisk_skltsne_set(frisk_skltsne* h, const float* Y, const float* update, const float* gains);
+int  frisk_skltsne_run(frisk_skltsne* h, int32_t iter_begin, int32_t iter_end, double momentum, double exaggeration, double* error,
+                       double* grad_norm);
+double frisk_skltsne_last_ms(const frisk_skltsne* h, int which);
+void frisk_skltsne_destroy(frisk_skltsne* h);
+
 /* Page-locked host memory for result buffers: D2H copies into it are asynchronous and run at PCIe rate
  * (pageable buffers work too, at a fraction of it).  Free with frisk_host_free before frisk_destroy. */
 void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);
