@@ -3,8 +3,8 @@
 // The resident layout of frisk_device.h needs three bit arrays per padded position: codes (2 bits), inv, low (1 bit each).
 // Over PCIe only the codes travel densely; the two masks travel as lists of half-open runs [begin, end) of padded positions
 // (N runs and soft-masked runs are few and long in assemblies) and are expanded to the bitmaps on the device
-// (expand_runs_kernel, profile_kernels.h).  PAD positions are known from the scaffold lengths and never travel.
-// Classification of a byte = classify_byte of profile_kernels.h (the device packer): ACGT / acgt -> code, everything else
+// (expand_runs_kernel, seq_kernels.h).  PAD positions are known from the scaffold lengths and never travel.
+// Classification of a byte = classify_byte of seq_kernels.h (the device packer): ACGT / acgt -> code, everything else
 // invalid; lowercase acgt -> soft-masked (case-sensitive tallies of the reference: countN L106-118, calcGC L120-137).
 #pragma once
 #include <algorithm>

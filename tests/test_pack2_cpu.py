@@ -1,5 +1,5 @@
 """Host side of the 0.25 B/base upload form (frisk_pack_2bit, csrc/seq_pack2.h) against a numpy restatement of the device
-packer's classification (csrc/profile_kernels.h: classify_byte) - no GPU needed: the entry point is host-only."""
+packer's classification (csrc/seq_kernels.h: classify_byte) - no GPU needed: the entry point is host-only."""
 import numpy as np
 import pytest
 

@@ -1,8 +1,9 @@
 // (CPU) the library's host-only headers under AddressSanitizer + UBSan (GPU sanitizers are not available on the pool): random batches
 // through the 2-bit packer (against a letter-by-letter restatement), bitmap -> runs, the HMM fit / Viterbi on random series of awkward
-// lengths, and the scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes, named shapes against values worked out by
-// hand.  build + run:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifrisk_amd/csrc
-//                      tools/exp/san_host.cpp -o build/san/san_host -lpthread -lz && build/san/san_host
+// lengths, the scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes, named shapes against values worked out by
+// hand, and the window-tile planner (scan_tiles.h): every rank's tiles of random shapes together.
+// build + run:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifrisk_amd/csrc
+//               tools/exp/san_host.cpp -o build/san/san_host -lpthread -lz && build/san/san_host
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -12,6 +13,7 @@
 #include "fasta_index.h"
 #include "fasta_pack2.h"
 #include "scan_schedule.h"
+#include "scan_tiles.h"
 #include <fstream>
 #include <unistd.h>
 
@@ -149,8 +151,83 @@ static long long check_scan_schedule() {          // -> schedules planned
     return (long long)plans;
 }
 
+// Window-tile sharding (scan_tiles.h): over seeded random shapes, every rank's plan_tiles() together.  The ranks' candidate ranges
+// partition the job's numbering; every window is scored by exactly one rank and every base counted by exactly one; what a tile
+// keeps resident, [base0, tile_end), holds its windows and its owned positions with the kmax - 1 bases behind them.
+static long long check_scan_tiles() {             // -> shapes planned
+    std::mt19937_64 rng(20240607);
+    const int shapes = 20000;
+    long long jumpbacks = 0, small_tiles = 0, windowless = 0, split_scaffolds = 0;
+    for (int shape = 0; shape < shapes; ++shape) {
+        const int32_t w = 1 + int32_t(rng() % 60), inc = 1 + int32_t(rng() % 40);
+        const bool all = (rng() & 1) != 0;
+        const int kmax = 1 + int(rng() % 12), world = 1 + int(rng() % 9);
+        std::vector<int64_t> lens(size_t(rng() % 7));
+        for (int64_t& n : lens) {
+            switch (rng() % 4) {
+                case 0: n = 0; break;
+                case 1: n = int64_t(rng() % uint64_t(2 * w + 2)); break;
+                case 2: n = std::max<int64_t>(0, int64_t(1.75 * w) - inc + int64_t(rng() % 5) - 2); break;      // the small-scaffold limit
+                default: n = int64_t(rng() % 401); break;
+            }
+        }
+        std::vector<int64_t> ncand(lens.size());
+        std::vector<std::vector<int>> scored(lens.size()), counted(lens.size());       // per window, per base: by how many ranks
+        std::vector<int> in_tiles(lens.size(), 0);
+        int64_t total = 0;
+        for (size_t s = 0; s < lens.size(); ++s) {
+            int32_t kind = 0;
+            plan_scaffold(lens[s], w, inc, all, ncand[s], kind);
+            total += ncand[s];
+            scored[s].assign(size_t(ncand[s]), 0);
+            counted[s].assign(size_t(lens[s]), 0);
+        }
+        int64_t prev_c1 = 0;
+        for (int rank = 0; rank < world; ++rank) {
+            int64_t c0 = -1, c1 = -1;
+            const std::vector<Tile> tiles = plan_tiles(lens, w, inc, all, kmax, rank, world, c0, c1);
+            CHECK(c0 == prev_c1 && c0 <= c1 && c1 <= total);
+            prev_c1 = c1;
+            int64_t mine = 0;
+            int32_t prev_scaf = -1;
+            for (const Tile& t : tiles) {
+                CHECK(t.scaf > prev_scaf && size_t(t.scaf) < lens.size());
+                prev_scaf = t.scaf;
+                if (t.scaf < 0 || size_t(t.scaf) >= lens.size()) continue;
+                const size_t s = size_t(t.scaf);
+                const int64_t size = lens[s], end = tile_end(t, w, inc, kmax);
+                ++in_tiles[s];
+                mine += t.ncand;
+                CHECK(t.size == size && 0 <= t.base0 && t.base0 <= end && end <= size);
+                CHECK(0 <= t.j0 && 0 <= t.ncand && t.j0 + t.ncand <= ncand[s]);
+                CHECK(0 <= t.own0 && t.own0 <= t.own1 && t.own1 <= size);
+                if (!(0 <= t.j0 && 0 <= t.ncand && t.j0 + t.ncand <= ncand[s] && 0 <= t.own0 && t.own0 <= t.own1 && t.own1 <= size)) continue;
+                for (int64_t p = t.own0; p < t.own1; ++p) ++counted[s][size_t(p)];
+                if (t.own1 > t.own0) CHECK(t.base0 <= t.own0 && std::min<int64_t>(size, t.own1 + kmax - 1) <= end);
+                for (int64_t j = t.j0; j < t.j0 + t.ncand; ++j) {
+                    ++scored[s][size_t(j)];
+                    int64_t a = j * inc, b = a + w;
+                    if (b > size) { a = std::max<int64_t>(0, size - w); b = size; ++jumpbacks; }       // the jumpback window
+                    CHECK(t.base0 <= a && b <= end);
+                }
+                small_tiles += t.kind == 1; windowless += t.ncand == 0; split_scaffolds += t.ncand > 0 && t.ncand < ncand[s];
+            }
+            CHECK(mine == c1 - c0);
+        }
+        CHECK(prev_c1 == total);
+        for (size_t s = 0; s < lens.size(); ++s) {
+            for (int n : scored[s]) CHECK(n == 1);
+            for (int n : counted[s]) CHECK(n == 1);
+            if (lens[s] == 0) CHECK(in_tiles[s] <= 1);
+        }
+    }
+    CHECK(jumpbacks > 1000 && small_tiles > 1000 && windowless > 1000 && split_scaffolds > 1000);      // (the sweep reaches them)
+    return shapes;
+}
+
 int main() {
     const long long plans = check_scan_schedule();
+    const long long tile_shapes = check_scan_tiles();
     std::mt19937_64 rng(12345);
     const char alphabet[] = "ACGTacgtNnRYKM-*xACGTACGTACGT";
     for (int round = 0; round < 300; ++round) {
@@ -292,6 +369,6 @@ int main() {
         }
         ::unlink(path.c_str());
     }
-    std::printf("%s (%d failed checks; %lld scan schedules; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
+    std::printf("%s (%d failed checks; %lld scan schedules; %lld tile plans; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, tile_shapes, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
     return fails ? 1 : 0;
 }
