@@ -30,6 +30,13 @@ the embedding as the pickle anomSKLTSNE.  barnes_hut keeps sklearn's nearest-nei
 all pairs: sklearn's angle -> 0 limit, not its angle = 0.5 tree approximation; pca starts from the exact PCA, not sklearn's
 randomized one.  --cluster after SKL-TSNE is still reported as unavailable and writes no cluster GFF3
 (PROJECTIONS_DUMPED).
+--spikeNormal (with --runProjection; the reference advertises it as a future function and never wired it) puts ordinary windows
+into the projection beside the anomalies: as many as there are anomalous rows, the unpicked windows whose log10(KLD) lies nearest
+the median of all scored windows (frisk_amd.postprocess.spike_rows; no random numbers).  The query is loaded by the native reader
+and the k-mer vectors of anomalies and spiked windows come from the device kernel on the packed batch (csrc/kvec_kernels.h,
+frisk_window_vectors).  The anomaly rows come first, unchanged; the spiked rows follow, labelled name:start:stop.  Projection and
+clustering run on all rows; --dumpPCAdata writes all of them and the bool pickle anomSpike; the cluster GFF3 keeps the anomaly
+rows (with the classes of the joint clustering) and the spiked rows go to spikeNormal_<cluster GFF3>.  No other output changes.
 Out of scope here: --graphics (seaborn/matplotlib).
 That option is accepted, as in the reference, and reported as unavailable if used.
 
@@ -384,6 +391,47 @@ def _spectral(args, Y, device, clock):
     clock.lap("SPECTRAL")
 
 
+def _spiked_counts(args, table, logKLD, threshold, feats, querySeq, device, clock):
+    """--runProjection with --spikeNormal (the reference advertises the option as a future function and never wired it): the
+    projection's input with ordinary windows beside the anomalies.  The query is loaded by the native reader and stays packed on
+    the device; the vectors of the anomaly set and of the spiked windows (postprocess.spike_rows: as many as there are anomalies,
+    nearest the median log10(KLD)) come from ONE projection.windowVectors call on it.  Returns (labelled, anomLabels, anomCounts,
+    spiked): the anomaly rows first, order and labels as without the option, then the spiked rows labelled name:start:stop as the
+    table reports them; spiked = the bool mask of the latter, None when there is nothing to spike."""
+    from .engine import Engine
+    from .projection import windowVectors
+    with Engine(args.pcaMin, args.pcaMax, device) as e:
+        index = {nm: i for i, nm in enumerate(e.load_fasta(querySeq))}
+        lens = list(e.seq_lens)
+
+        def ranges(records):        # (name, 1-based start, stop) -> what the slice seq[start - 1:stop] covers
+            out = []
+            for nm, a, b in records:
+                lo, hi, _ = slice(int(a) - 1, int(b)).indices(lens[index[nm]])
+                out.append((index[nm], lo, hi))
+            return out
+        anom = [(f[0], f[1], f[2]) for f in feats if f[0] in index]
+        labelled = [":".join([nm, str(a), str(b)]) for nm, a, b in anom]
+        rows = np.zeros(0, dtype=np.int64)
+        if not anom:
+            log.info("--spikeNormal: no anomalous window to set ordinary windows beside.")
+        else:
+            rows = pp.spike_rows(logKLD, pp.pickedKLD(logKLD, threshold, bool(args.findSelf)), len(anom))
+            rows = rows[np.array([table.names[int(table.seq_index[r])] in index for r in rows.tolist()], dtype=bool)]
+            if rows.size == 0:
+                log.info("--spikeNormal: every scored window is anomalous or unscored: no ordinary window to add.")
+        spikes = [(table.names[int(table.seq_index[r])], int(table.start[r]), int(table.stop[r])) for r in rows.tolist()]
+        labels = labelled + [":".join([nm, str(a), str(b)]) for nm, a, b in spikes]
+        where = ranges(anom + spikes)
+        counts = windowVectors(e, [w[0] for w in where], [w[1] for w in where], [w[2] for w in where], args.pcaMin, args.pcaMax,
+                               labels=labels)
+    if spikes:
+        log.info("--spikeNormal: %s ordinary windows nearest the median log10(KLD) beside %s anomalous ones.", len(spikes), len(anom))
+    clock.lap("k-mer vectors (--spikeNormal)")
+    spiked = np.arange(len(labels)) >= len(anom) if spikes else None
+    return labelled, np.array([[lab] for lab in labels]) if labels else np.zeros((0, 1), dtype=object), counts, spiked
+
+
 def _gff_features(args, anomalies, intervals):
     """--gffIn (L1709-1747): the records of the annotation whose type is in --gffFeatures and that lie within --gffRange bases of
     an anomaly (with a threshold option) or of a State1 / State2 interval of the main HMM track (--hmmKLD; `intervals` as hmm2BED
@@ -624,6 +672,9 @@ def _main(argv=None):
                      getattr(_model, "n_iter_", "?"), getattr(_model, "loglik_", "?"))
             clock.lap("HMM segmentation + GFF")
         fine_intervals = None
+        spiked = None               # --spikeNormal: which rows of the projection's input are spiked windows (None: no spikes)
+        if args.spikeNormal and not args.runProjection:
+            log.warning("--spikeNormal has no effect without --runProjection.")
         if fine_table is not None:                                          # --updateHMM: the fine track, device model
             from .hmm import hmm2BED, hmmBED2GFF
             if not np.any(~np.isnan(np.where(fine_table.kld_is_int0 != 0, 0.0, fine_table.kld))):
@@ -639,15 +690,21 @@ def _main(argv=None):
             from .fasta import readFasta
             from .projection import symmetricCounts
             feats, _ = pp.thresholdKLD(table, threshold, args, merge=(args.dimReduce == "features"))
-            names, seqs = readFasta(querySeq)
-            fasta = dict(zip(names, seqs))
-            labelled = [(":".join([f[0], str(f[1]), str(f[2])]), fasta[f[0]][int(f[1]) - 1:int(f[2])]) for f in feats if f[0] in fasta]
-            anomLabels, anomCounts = symmetricCounts(labelled, args.pcaMin, args.pcaMax, device=local_rank)
+            if args.spikeNormal:
+                labelled, anomLabels, anomCounts, spiked = _spiked_counts(args, table, logKLD, threshold, feats, querySeq, local_rank, clock)
+            else:
+                names, seqs = readFasta(querySeq)
+                fasta = dict(zip(names, seqs))
+                labelled = [(":".join([f[0], str(f[1]), str(f[2])]), fasta[f[0]][int(f[1]) - 1:int(f[2])]) for f in feats if f[0] in fasta]
+                anomLabels, anomCounts = symmetricCounts(labelled, args.pcaMin, args.pcaMax, device=local_rank)
             if args.dumpPCAdata:
                 with open(os.path.join(args.tempDir, "anomLabels"), "wb") as fh:
                     pickle.dump(anomLabels, fh, protocol=2)
                 with open(os.path.join(args.tempDir, "anomCounts"), "wb") as fh:
                     pickle.dump(anomCounts, fh, protocol=2)
+                if spiked is not None:
+                    with open(os.path.join(args.tempDir, "anomSpike"), "wb") as fh:
+                        pickle.dump(spiked, fh, protocol=2)
             if projection or projected_only:
                 y_pred = _project(args, anomCounts, local_rank, clock)
             else:
@@ -667,8 +724,13 @@ def _main(argv=None):
                 with open(os.path.join(args.tempDir, "HMMupdated_" + args.gffOutfile), "w") as fh:
                     fh.writelines(pp.anomaly2GFF(refined, args))
             if clustering:                                                  # L1688-1697
+                rows = pp.cluster_rows(anomLabels, y_pred)
+                if spiked is not None:      # --spikeNormal: the anomalies keep their file, with the classes of the joint clustering
+                    with open(os.path.join(args.tempDir, "spikeNormal_" + pp.clusterGffName(args)), "w") as fh:
+                        fh.writelines(pp.anomClust2gff([r for r, s in zip(rows, spiked) if s]))
+                    rows = [r for r, s in zip(rows, spiked) if not s]
                 with open(os.path.join(args.tempDir, pp.clusterGffName(args)), "w") as fh:
-                    fh.writelines(pp.anomClust2gff(pp.cluster_rows(anomLabels, y_pred)))
+                    fh.writelines(pp.anomClust2gff(rows))
         if rip:
             feats = pp.thresholdRIP(table, args)
             if feats:

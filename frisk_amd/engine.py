@@ -342,6 +342,23 @@ class Engine:
         self._check(self._lib.frisk_seq_read(self._ctx, index, int(offset), int(n), _ptr(out)))
         return out[:n].tobytes()
 
+    def window_vectors(self, seq_index, start, stop, kmin, kmax, batch_rows=0):
+        """(X, nn, status) of frisk_window_vectors: row r of X = the symmetric k-mer proportions of orders kmin..kmax (independent of
+        the engine's own) of bases [start[r], stop[r]) - 0-based, half-open - of resident scaffold seq_index[r]; nn[r] = its
+        positions that are not uppercase A/T/G/C; status[r] & _ffi.KVEC_EMPTY_ORDER: the range holds no valid word of some order.
+        batch_rows > 0 forces that many rows per launch (0: the library's default)."""
+        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
+        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
+        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        n = int(seq_index.size)
+        if start.size != n or stop.size != n:
+            raise ValueError("seq_index, start and stop must have one entry per range")
+        f = sum((4 ** x + (2 ** x if x % 2 == 0 else 0)) // 2 for x in range(int(kmin), int(kmax) + 1)) if 1 <= kmin <= kmax else 0
+        X, nn, status = np.empty((n, f), np.float64), np.empty(n, np.int64), np.empty(n, np.uint32)
+        self._check(self._lib.frisk_window_vectors(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, int(kmin), int(kmax),
+                                                   int(batch_rows), _ptr(X), _ptr(nn), _ptr(status)))
+        return X, nn, status
+
     @property
     def padded_len(self):
         return int(self._lib.frisk_seq_padded_len(self._ctx))

@@ -237,6 +237,31 @@ def thresholdKLD(table, threshold, args, merge=True):
     return feats, chosen
 
 
+def pickedKLD(logKLD, threshold, find_self=False):
+    """thresholdKLD's selection as a mask over the table's rows, before any merging: log10(KLD) >= threshold (<= with --findSelf),
+    never a NaN row."""
+    logs = np.asarray(logKLD, dtype=np.float64).ravel()
+    with np.errstate(invalid="ignore"):
+        pick = (logs <= threshold) if find_self else (logs >= threshold)
+    return pick & ~np.isnan(logs)
+
+
+def spike_rows(logKLD, picked, n):
+    """--spikeNormal: the table rows that stand for "the centre of the self population" beside n anomalies.
+    Candidates are the rows whose log10(KLD) is finite and that thresholdKLD did not pick (`picked`: pickedKLD's mask, already
+    inverted under --findSelf); the centre is the median of log10(KLD) over ALL finite rows; the min(n, candidates) candidates
+    nearest the centre are taken, ties by table order (stable sort), and returned in table order.  No random numbers."""
+    logs = np.asarray(logKLD, dtype=np.float64).ravel()
+    finite = np.isfinite(logs)
+    cand = np.nonzero(finite & ~np.asarray(picked, dtype=bool).ravel())[0]
+    n = min(int(n), int(cand.size))
+    if n <= 0:
+        return np.zeros(0, dtype=np.int64)
+    centre = np.median(logs[finite])
+    nearest = np.argsort(np.abs(logs[cand] - centre), kind="stable")[:n]
+    return np.sort(cand[nearest]).astype(np.int64)
+
+
 class _LazyRows:
     """The selected rows of a big table, in sorted order, as tuples on demand (the callers of thresholdKLD use them rarely)."""
 

@@ -83,6 +83,42 @@ def symmetricCounts(labelled_seqs, pcaMin, pcaMax, device=0):
     return labels, np.vstack(rows)
 
 
+_fallback_logged = False
+
+
+def windowVectors(engine, seq_index, start, stop, pcaMin, pcaMax, labels=None):
+    """symmetricCounts' rows for ranges of the engine's resident batch: row r = the proportions vector of bases
+    [start[r], stop[r]) - 0-based, half-open - of resident scaffold seq_index[r], counted, folded and divided on the device
+    (Engine.window_vectors, csrc/kvec_kernels.h) with the reference's rules applied as symmetricCounts applies them: a range with
+    >= 30 % unresolved bases (L213 / L238) raises the same ValueError, and so does a range without a valid word of some order
+    (the reference would divide by zero at L822).  labels: what the errors call the rows (default seq_index:start+1:stop).
+    pcaMax above the device kernel's orders: the slices are read back and go through symmetricCounts."""
+    global _fallback_logged
+    seq_index = np.asarray(seq_index, dtype=np.int64).ravel()
+    start = np.asarray(start, dtype=np.int64).ravel()
+    stop = np.asarray(stop, dtype=np.int64).ravel()
+    n = int(seq_index.size)
+
+    def name(r):
+        return labels[r] if labels is not None else "%d:%d:%d" % (seq_index[r], start[r] + 1, stop[r])
+    if n == 0:
+        return np.zeros((0, len(feature_keys(pcaMin, pcaMax))))
+    if pcaMax > _ffi.KVEC_MAX_K:
+        if not _fallback_logged:
+            logging.getLogger("frisk_amd").info("k-mer vectors of orders %s..%s: above the device kernel's %s, the slices go through "
+                                                "the scan's count dump instead", pcaMin, pcaMax, _ffi.KVEC_MAX_K)
+            _fallback_logged = True
+        seqs = [(name(r), engine.read_seq(int(seq_index[r]), int(start[r]), int(stop[r] - start[r])).decode("ascii")) for r in range(n)]
+        return symmetricCounts(seqs, pcaMin, pcaMax, device=getattr(engine, "device", 0))[1]
+    X, nn, status = engine.window_vectors(seq_index, start, stop, pcaMin, pcaMax)
+    for r in np.nonzero(np.asarray(nn) >= 0.3 * (stop - start))[0].tolist():
+        raise ValueError("sequence %r has >= 30 %% unresolved bases: no k-mer vector" % (name(r),))
+    for r in np.nonzero(np.asarray(status) & _ffi.KVEC_EMPTY_ORDER)[0].tolist():
+        empty = [x for x in range(pcaMin, pcaMax + 1) if int(status[r]) >> (_ffi.KVEC_ORDER_SHIFT + x) & 1]
+        raise ValueError("row %d (%r) has no valid word of order %s: no k-mer vector" % (r, name(r), empty[0] if empty else "?"))
+    return X
+
+
 # ------------------------------------------------------------------------------------------------ projection / clustering
 DBSCAN_MIN_SAMPLES = 50         # DBSCAN(eps=args.epsDBSCAN, min_samples=50) (L1639)
 KMEANS_N_INIT, KMEANS_MAX_ITER, KMEANS_TOL = 20, 500, 1e-4      # KMeans(n_init=20, max_iter=500, tol=0.0001) (L1647-1649)

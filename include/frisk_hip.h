@@ -178,6 +178,26 @@ int frisk_seq_synth2(frisk_ctx* ctx, const int64_t* lens, int32_t n_seq, uint64_
  * A/T/G/C, a/t/g/c, N for every non-ACGT letter) - test / bench-sampling utility. */
 int frisk_seq_read(frisk_ctx* ctx, int32_t seq_index, int64_t offset, int64_t n, uint8_t* out);
 
+/* ---- k-mer proportion vectors of arbitrary ranges (the projection's input, L1573-1591) -------
+ * Row r of X (n x F doubles on the host, F = number of reverse-complement-folded words of orders kmin..kmax: 2 772 for 1..6) is
+ * the reference's computeKmers(sym=True, pcaMode=True) -> scrubMirrors -> flattenKmerMap(prop=True) vector (L280-367, L797-831) of
+ * bases [start[r], stop[r]) - 0-based, half-open - of scaffold seq_index[r] of the resident batch, counted on the device from the
+ * packed batch (csrc/kvec_kernels.h): lowercase counts, a word with a base outside ACGTacgt does not, and no word reaches past
+ * stop[r].  nn[r] = the reference's countN of the range (positions that are not uppercase A/T/G/C); status[r] has
+ * FRISK_KVEC_EMPTY_ORDER set when the range holds no valid word of some order, and bit FRISK_KVEC_ORDER_SHIFT + x for every such
+ * order x (the row's entries of that order are then 0, never a division by zero).  kmin / kmax are independent of the context's
+ * own orders: 1 <= kmin <= kmax <= FRISK_KVEC_MAX_K.  The rows are computed batch_rows at a time (0: as many as keep the
+ * device-side block of X at or under 256 MB).  FRISK_E_ARG, with nothing launched: no resident batch, a tiled batch, an index out
+ * of range, start < 0, stop <= start, stop > frisk_seq_len, a range of 2^32 bases or more, orders outside the above.  n = 0 is
+ * FRISK_OK and touches no output.  frisk_last_kernel_ms(ctx, 3) = the kernels' time, summed over the batches of the last call. */
+#define FRISK_KVEC_MAX_K 7
+#define FRISK_KVEC_THREADS 256          /* one workgroup per range */
+#define FRISK_KVEC_GRID_CAP 2048        /* workgroups of one launch: further ranges by grid stride */
+#define FRISK_KVEC_EMPTY_ORDER 1u
+#define FRISK_KVEC_ORDER_SHIFT 8        /* status bit 8 + x: order x is the empty one */
+int frisk_window_vectors(frisk_ctx* ctx, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n, int kmin,
+                         int kmax, int64_t batch_rows, double* X, int64_t* nn, uint32_t* status);
+
 /* ---- phase A: genome profile (computeKmers genomeMode=True, L1442) -------------------------
  * reset -> add (once per resident batch; forward counts only) -> [all-reduce across GPUs]
  * -> finalize (adds the reverse complement, L350-351, and builds the genome-side IVOM table). */
@@ -495,7 +515,7 @@ void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);
 void  frisk_host_free(frisk_ctx* ctx, void* ptr);
 
 /* Timing of the most recent launches on the context's stream, measured with HIP events:
- * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel.  Returns milliseconds, <0 if none. */
+ * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels.  Returns milliseconds, <0 if none. */
 double frisk_last_kernel_ms(const frisk_ctx* ctx, int which);
 
 #ifdef __cplusplus
