@@ -13,6 +13,7 @@ OK, E_ARG, E_HIP, E_STATE, E_CAP, E_ZERO_WEIGHT, E_INDEX = 0, -1, -2, -3, -4, -5
 SCAN_RIP, SCAN_SCAFFOLDS_ALL, SCAN_CHUNKS, SCAN_BITS4, SCAN_SIDE4 = 1, 2, 256, 512, 1024
 ROW_KEPT, ROW_ZERO_WEIGHT, ROW_JUMPBACK, ROW_NO_MAXMER = 1, 2, 4, 8
 KVEC_MAX_K, KVEC_THREADS, KVEC_GRID_CAP, KVEC_EMPTY_ORDER, KVEC_ORDER_SHIFT = 7, 256, 2048, 1, 8      # frisk_window_vectors
+RANGES_BIG = 0x10000                                                                                 # frisk_score_ranges
 
 # every symbol include/frisk_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -53,6 +54,7 @@ SYMBOLS = [
                                    C.c_double]),
     ("frisk_seq_read", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P]),
     ("frisk_window_vectors", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
+    ("frisk_score_ranges", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     ("frisk_profile_reset", C.c_int, [_P]),
     ("frisk_profile_add", C.c_int, [_P, C.c_int, C.c_int64, C.c_int64]),
     ("frisk_seq_padded_len", C.c_int64, [_P]),

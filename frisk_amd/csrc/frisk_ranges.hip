@@ -1,0 +1,139 @@
+// frisk_ranges.hip - frisk_score_ranges of the C ABI (include/frisk_hip.h): the scan loop's columns (KLD, GC, RIP indices) of
+// arbitrary ranges of the resident batch against the context's finalised profile (range_kernels.h).  The host checks the rows,
+// sorts them longest first (the workgroups of a launch take its list by grid stride), splits them between the two forms and
+// queues both launches on the context's stream; a range the short form cannot hold reaches the long form through a device list,
+// without a host round trip.  The context is frisk_ctx.h's; the scan's plan and row buffers are not touched.  gfx950 (MI355X)
+// only.  Build: see __graft_entry__.build_hip().
+#include <algorithm>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "frisk_ctx.h"
+#include "range_kernels.h"
+
+namespace {
+
+template <bool K8>
+hipError_t launch_short(const RangeParams& P, int grid, size_t lds, hipStream_t st) {
+    auto kern = range_short_kernel<K8>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+    kern<<<grid, FRISK_RANGE_NT, lds, st>>>(P);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int frisk_score_ranges(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                                  uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri,
+                                  int64_t* nn) {
+    if (!c) return FRISK_E_ARG;
+    if (n < 0) return fail(c, FRISK_E_ARG, "frisk_score_ranges: n < 0");
+    const frisk_ctx::Batch& B = c->b();
+    if (!B.have_seq) return fail(c, FRISK_E_ARG, "frisk_score_ranges: no resident sequence batch");
+    if (B.tiled) return fail(c, FRISK_E_ARG, "frisk_score_ranges: the resident batch holds tiles, not whole scaffolds");
+    const bool rip = (flags & FRISK_SCAN_RIP) != 0;
+    if (rip && !(c->kmin <= 2 && c->kmax >= 2)) return fail(c, FRISK_E_ARG, "FRISK_SCAN_RIP needs kmin <= 2 <= kmax");
+    if (!c->profile_final) return fail(c, FRISK_E_STATE, "frisk_score_ranges: no finalised profile");
+    if (n == 0) return FRISK_OK;
+    if (!seq_index || !start || !stop || !status || !kld || !gc || !nn || (rip && (!pi || !si || !cri)))
+        return fail(c, FRISK_E_ARG, "frisk_score_ranges: null array");
+    std::vector<int64_t> ranges(size_t(n) * 2);
+    for (int64_t r = 0; r < n; ++r) {
+        const int32_t s = seq_index[r];
+        if (s < 0 || s >= B.n_seq) return fail(c, FRISK_E_ARG, "frisk_score_ranges: sequence index out of range in row " + std::to_string(r));
+        if (start[r] < 0 || stop[r] <= start[r] || stop[r] > B.seq_len[size_t(s)] || stop[r] - start[r] > int64_t(0x7FFFFFFF))
+            return fail(c, FRISK_E_ARG, "frisk_score_ranges: range outside the scaffold (or empty, or of 2^31 bases or more) in row " + std::to_string(r));
+        ranges[size_t(2 * r)] = B.seq_off[size_t(s)] + start[r];
+        ranges[size_t(2 * r + 1)] = stop[r] - start[r];
+    }
+    // longest first (ties by row: the order is a function of the call alone), then one list per form
+    std::vector<int64_t> order(static_cast<size_t>(n));
+    std::iota(order.begin(), order.end(), int64_t(0));
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        const int64_t la = ranges[size_t(2 * a + 1)], lb = ranges[size_t(2 * b + 1)];
+        return la != lb ? la > lb : a < b;
+    });
+    const bool k8 = c->kmax == 8;
+    const bool all_long = (flags & FRISK_RANGES_BIG) != 0 || c->kmax > 8;
+    std::vector<int64_t> short_rows, long_rows;
+    for (int64_t r : order) (all_long || ranges[size_t(2 * r + 1)] > FRISK_RANGE_SHORT_MAX ? long_rows : short_rows).push_back(r);
+    const int64_t n_short = int64_t(short_rows.size()), n_long = int64_t(long_rows.size());
+    const int64_t long_cap = n_long + (k8 ? n_short : 0);       // every short row of kmax = 8 may be handed over
+
+    HIPC(c, hipSetDevice(c->device));
+    if (int rc = settle_stream(c)) return rc;
+    const size_t N = size_t(n);
+    const int ncol = rip ? 5 : 2;
+    DevBuf<int64_t> d_ranges, d_short, d_long, d_nn;            // (freed on every return below)
+    DevBuf<unsigned int> d_cnt;                                 // [0]: rows handed over to the long form
+    DevBuf<uint32_t> d_status;
+    DevBuf<double> d_val;
+    HIPC(c, d_ranges.reserve(2 * N, 2 * N));
+    HIPC(c, d_short.reserve(size_t(std::max<int64_t>(n_short, 1)), size_t(std::max<int64_t>(n_short, 1))));
+    HIPC(c, d_long.reserve(size_t(std::max<int64_t>(long_cap, 1)), size_t(std::max<int64_t>(long_cap, 1))));
+    HIPC(c, d_nn.reserve(N, N));
+    HIPC(c, d_cnt.reserve(4, 4));
+    HIPC(c, d_status.reserve(N, N));
+    HIPC(c, d_val.reserve(N * size_t(ncol), N * size_t(ncol)));
+    HIPC(c, hipMemcpyAsync(d_ranges.p, ranges.data(), 2 * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (n_short) HIPC(c, hipMemcpyAsync(d_short.p, short_rows.data(), size_t(n_short) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (n_long) HIPC(c, hipMemcpyAsync(d_long.p, long_rows.data(), size_t(n_long) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemsetAsync(d_cnt.p, 0, 4 * sizeof(unsigned int), c->stream));
+
+    RangeParams P = RangeParams();
+    P.codes = B.d_codes.p; P.inv = B.d_inv.p; P.low = B.d_low.p; P.ig = c->d_ig.p; P.ranges = d_ranges.p;
+    P.kmin = c->kmin; P.kmax = c->kmax; P.rip = rip ? 1u : 0u;
+    P.status = d_status.p; P.nn = d_nn.p; P.kld = d_val.p; P.gc = d_val.p + N;
+    if (rip) { P.pi = d_val.p + 2 * N; P.si = d_val.p + 3 * N; P.cri = d_val.p + 4 * N; }
+
+    // the long form's scratch: one slice of 32-bit tables per workgroup (350 KB at 1..8, 89 MB at K = 12), as many workgroups as
+    // the device can spare scratch for.  The short rows of kmax = 8 may all be handed over, but hardly any is: they add a few
+    // workgroups to the grid, not one each (the grid-stride loop takes whatever the list holds in the end).
+    const int64_t stride = (c->nprof + 3) / 4 * 4;
+    int64_t want = std::min<int64_t>(n_long + std::min<int64_t>(long_cap - n_long, FRISK_RANGE_HANDOVER_WGS), c->num_cu);
+    if (long_cap) {
+        if (size_t(want) * size_t(stride) > c->d_big.cap) {
+            size_t free_b = 0, total_b = 0;
+            HIPC(c, hipMemGetInfo(&free_b, &total_b));
+            const int64_t fit = int64_t((free_b / 2 + c->d_big.cap * 4) / (size_t(stride) * 4));
+            want = std::max<int64_t>(1, std::min(want, fit));
+        }
+        HIPC(c, c->d_big.reserve(size_t(want) * size_t(stride)));
+        HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(want) * size_t(stride) * 4, c->stream));
+    }
+
+    HIPC(c, hipEventRecord(c->ev0, c->stream));
+    if (n_short) {
+        RangeParams S = P;
+        S.list = d_short.p; S.n_list = n_short; S.more = nullptr;
+        S.out_list = d_long.p + n_long; S.out_count = d_cnt.p;
+        const RangeLds L = range_lds(c->kmin, c->kmax);
+        // kmax = 8: the order-8 table leaves room for one workgroup per CU; below, three (43.7 KB at 1..7)
+        const int per_cu = k8 ? 1 : 3;
+        const int grid = int(std::min<int64_t>(n_short, int64_t(c->num_cu) * per_cu));
+        HIPC(c, k8 ? launch_short<true>(S, grid, L.total, c->stream) : launch_short<false>(S, grid, L.total, c->stream));
+    }
+    if (long_cap) {     // (kmax = 8 without a long row: a few workgroups that find the hand-over list empty nearly always)
+        RangeParams G = P;
+        G.list = d_long.p; G.n_list = n_long; G.more = (k8 && n_short) ? d_cnt.p : nullptr;
+        range_long_kernel<<<int(want), FRISK_RANGE_BIG_NT, 0, c->stream>>>(G, c->d_big.p, stride);
+        HIPC(c, hipGetLastError());
+    }
+    HIPC(c, hipEventRecord(c->ev1, c->stream));
+    HIPC(c, hipMemcpyAsync(status, d_status.p, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(nn, d_nn.p, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(kld, P.kld, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(gc, P.gc, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (rip) {
+        HIPC(c, hipMemcpyAsync(pi, P.pi, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(si, P.si, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(cri, P.cri, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->ms[4] = ms;
+    return FRISK_OK;
+}

@@ -531,6 +531,27 @@ class Engine:
         self._check(self._lib.frisk_scan_ivom(self._ctx, int(w), int(inc), flags, int(c0), int(c1), max(n, 1), _ptr(wi), _ptr(gi)))
         return wi[:n], gi[:n]
 
+    def score_ranges(self, seq_index, start, stop, rip=False, big=False):
+        """frisk_score_ranges: the scan loop's columns of bases [start[r], stop[r]) - 0-based, half-open - of resident scaffold
+        seq_index[r], each range scored as the slice it is against the finalised profile.  Returns a ScanResult with seq_index,
+        start, stop (as given), status, kld, gc, pi / si / cri (None without rip) and nn (positions that are not uppercase
+        A/C/G/T); `kept` is False for a range the N filter drops.  big=True (test hook): every range through the global-scratch
+        form - the same bits."""
+        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
+        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
+        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        n = int(seq_index.size)
+        if start.size != n or stop.size != n:
+            raise ValueError("seq_index, start and stop must have one entry per range")
+        new = lambda dt: np.zeros(n, dt)                                   # noqa: E731
+        r = ScanResult(seq_index=seq_index, start=start, stop=stop, status=new(np.uint32), kld=new(np.float64), gc=new(np.float64),
+                       pi=new(np.float64) if rip else None, si=new(np.float64) if rip else None,
+                       cri=new(np.float64) if rip else None, nn=new(np.int64))
+        flags = (_ffi.SCAN_RIP if rip else 0) | (_ffi.RANGES_BIG if big else 0)
+        self._check(self._lib.frisk_score_ranges(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, flags, _ptr(r.status),
+                                                 _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn)))
+        return r
+
     def scan_stat(self):
         """(counter width of the bulk launch, windows handed 4->8 bit, windows handed on to 16 bit, row segments) of the last scan."""
         return tuple(int(self._lib.frisk_last_scan_stat(self._ctx, i)) for i in range(4))

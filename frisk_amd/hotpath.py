@@ -286,6 +286,37 @@ class HotPath:
             raise err
         return table, res
 
+    def scoreRegions(self, args, querySeq, regions, genomeKmers=None):
+        """The loop body L1478-1494 on arbitrary regions instead of the window grid: `regions` = (scaffold name, start, stop)
+        records, 0-based and half-open, each scored as the slice it is (Engine.score_ranges).  The profile is installed from
+        `genomeKmers` (the pickled form) or, without it, computed from args.hostSeq; then `querySeq` is made resident by the
+        native reader.  Returns the ScanResult, rows in the order of `regions`.  A record that names an unknown scaffold or
+        reaches past its end raises ValueError naming the record - it is not clipped."""
+        if genomeKmers is not None:
+            self.setGenomeProfile(genomeKmers)
+        else:
+            self.genomeProfileArrays(args)
+        self._load(querySeq)
+        rip = bool(getattr(args, "RIP", False)) and args.minWordSize <= 2
+        if rip and args.maxWordSize < 2:
+            raise ValueError("2 is not in list")        # range(m, K+1).index(2), reference L478
+        index = {}
+        for i, name in enumerate(self.names):
+            index.setdefault(name, i)
+        lens = self.engine.seq_lens
+        seq, start, stop = [], [], []
+        for no, (name, a, b) in enumerate(regions, 1):
+            what = "region %d (%s:%d-%d)" % (no, name, a + 1, b)
+            if name not in index:
+                raise ValueError("%s names a scaffold that %s does not hold" % (what, querySeq))
+            s = index[name]
+            if a < 0 or b <= a:
+                raise ValueError("%s is empty or starts before the scaffold's first base" % what)
+            if b > lens[s]:
+                raise ValueError("%s reaches past the end of the scaffold (%d bases)" % (what, lens[s]))
+            seq.append(s); start.append(a); stop.append(b)
+        return self.engine.score_ranges(np.asarray(seq, np.int32), np.asarray(start, np.int64), np.asarray(stop, np.int64), rip=rip)
+
     def scanGenome(self, args, querySeq, debug=False):
         """The same as a list of row tuples (tests, small jobs): (rows, result)."""
         table, res = self.scanTable(args, querySeq, debug=debug)

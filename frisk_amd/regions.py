@@ -1,0 +1,171 @@
+"""python -m frisk_amd.regions: score arbitrary regions against the host profile on the device.
+
+The scanner (python -m frisk_amd) scores the windows of one (w, inc) grid.  This module scores the regions a BED or GFF file
+names - merged anomalies, refined boundaries, genes - each as the slice it is, with the same k-mer profile, the same IVOM / KLD,
+GC and RIP arithmetic (Engine.score_ranges -> frisk_score_ranges, csrc/range_kernels.h):
+
+    python -m frisk_amd.regions -H host.fa --gff genes.gff3 --gffFeatures gene          which genes are themselves foreign?
+    python -m frisk_amd.regions -H donor.fa -Q query.fa --bed anomalies.bed             where did these regions come from?
+
+-H, -Q, -m, -k, -t, --maskHost, --recalc and --RIP are the main command line's, with the same defaults and the same inverted
+--recalc (giving it forces recomputation); the genome k-mer cache file in --tempDir is the main command line's too, read when it
+is there and written when it is not.  Exactly one of --bed and --gff names the regions:
+    BED   columns 1-3, 0-based half-open; an optional column 4 is the id; `#`, `track` and `browser` lines are skipped
+    GFF   read as --gffIn reads it (postprocess.read_gff), 1-based inclusive; the id is the ID= attribute, else `.`
+Output (-O, in --tempDir): header `name start stop length windowKLD GC [PI SI CRI] id note`, one row per input record in input
+order, start / stop 1-based inclusive, floats as in the score table.  note: `.`, `unresolved` (30 % or more of the region is not
+uppercase A/C/G/T: not scored, as the reference drops such a window), `ZeroDivisionError` (where the reference would raise it) or
+`noMaxmer` (no valid max-mer: the KLD is the int 0).  A record that names an unknown scaffold or reaches past its end ends the
+run with exit status 1 and a message naming the record; it is not clipped.
+"""
+import argparse
+import gzip
+import logging
+import os
+import pickle
+import sys
+
+from . import _ffi
+from . import cli
+from . import postprocess as pp
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="frisk-regions", description="Score the regions of a BED / GFF file against the host's "
+                                "k-mer profile (KLD, GC, RIP indices), each region as a whole.")
+    p.add_argument("-H", "--hostSeq", type=str, required=True, help="host genome FASTA (one species)")
+    p.add_argument("-Q", "--querySeq", type=str, default=None, help="the regions lie in this FASTA (default: the host)")
+    p.add_argument("-O", "--outfile", type=str, default="region_scores.tsv", help="score table of the regions, written in --tempDir")
+    p.add_argument("-t", "--tempDir", type=str, default="temp", help="working / output directory")
+    p.add_argument("-m", "--minWordSize", type=int, default="1", help="shortest k-mer")
+    p.add_argument("-k", "--maxWordSize", type=int, default="8", help="longest k-mer")
+    p.add_argument("--maskHost", action="store_true", default=False, help="skip soft-masked k-mers when profiling the host")
+    p.add_argument("--recalc", action="store_false", default=True, help="force recomputation of the host k-mer profile")
+    p.add_argument("--RIP", action="store_true", default=False, help="report RIP indices per region")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--bed", type=str, default=None, help="regions as BED: columns 1-3, optional id in column 4")
+    src.add_argument("--gff", type=str, default=None, help="regions as GFF records")
+    p.add_argument("--gffFeatures", type=str, nargs="+", default=None, help="with --gff: keep records of these types (column 3)")
+    return p
+
+
+def read_bed(path):
+    """[(name, start, stop, id)] of a BED file (plain or gzip), 0-based half-open as BED is; id = column 4, else '.'.
+    Skipped: blank lines and lines that start with '#', `track` or `browser`.  ValueError names the file and the line otherwise."""
+    with open(path, "rb") as fh:
+        magic = fh.read(2)
+    out = []
+    with (gzip.open if magic == b"\x1f\x8b" else open)(path, "rt", encoding="utf-8", errors="surrogateescape", newline="\n") as fh:
+        for no, raw in enumerate(fh, 1):
+            line = raw.rstrip("\r\n")
+            if not line.strip() or line.startswith(("#", "track", "browser")):
+                continue
+            f = line.split("\t")
+            if len(f) < 3:
+                raise ValueError("%s, line %d: %d tab-separated fields, a BED record has at least 3" % (path, no, len(f)))
+            try:
+                a, b = int(f[1]), int(f[2])
+            except ValueError:
+                raise ValueError("%s, line %d: start %r and end %r must be integers" % (path, no, f[1], f[2])) from None
+            if a < 0 or b <= a:
+                raise ValueError("%s, line %d: an empty or negative range %d-%d" % (path, no, a, b))
+            out.append((f[0], a, b, f[3] if len(f) > 3 and f[3] else "."))
+    return out
+
+
+def gff_id(line):
+    """The ID= attribute of a GFF record's text, else '.'."""
+    for attr in line.rstrip("\n").split("\t")[8].split(";"):
+        attr = attr.strip()
+        if attr.startswith("ID="):
+            return attr[3:] or "."
+    return "."
+
+
+def read_gff_regions(path, feature_types=None):
+    """[(name, start, stop, id)] of a GFF file's records, 0-based half-open: [column 4 - 1, column 5)."""
+    rec = pp.read_gff(path, feature_types)
+    return [(str(c), int(a), int(b), gff_id(line)) for line, c, a, b in zip(rec.lines, rec.chrom, rec.start, rec.end)]
+
+
+def columns(rip):
+    return ["name", "start", "stop", "length", "windowKLD", "GC"] + (["PI", "SI", "CRI"] if rip else []) + ["id", "note"]
+
+
+def region_rows(regions, res, rip, fmt):
+    """One tab-separated line per region, in input order; start / stop 1-based inclusive."""
+    for r, (name, a, b, ident) in enumerate(regions):
+        st = int(res.status[r])
+        if not st & _ffi.ROW_KEPT:
+            note = "unresolved"
+        elif st & _ffi.ROW_ZERO_WEIGHT:
+            note = "ZeroDivisionError"
+        elif st & _ffi.ROW_NO_MAXMER:
+            note = "noMaxmer"
+        else:
+            note = "."
+        kld = 0 if note == "noMaxmer" else float(res.kld[r])            # the int 0 of an empty sum (L465)
+        vals = [name, a + 1, b, b - a, kld, float(res.gc[r])]
+        if rip:
+            vals += [float(res.pi[r]), float(res.si[r]), float(res.cri[r])]
+        yield "\t".join([fmt(v) for v in vals] + [ident, note]) + "\n"
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    log = logging.getLogger("frisk_amd")
+    if args.minWordSize > args.maxWordSize:
+        logging.error("[ERROR] Minimum kmer size (-m/--minWordSize) must be less than Maximum kmer size (-k/--maxWordSize)\n")
+        return 1
+    if args.gffFeatures and not args.gff:
+        logging.error("[ERROR] --gffFeatures goes with --gff\n")
+        return 1
+    try:
+        regions = read_bed(args.bed) if args.bed else read_gff_regions(args.gff, args.gffFeatures)
+    except (OSError, ValueError) as err:
+        logging.error("[ERROR] %s\n", err)
+        return 1
+    rip = bool(args.RIP) and args.minWordSize <= 2
+    if not os.path.isdir(os.path.abspath(args.tempDir)):
+        os.makedirs(os.path.abspath(args.tempDir))
+    out_path = os.path.join(args.tempDir, args.outfile)
+    header = "\t".join(columns(rip)) + "\n"
+    if not regions:
+        with open(out_path, "w") as fh:
+            fh.write(header)
+        log.info("No regions in %s: wrote the header to %s", args.bed or args.gff, out_path)
+        return 0
+
+    from .hotpath import HotPath
+    genomepickle = cli.makePicklePath(args, "genome")
+    hp = HotPath(args.minWordSize, args.maxWordSize, device=0, cache_dir=args.tempDir, use_cache=bool(args.recalc))
+    try:
+        genomeKmers = None
+        if os.path.isfile(genomepickle) and args.recalc:        # --recalc is store_false: giving it forces recomputation
+            log.info("Importing previously calculated genome kmers from %s", genomepickle)
+            with open(genomepickle, "rb") as fh:
+                genomeKmers = pickle.load(fh, encoding="latin1")
+        else:
+            log.info("Calculating kmers for host sequence: %s", args.hostSeq)
+        try:
+            res = hp.scoreRegions(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], genomeKmers=genomeKmers)
+        except ValueError as err:
+            logging.error("[ERROR] %s\n", err)
+            return 1
+        if genomeKmers is None:
+            tmp = genomepickle + ".tmp%d" % os.getpid()
+            with open(tmp, "wb") as fh:
+                pickle.dump(hp.profileMaps(), fh, protocol=2)
+            os.replace(tmp, genomepickle)
+    finally:
+        hp.close()
+    with open(out_path, "w") as fh:
+        fh.write(header)
+        fh.writelines(region_rows(regions, res, rip, cli._fmt()))
+    log.info("Scored %d regions: %s", len(regions), out_path)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -252,6 +252,29 @@ int frisk_scan(frisk_ctx* ctx, int32_t w, int32_t inc, uint32_t flags, int64_t c
                double* kld, double* gc, double* pi, double* si, double* cri,
                uint32_t* dbg_counts, int64_t* dbg_meta);
 
+/* ---- the scan loop's columns of arbitrary ranges -------------------------------------------
+ * Row r is one iteration of the scan loop (L1478-1494: computeKmers(window), both IvomBuilds, KLD, calcGC, calcRIP) on bases
+ * [start[r], stop[r]) - 0-based, half-open - of scaffold seq_index[r] of the resident batch, against the context's finalised
+ * profile and orders: a merged anomaly, a refined boundary, a gene, or - with another genome's profile in the context - the
+ * same regions against a donor.  The range is scored as the slice it is (as frisk_window_vectors counts it): no word reaches past
+ * stop[r], lowercase counts in words, S = its uppercase A/C/G/T.  One workgroup per range (csrc/range_kernels.h): 16-bit tables
+ * in LDS for kmax <= 8 and ranges up to 65 535 bases, 32-bit tables in global scratch otherwise; a row's bits depend on the range
+ * and the profile alone - not on the other rows, their order, the form or the grid.
+ * status[r]: the FRISK_ROW_* bits (FRISK_ROW_JUMPBACK is never set); nn[r] = length - S, always written.  A range with
+ * nn >= 0.3 * length is left unscored as the reference leaves such a window (L238): no FRISK_ROW_KEPT, NaN in every double
+ * column.  FRISK_ROW_NO_MAXMER: kld = 0.  FRISK_ROW_ZERO_WEIGHT (a max-mer present and kmin-1 <= S <= kmax-1, or a max-mer without
+ * genome weight, as in frisk_scan): kld = NaN.  Ranges with S < kmin-1 (negative divisors) are unspecified, as in frisk_scan.
+ * flags: FRISK_SCAN_RIP fills pi/si/cri (nullable otherwise; needs kmin <= 2 <= kmax, else FRISK_E_ARG); FRISK_RANGES_BIG is a
+ * test hook that forces the global-scratch form on every range (the same bits).
+ * FRISK_E_ARG, with nothing launched: no resident batch, a tiled batch, an index out of range, start < 0, stop <= start,
+ * stop > frisk_seq_len, a range of 2^31 bases or more, a null required array.  FRISK_E_STATE: no finalised profile.  n = 0 is
+ * FRISK_OK and touches no output.  A streamed batch is waited for.  The scan's plan and rows are left alone.
+ * frisk_last_kernel_ms(ctx, 4) = the kernels' time of the last call. */
+#define FRISK_RANGES_BIG 0x10000u
+int frisk_score_ranges(frisk_ctx* ctx, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                       uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri,
+                       int64_t* nn);
+
 /* Test utility (kmax <= 6): the two distributions IvomBuild returns for each candidate window of [c0,c1) (L1481-1482, L369-457) -
  * window-side and genome-side interpolated probabilities of the window's present max-mers, each normalised to sum 1 -
  * as dense vectors of 4^kmax doubles per candidate (0 for absent max-mers; all 0 for windows the reference drops). */
@@ -515,7 +538,8 @@ void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);
 void  frisk_host_free(frisk_ctx* ctx, void* ptr);
 
 /* Timing of the most recent launches on the context's stream, measured with HIP events:
- * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels.  Returns milliseconds, <0 if none. */
+ * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels, 4 frisk_score_ranges' kernels.
+ * Returns milliseconds, <0 if none. */
 double frisk_last_kernel_ms(const frisk_ctx* ctx, int which);
 
 #ifdef __cplusplus
