@@ -49,7 +49,7 @@ struct frisk_ctx {
     int num_cu = 256;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double ms[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};  // frisk_last_kernel_ms: scan, profile_add, pack / load, window vectors, score ranges
+    double ms[6] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0};    // frisk_last_kernel_ms: scan, profile_add, pack / load, window vectors, score ranges, the panel
     std::string err;
 
     // sequence batches: bat[cur] is the resident one; the other slot receives the next batch while the resident one is
@@ -120,6 +120,10 @@ struct frisk_ctx {
     DevBuf<int64_t> d_meta;          // {totalLen, exMax, nnTotal} of the finalised profile, on the device
     PinBuf<int64_t> h_meta;          // page-locked mirror, valid after the stream has been synchronised
     bool profile_final = false;
+    // the panel of frisk_score_ranges_panel: snapshots of finalised genome-side tables, FRISK_PANEL_TILE to a block of
+    // [code][FRISK_PANEL_TILE] doubles (panel_kernels.h); a block is allocated when its first slot is pushed
+    DevBuf<double> panel_tile[FRISK_PANEL_MAX / FRISK_PANEL_TILE];
+    int32_t panel_n = 0;
     bool ms_pending[3] = {false, false, false};     // events recorded, elapsed time not read yet (frisk_last_kernel_ms)
     hipEvent_t evp0 = nullptr, evp1 = nullptr;      // profile_add kernel
 

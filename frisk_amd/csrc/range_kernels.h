@@ -112,12 +112,13 @@ __device__ inline void range_constants(int64_t S, double* r) {
 }
 
 // THE scoring body: one present max-mer - window-side IVOM in closed form from the counts of its prefixes, genome side from the
-// table, three exact additions.  count(x, c): occurrences of the x-mer c in the range.
+// table, three exact additions.  count(x, c): occurrences of the x-mer c in the range.  In two halves: what the range alone
+// decides (W, A), and what a profile's value Ig adds to its three sums - panel_kernels.h runs the second once per profile.
 template <typename COUNT>
-__device__ inline void range_score_maxmer(uint32_t code, int kmin, int kmax, const double* r, const double* __restrict__ ig,
-                                          COUNT&& count, ExactSum& accw, ExactSum& accg, ExactSum& acct) {
-    unsigned long long W = 0;
-    double A = 0.0;
+__device__ inline void range_maxmer_window(uint32_t code, int kmin, int kmax, const double* r, COUNT&& count, unsigned long long& W,
+                                           double& A) {
+    W = 0;
+    A = 0.0;
 #pragma unroll
     for (int x = 1; x <= FRISK_MAX_K; ++x) {
         if (x < kmin || x > kmax) continue;
@@ -126,12 +127,21 @@ __device__ inline void range_score_maxmer(uint32_t code, int kmin, int kmax, con
         W += (unsigned long long)cx << (2 * x);                         // count * 4**x (L399-408)
         A = __builtin_fma(cd * cd, r[x], A);                            // w_x * p_x = c^2 4^x / D_x
     }
-    const double Ig = ig[code];
-    const double ratio = div_exact(A, double(W) * Ig);
+}
+__device__ inline void range_maxmer_add(double A, double Wd, double Ig, ExactSum& accw, ExactSum& accg, ExactSum& acct) {
+    const double ratio = div_exact(A, Wd * Ig);
     const double Iw = ratio * Ig;
     exact_add(accw, Iw);
     exact_add(accg, Ig);
     exact_add(acct, Iw * log_pos(ratio));
+}
+template <typename COUNT>
+__device__ inline void range_score_maxmer(uint32_t code, int kmin, int kmax, const double* r, const double* __restrict__ ig,
+                                          COUNT&& count, ExactSum& accw, ExactSum& accg, ExactSum& acct) {
+    unsigned long long W;
+    double A;
+    range_maxmer_window(code, kmin, kmax, r, count, W, A);
+    range_maxmer_add(A, double(W), ig[code], accw, accg, acct);
 }
 
 // the three sums over the workgroup, the KLD (L453-454, L465-470) and the row's status; every thread calls, thread 0 writes
@@ -159,13 +169,18 @@ __device__ inline uint32_t range_status(uint32_t nvalid_top, int64_t S, int kmin
     return status;
 }
 
+// what stages 1 and 2 make of a row (workgroup-uniform): its tables are ready to be scored, the long form takes it over, or the
+// N rule drops it
+enum { RANGE_ROW_SCORE = 0, RANGE_ROW_HANDED = 1, RANGE_ROW_DROPPED = 2 };
+
 // ---- short form -------------------------------------------------------------------------------------------------------------
+// Stages 1 and 2 of one row, every thread of the workgroup: clear, count, composition, the N rule, marginalisation; gc / RIP / nn
+// of a kept row and every column of a dropped one are written here.  `tl`: 8 words of LDS.  Ends behind a barrier: the tables
+// (T) may be read.  Shared with panel_kernels.h.
 template <bool K8>
-__global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const RangeParams P) {
-    constexpr int NT = FRISK_RANGE_NT, NW = NT / 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ uint32_t tl[8];
-    __shared__ double red[NW * 6];
+__device__ inline int range_short_tables(const RangeParams& P, int64_t row, unsigned char* lds, uint32_t* tl, WinTables<K8>& T,
+                                         int64_t& S, uint32_t& nvalid_top) {
+    constexpr int NT = FRISK_RANGE_NT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int kmin = P.kmin;
     const int kmax = K8 ? 8 : P.kmax;
@@ -175,11 +190,7 @@ __global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const Range
     uint32_t* small32 = reinterpret_cast<uint32_t*>(lds + L.small);
     uint16_t* small16 = reinterpret_cast<uint16_t*>(lds + L.small);
     uint16_t* orph = reinterpret_cast<uint16_t*>(lds + L.orphans);
-    const uint32_t nK = 1u << (2 * kmax);
-
-    const int64_t n_rows = range_rows(P);
-    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t row = P.list[q];
+    {
         const int64_t g0 = P.ranges[2 * row];
         const int n = int(P.ranges[2 * row + 1]);       // <= FRISK_RANGE_SHORT_MAX
         // ---- clear: 128 KiB over 512 threads is 16 uint4 stores each
@@ -233,19 +244,19 @@ __global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const Range
         }
         __syncthreads();
         const int64_t upA = range_uni(tl[0]), upT = range_uni(tl[1]), upG = range_uni(tl[2]), upC = range_uni(tl[3]);
-        const uint32_t nvalid_top = range_uni(tl[4]);
+        nvalid_top = range_uni(tl[4]);
         const int n_orph = K8 ? int(range_uni(tl[5])) : 0;
         if (K8 && n_orph > FRISK_RANGE_ORPHANS) {       // the list is incomplete: the long form scores this row
             if (tid == 0) P.out_list[atomicAdd(P.out_count, 1u)] = row;
             __syncthreads();                            // the counters are cleared for the next range only after every read of them
-            continue;
+            return RANGE_ROW_HANDED;
         }
-        const int64_t S = upA + upT + upG + upC;                            // windowSpace (L380)
+        S = upA + upT + upG + upC;                                          // windowSpace (L380)
         const int64_t nn = int64_t(n) - S;
         if (double(nn) >= 0.3 * double(n)) {                                // L237-241 / L213, in double like CPython
             if (tid == 0) range_write_unresolved(P, row, nn);
             __syncthreads();
-            continue;
+            return RANGE_ROW_DROPPED;
         }
 
         // ---- stage 2: marginalise the small tables: C_x[q] = D_x[q] + sum_b C_{x+1}[4q+b]
@@ -257,7 +268,6 @@ __global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const Range
             }
             __syncthreads();
         }
-        WinTables<K8> T;
         T.t8_16 = reinterpret_cast<const uint16_t*>(t8);
         T.small16 = small16;
         T.orph = orph; T.n_orph = n_orph;
@@ -270,8 +280,34 @@ __global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const Range
         }
         T.kmin = kmin;
         auto count = [&](int x, uint32_t c) -> uint32_t { return T.count(x, c); };
-        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
         if (tid == 0) range_write_composition(P, row, S, upG + upC, nn, count);
+    }
+    return RANGE_ROW_SCORE;
+}
+
+template <bool K8>
+__global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const RangeParams P) {
+    constexpr int NT = FRISK_RANGE_NT, NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ uint32_t tl[8];
+    __shared__ double red[NW * 6];
+    const int tid = threadIdx.x;
+    const int kmin = P.kmin;
+    const int kmax = K8 ? 8 : P.kmax;
+    const RangeLds L = range_lds(kmin, kmax);
+    const uint32_t* t8 = reinterpret_cast<const uint32_t*>(lds);
+    const uint16_t* small16 = reinterpret_cast<const uint16_t*>(lds + L.small);
+    const uint32_t nK = 1u << (2 * kmax);
+
+    const int64_t n_rows = range_rows(P);
+    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
+        const int64_t row = P.list[q];
+        WinTables<K8> T;
+        int64_t S;
+        uint32_t nvalid_top;
+        if (range_short_tables<K8>(P, row, lds, tl, T, S, nvalid_top) != RANGE_ROW_SCORE) continue;
+        auto count = [&](int x, uint32_t c) -> uint32_t { return T.count(x, c); };
+        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
 
         // ---- stages 3 + 4: every non-empty bin of the order-K table is a present max-mer
         double r[FRISK_MAX_K + 1];
@@ -301,18 +337,20 @@ __global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const Range
 
 // ---- long form --------------------------------------------------------------------------------------------------------------
 // `big`: one slice of `big_stride` 32-bit words per workgroup, all-zero at launch and between ranges
-__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void range_long_kernel(const RangeParams P, uint32_t* __restrict__ big, int64_t big_stride) {
-    constexpr int NT = FRISK_RANGE_BIG_NT, NW = NT / 64;
-    __shared__ uint32_t tl[8];
-    __shared__ double red[NW * 6];
+// the slice is zeroed by ordinary stores, made visible at L2 before the next range's atomics
+__device__ inline void range_zero_tables(uint32_t* cnt, int64_t big_stride) {
+    for (int64_t i = threadIdx.x; i < big_stride / 4; i += FRISK_RANGE_BIG_NT) reinterpret_cast<uint4*>(cnt)[i] = make_uint4(0, 0, 0, 0);
+    __threadfence();
+}
+
+// Stages 1 and 2 of one row on the workgroup's slice `cnt`, as range_short_tables; a dropped row's slice is zeroed again here, a
+// scored row's by the caller behind its last read.  Shared with panel_kernels.h.
+__device__ inline int range_long_tables(const RangeParams& P, int64_t row, uint32_t* cnt, int64_t big_stride, uint32_t* tl, int64_t& S,
+                                        uint32_t& nvalid_top) {
+    constexpr int NT = FRISK_RANGE_BIG_NT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int kmin = P.kmin, kmax = P.kmax;
-    uint32_t* cnt = big + int64_t(blockIdx.x) * big_stride;
-    const int64_t offK = table_offset(kmin, kmax);
-    const uint32_t nK = 1u << (2 * kmax);
-    const int64_t n_rows = range_rows(P);
-    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t row = P.list[q];
+    {
         const int64_t g0 = P.ranges[2 * row], n = P.ranges[2 * row + 1];
         if (tid < 8) tl[tid] = 0;
         __syncthreads();
@@ -351,18 +389,14 @@ __global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void range_long_kernel(const Ra
         __threadfence();
         __syncthreads();
         const int64_t upA = range_uni(tl[0]), upT = range_uni(tl[1]), upG = range_uni(tl[2]), upC = range_uni(tl[3]);
-        const uint32_t nvalid_top = range_uni(tl[4]);
-        const int64_t S = upA + upT + upG + upC;
+        nvalid_top = range_uni(tl[4]);
+        S = upA + upT + upG + upC;
         const int64_t nn = n - S;
-        auto zero_tables = [&]() {          // ordinary stores, made visible at L2 before the next range's atomics
-            for (int64_t i = tid; i < big_stride / 4; i += NT) reinterpret_cast<uint4*>(cnt)[i] = make_uint4(0, 0, 0, 0);
-            __threadfence();
-        };
         if (double(nn) >= 0.3 * double(n)) {
-            zero_tables();
+            range_zero_tables(cnt, big_stride);
             if (tid == 0) range_write_unresolved(P, row, nn);
             __syncthreads();
-            continue;
+            return RANGE_ROW_DROPPED;
         }
         // ---- stage 2: C_x[q] = D_x[q] + sum_b C_{x+1}[4q+b], level by level
         for (int x = kmax - 1; x >= kmin; --x) {
@@ -374,8 +408,28 @@ __global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void range_long_kernel(const Ra
             __syncthreads();
         }
         auto count = [&](int x, uint32_t c) -> uint32_t { return cnt[table_offset(kmin, x) + c]; };
-        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
         if (tid == 0) range_write_composition(P, row, S, upG + upC, nn, count);
+    }
+    return RANGE_ROW_SCORE;
+}
+
+__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void range_long_kernel(const RangeParams P, uint32_t* __restrict__ big, int64_t big_stride) {
+    constexpr int NT = FRISK_RANGE_BIG_NT, NW = NT / 64;
+    __shared__ uint32_t tl[8];
+    __shared__ double red[NW * 6];
+    const int tid = threadIdx.x;
+    const int kmin = P.kmin, kmax = P.kmax;
+    uint32_t* cnt = big + int64_t(blockIdx.x) * big_stride;
+    const int64_t offK = table_offset(kmin, kmax);
+    const uint32_t nK = 1u << (2 * kmax);
+    const int64_t n_rows = range_rows(P);
+    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
+        const int64_t row = P.list[q];
+        int64_t S;
+        uint32_t nvalid_top;
+        if (range_long_tables(P, row, cnt, big_stride, tl, S, nvalid_top) != RANGE_ROW_SCORE) continue;
+        auto count = [&](int x, uint32_t c) -> uint32_t { return cnt[table_offset(kmin, x) + c]; };
+        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
         double r[FRISK_MAX_K + 1];
         range_constants(S, r);
         ExactSum accw = exact_begin(), accg = exact_begin(), acct = exact_begin();
@@ -384,6 +438,6 @@ __global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void range_long_kernel(const Ra
             range_score_maxmer(code, kmin, kmax, r, P.ig, count, accw, accg, acct);
         }
         range_finish<NW>(P, row, status, nvalid_top, accw, accg, acct, red);    // (its barrier: every read of the tables is done)
-        zero_tables();
+        range_zero_tables(cnt, big_stride);
     }
 }

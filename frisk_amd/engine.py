@@ -38,6 +38,22 @@ class ScanResult:
         return int(self.status.shape[0])
 
 
+class PanelResult:
+    """score_ranges_panel: `status` and `kld` are (P, n) - one plane per profile of the panel -, every other column is the
+    ranges' own; plane(p) is the ScanResult that score_ranges returns under profile p."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def plane(self, p):
+        cols = dict(self.__dict__)
+        cols.update(status=self.status[p], kld=self.kld[p])
+        return ScanResult(**cols)
+
+    def __len__(self):
+        return int(self.status.shape[1])
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -550,6 +566,42 @@ class Engine:
         flags = (_ffi.SCAN_RIP if rip else 0) | (_ffi.RANGES_BIG if big else 0)
         self._check(self._lib.frisk_score_ranges(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, flags, _ptr(r.status),
                                                  _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn)))
+        return r
+
+    # the panel: snapshots of finalised genome profiles on the device, scored together (csrc/panel_kernels.h)
+    def panel_reset(self):
+        """Empty the panel and free its memory."""
+        self._check(self._lib.frisk_panel_reset(self._ctx))
+
+    def panel_push(self):
+        """Append a snapshot of the finalised genome profile to the panel; returns its slot (= its plane in score_ranges_panel).
+        Later profile calls do not change the slot."""
+        slot = C.c_int32(-1)
+        self._check(self._lib.frisk_panel_push(self._ctx, C.byref(slot)))
+        return int(slot.value)
+
+    @property
+    def panel_size(self):
+        return int(self._lib.frisk_panel_size(self._ctx))
+
+    def score_ranges_panel(self, seq_index, start, stop, rip=False, big=False):
+        """frisk_score_ranges_panel: score_ranges against every profile of the panel in one pass - each range is counted once.
+        Returns a PanelResult: status and kld of shape (P, n), plane p bit for bit the score_ranges rows under profile p; gc,
+        pi / si / cri (None without rip), nn, seq_index, start, stop as in score_ranges (they do not depend on the profile)."""
+        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
+        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
+        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        n = int(seq_index.size)
+        if start.size != n or stop.size != n:
+            raise ValueError("seq_index, start and stop must have one entry per range")
+        planes = self.panel_size
+        new = lambda dt: np.zeros(n, dt)                                   # noqa: E731
+        r = PanelResult(seq_index=seq_index, start=start, stop=stop, status=np.zeros((planes, n), np.uint32),
+                        kld=np.zeros((planes, n), np.float64), gc=new(np.float64), pi=new(np.float64) if rip else None,
+                        si=new(np.float64) if rip else None, cri=new(np.float64) if rip else None, nn=new(np.int64))
+        flags = (_ffi.SCAN_RIP if rip else 0) | (_ffi.RANGES_BIG if big else 0)
+        self._check(self._lib.frisk_score_ranges_panel(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, flags, _ptr(r.status),
+                                                       _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn)))
         return r
 
     def scan_stat(self):

@@ -296,6 +296,11 @@ class HotPath:
             self.setGenomeProfile(genomeKmers)
         else:
             self.genomeProfileArrays(args)
+        seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
+        return self.engine.score_ranges(seq, start, stop, rip=rip)
+
+    def _regionArrays(self, args, querySeq, regions):
+        """scoreRegions / scoreRegionsPanel: make `querySeq` resident and turn the records into (seq_index, start, stop, rip)."""
         self._load(querySeq)
         rip = bool(getattr(args, "RIP", False)) and args.minWordSize <= 2
         if rip and args.maxWordSize < 2:
@@ -315,7 +320,32 @@ class HotPath:
             if b > lens[s]:
                 raise ValueError("%s reaches past the end of the scaffold (%d bases)" % (what, lens[s]))
             seq.append(s); start.append(a); stop.append(b)
-        return self.engine.score_ranges(np.asarray(seq, np.int32), np.asarray(start, np.int64), np.asarray(stop, np.int64), rip=rip)
+        return np.asarray(seq, np.int32), np.asarray(start, np.int64), np.asarray(stop, np.int64), rip
+
+    def scoreRegionsPanel(self, args, querySeq, regions, donors, genomeKmers=None, donorKmers=None):
+        """scoreRegions against the host AND a panel of donor genomes in one pass over the regions (Engine.score_ranges_panel:
+        each region is counted once).  `donors`: FASTA paths.  The host's profile, then each donor's, is installed from its
+        pickled form (`genomeKmers`; `donorKmers[path]`) or, without it, computed as genomeProfileArrays computes the host's -
+        args.maskHost applies to every profile - and pushed to the engine's panel; then `querySeq` is made resident and the
+        regions are checked as scoreRegions checks them.  Returns (PanelResult, plane of the host, [plane of each donor]).
+        self.panelProfiles[path] = the profile_get() arrays of every profile that was computed here, for the caller's caches."""
+        import argparse
+        e = self.engine
+        e.panel_reset()
+        self.panelProfiles = {}
+        given = dict(donorKmers or {})
+        given[args.hostSeq] = genomeKmers
+        planes = []
+        for path in [args.hostSeq] + list(donors):
+            if given.get(path) is not None:
+                self.setGenomeProfile(given[path])
+            else:
+                one = argparse.Namespace(**vars(args))
+                one.hostSeq = path
+                self.panelProfiles[path] = self.genomeProfileArrays(one)
+            planes.append(e.panel_push())
+        seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
+        return e.score_ranges_panel(seq, start, stop, rip=rip), planes[0], planes[1:]
 
     def scanGenome(self, args, querySeq, debug=False):
         """The same as a list of row tuples (tests, small jobs): (rows, result)."""

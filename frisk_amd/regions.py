@@ -17,6 +17,17 @@ order, start / stop 1-based inclusive, floats as in the score table.  note: `.`,
 uppercase A/C/G/T: not scored, as the reference drops such a window), `ZeroDivisionError` (where the reference would raise it) or
 `noMaxmer` (no valid max-mer: the KLD is the int 0).  A record that names an unknown scaffold or reaches past its end ends the
 run with exit status 1 and a message naming the record; it is not clipped.
+
+    python -m frisk_amd.regions -H host.fa -Q query.fa --bed anomalies.bed --donors d1.fa d2.fa     which donor is nearest?
+
+--donors scores every region against the host's profile AND each donor's in one pass over the regions (Engine.score_ranges_panel ->
+frisk_score_ranges_panel, csrc/panel_kernels.h: a region is counted once).  Labels are the FASTA basenames, the host's included;
+two equal labels end the run with exit status 1.  Each donor's genome k-mer cache is the file the main command line uses with that
+FASTA as -H: read when it is there and --recalc was not given, written otherwise; --maskHost applies to every profile.  -O is
+byte for byte the file of the same run without --donors.  --donorOutfile (in --tempDir): header `name start stop length id <host
+label> <donor labels, command-line order> nearest margin`, one row per input record; a cell is the KLD as -O would print it under
+that profile (the int 0 for noMaxmer, nan for unresolved / ZeroDivisionError), `nearest` the label of the smallest non-NaN cell
+(the first in column order wins a tie; `.` for none), `margin` the second smallest minus the smallest (`.` with fewer than two).
 """
 import argparse
 import gzip
@@ -46,6 +57,10 @@ def build_parser():
     src.add_argument("--bed", type=str, default=None, help="regions as BED: columns 1-3, optional id in column 4")
     src.add_argument("--gff", type=str, default=None, help="regions as GFF records")
     p.add_argument("--gffFeatures", type=str, nargs="+", default=None, help="with --gff: keep records of these types (column 3)")
+    p.add_argument("--donors", type=str, nargs="+", default=None, help="candidate donor genomes (FASTA): score every region against "
+                   "each of them too, in the same pass, and name the nearest profile")
+    p.add_argument("--donorOutfile", type=str, default="region_donor_scores.tsv", help="with --donors: the per-donor KLD table, "
+                   "written in --tempDir")
     return p
 
 
@@ -92,23 +107,88 @@ def columns(rip):
     return ["name", "start", "stop", "length", "windowKLD", "GC"] + (["PI", "SI", "CRI"] if rip else []) + ["id", "note"]
 
 
+def region_cell(status, kld):
+    """(note, KLD as it is printed) of one row under one profile: the int 0 of an empty sum (L465) for `noMaxmer`."""
+    st = int(status)
+    if not st & _ffi.ROW_KEPT:
+        note = "unresolved"
+    elif st & _ffi.ROW_ZERO_WEIGHT:
+        note = "ZeroDivisionError"
+    elif st & _ffi.ROW_NO_MAXMER:
+        note = "noMaxmer"
+    else:
+        note = "."
+    return note, (0 if note == "noMaxmer" else float(kld))
+
+
 def region_rows(regions, res, rip, fmt):
     """One tab-separated line per region, in input order; start / stop 1-based inclusive."""
     for r, (name, a, b, ident) in enumerate(regions):
-        st = int(res.status[r])
-        if not st & _ffi.ROW_KEPT:
-            note = "unresolved"
-        elif st & _ffi.ROW_ZERO_WEIGHT:
-            note = "ZeroDivisionError"
-        elif st & _ffi.ROW_NO_MAXMER:
-            note = "noMaxmer"
-        else:
-            note = "."
-        kld = 0 if note == "noMaxmer" else float(res.kld[r])            # the int 0 of an empty sum (L465)
+        note, kld = region_cell(res.status[r], res.kld[r])
         vals = [name, a + 1, b, b - a, kld, float(res.gc[r])]
         if rip:
             vals += [float(res.pi[r]), float(res.si[r]), float(res.cri[r])]
         yield "\t".join([fmt(v) for v in vals] + [ident, note]) + "\n"
+
+
+def nearest_margin(cells):
+    """(index of the smallest non-NaN cell or None, second smallest minus smallest or None) of one region's KLDs, one per
+    profile in column order.  The first in column order wins a tie - and ties are real: a region with a single present max-mer
+    has KLD 0 against every profile.  No margin with fewer than two non-NaN cells."""
+    best = sorted((v, i) for i, v in enumerate(cells) if v == v)
+    if not best:
+        return None, None
+    return best[0][1], (best[1][0] - best[0][0] if len(best) > 1 else None)
+
+
+def donor_columns(labels):
+    return ["name", "start", "stop", "length", "id"] + list(labels) + ["nearest", "margin"]
+
+
+def donor_rows(regions, panel, planes, labels, fmt):
+    """One line per region of the per-donor table: the KLD against each profile (plane planes[i] of `panel` under labels[i]),
+    printed as region_rows prints it for that profile, then the nearest profile's label and its margin (`.` for none)."""
+    for r, (name, a, b, ident) in enumerate(regions):
+        cells = [region_cell(panel.status[p][r], panel.kld[p][r])[1] for p in planes]
+        near, margin = nearest_margin(cells)
+        yield "\t".join([fmt(v) for v in [name, a + 1, b, b - a]] + [ident] + [fmt(v) for v in cells] +
+                        ["." if near is None else labels[near], "." if margin is None else fmt(margin)]) + "\n"
+
+
+def _load_pickle(path, log):
+    log.info("Importing previously calculated genome kmers from %s", path)
+    with open(path, "rb") as fh:
+        return pickle.load(fh, encoding="latin1")
+
+
+def _dump_pickle(path, maps):
+    tmp = path + ".tmp%d" % os.getpid()
+    with open(tmp, "wb") as fh:
+        pickle.dump(maps, fh, protocol=2)
+    os.replace(tmp, path)
+
+
+def score_with_donors(args, hp, regions, log):
+    """--donors: the host's and every donor's profile into the engine's panel - each from its genome k-mer cache (the file the main
+    command line would use with that FASTA as -H) when it is there and --recalc was not given, computed and cached otherwise -,
+    then one pass over the regions.  Returns (PanelResult, [plane of the host, planes of the donors])."""
+    from .hotpath import profileToMaps
+    paths = [args.hostSeq] + list(args.donors)
+    caches, have = {}, {}
+    for path in paths:
+        one = argparse.Namespace(**vars(args))
+        one.hostSeq = path
+        caches[path] = cli.makePicklePath(one, "genome")
+        if os.path.isfile(caches[path]) and args.recalc:
+            have[path] = _load_pickle(caches[path], log)
+        else:
+            log.info("Calculating kmers for %s sequence: %s", "host" if path == args.hostSeq else "donor", path)
+    panel, host, donors = hp.scoreRegionsPanel(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], args.donors,
+                                               genomeKmers=have.get(args.hostSeq),
+                                               donorKmers={p: have[p] for p in args.donors if p in have})
+    for path, arrays in hp.panelProfiles.items():
+        _dump_pickle(caches[path], profileToMaps(*arrays, args.minWordSize, args.maxWordSize))
+    return panel, [host] + list(donors)
 
 
 def main(argv=None):
@@ -120,6 +200,11 @@ def main(argv=None):
         return 1
     if args.gffFeatures and not args.gff:
         logging.error("[ERROR] --gffFeatures goes with --gff\n")
+        return 1
+    labels = [os.path.basename(p) for p in [args.hostSeq] + list(args.donors or [])]
+    if len(set(labels)) != len(labels):
+        logging.error("[ERROR] the host and the donors (--donors) must differ in their file names, which label the columns: %s\n",
+                      " ".join(labels))
         return 1
     try:
         regions = read_bed(args.bed) if args.bed else read_gff_regions(args.gff, args.gffFeatures)
@@ -134,36 +219,47 @@ def main(argv=None):
     if not regions:
         with open(out_path, "w") as fh:
             fh.write(header)
+        if args.donors:
+            with open(os.path.join(args.tempDir, args.donorOutfile), "w") as fh:
+                fh.write("\t".join(donor_columns(labels)) + "\n")
         log.info("No regions in %s: wrote the header to %s", args.bed or args.gff, out_path)
         return 0
 
     from .hotpath import HotPath
     genomepickle = cli.makePicklePath(args, "genome")
     hp = HotPath(args.minWordSize, args.maxWordSize, device=0, cache_dir=args.tempDir, use_cache=bool(args.recalc))
+    panel = None
     try:
         genomeKmers = None
-        if os.path.isfile(genomepickle) and args.recalc:        # --recalc is store_false: giving it forces recomputation
-            log.info("Importing previously calculated genome kmers from %s", genomepickle)
-            with open(genomepickle, "rb") as fh:
-                genomeKmers = pickle.load(fh, encoding="latin1")
+        if args.donors:
+            pass                                                # (every profile's cache is score_with_donors' business)
+        elif os.path.isfile(genomepickle) and args.recalc:      # --recalc is store_false: giving it forces recomputation
+            genomeKmers = _load_pickle(genomepickle, log)
         else:
             log.info("Calculating kmers for host sequence: %s", args.hostSeq)
         try:
-            res = hp.scoreRegions(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], genomeKmers=genomeKmers)
+            if args.donors:
+                panel, planes = score_with_donors(args, hp, regions, log)
+                res = panel.plane(planes[0])
+            else:
+                res = hp.scoreRegions(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], genomeKmers=genomeKmers)
         except ValueError as err:
             logging.error("[ERROR] %s\n", err)
             return 1
-        if genomeKmers is None:
-            tmp = genomepickle + ".tmp%d" % os.getpid()
-            with open(tmp, "wb") as fh:
-                pickle.dump(hp.profileMaps(), fh, protocol=2)
-            os.replace(tmp, genomepickle)
+        if genomeKmers is None and not args.donors:
+            _dump_pickle(genomepickle, hp.profileMaps())
     finally:
         hp.close()
     with open(out_path, "w") as fh:
         fh.write(header)
         fh.writelines(region_rows(regions, res, rip, cli._fmt()))
     log.info("Scored %d regions: %s", len(regions), out_path)
+    if panel is not None:
+        donor_path = os.path.join(args.tempDir, args.donorOutfile)
+        with open(donor_path, "w") as fh:
+            fh.write("\t".join(donor_columns(labels)) + "\n")
+            fh.writelines(donor_rows(regions, panel, planes, labels, cli._fmt()))
+        log.info("Scored them against %d donor genomes: %s", len(args.donors), donor_path)
     return 0
 
 

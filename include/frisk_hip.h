@@ -275,6 +275,35 @@ int frisk_score_ranges(frisk_ctx* ctx, const int32_t* seq_index, const int64_t* 
                        uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri,
                        int64_t* nn);
 
+/* ---- the same rows against a panel of genome profiles, in one pass ---------------------------
+ * "Where did this region come from?" asked of many candidate donors at once.  A context keeps a PANEL of finalised genome-side
+ * tables on the device; frisk_score_ranges_panel counts each range once and scores it against every profile of the panel
+ * (csrc/panel_kernels.h).
+ * frisk_panel_push appends a SNAPSHOT of the context's finalised genome-side table and returns its index in *slot (nullable).
+ *   The panel holds a copy: frisk_profile_reset / _set / _finalize never change a stored slot afterwards, and the panel never
+ *   changes the context's own profile.  FRISK_E_STATE without a finalised profile, FRISK_E_ARG for a push into a full panel
+ *   (FRISK_PANEL_MAX slots); either leaves the panel as it was.  Memory: tiles of FRISK_PANEL_TILE slots, 64 bytes x 4^kmax each
+ *   (4 MB at K = 8, 1 GB at K = 12), allocated as the panel grows.
+ * frisk_panel_reset empties the panel and frees its memory (frisk_destroy does too); frisk_panel_size = P, its profiles.
+ * frisk_score_ranges_panel: status and kld hold P planes of n rows, plane p = [p*n, (p+1)*n).  Row r of plane p is bit for bit
+ *   what frisk_score_ranges returns for that range when profile p is the context's finalised profile.  gc, pi, si, cri, nn and the
+ *   status bits FRISK_ROW_KEPT and FRISK_ROW_NO_MAXMER do not depend on the profile: the value columns are written once, [n] each.
+ *   FRISK_ROW_ZERO_WEIGHT can differ between planes (a max-mer without weight in one genome and not in another).  A range that the
+ *   N rule drops has status 0 and NaN in every plane.
+ *   flags: FRISK_SCAN_RIP and FRISK_RANGES_BIG as in frisk_score_ranges.  The same row and batch checks, with the same FRISK_E_ARG
+ *   and nothing launched.  FRISK_E_STATE: an empty panel (the context's own profile is not needed).  n = 0 is FRISK_OK and touches
+ *   no output.  A streamed batch is waited for.  The scan's plan and rows, the context's profile and frisk_score_ranges are left
+ *   alone: a call of those before and after panel use returns the same bytes.
+ * frisk_last_kernel_ms(ctx, 5) = the panel kernels' time of the last call. */
+#define FRISK_PANEL_MAX  64      /* profiles a context's panel can hold */
+#define FRISK_PANEL_TILE  8      /* profiles scored per walk of a region's table */
+int     frisk_panel_reset(frisk_ctx* ctx);
+int     frisk_panel_push(frisk_ctx* ctx, int32_t* slot);
+int32_t frisk_panel_size(const frisk_ctx* ctx);
+int     frisk_score_ranges_panel(frisk_ctx* ctx, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                                 uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri,
+                                 int64_t* nn);
+
 /* Test utility (kmax <= 6): the two distributions IvomBuild returns for each candidate window of [c0,c1) (L1481-1482, L369-457) -
  * window-side and genome-side interpolated probabilities of the window's present max-mers, each normalised to sum 1 -
  * as dense vectors of 4^kmax doubles per candidate (0 for absent max-mers; all 0 for windows the reference drops). */
@@ -538,8 +567,8 @@ void* frisk_host_alloc(frisk_ctx* ctx, int64_t bytes);
 void  frisk_host_free(frisk_ctx* ctx, void* ptr);
 
 /* Timing of the most recent launches on the context's stream, measured with HIP events:
- * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels, 4 frisk_score_ranges' kernels.
- * Returns milliseconds, <0 if none. */
+ * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels, 4 frisk_score_ranges' kernels,
+ * 5 frisk_score_ranges_panel's kernels.  Returns milliseconds, <0 if none. */
 double frisk_last_kernel_ms(const frisk_ctx* ctx, int which);
 
 #ifdef __cplusplus

@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Kernel time of frisk_score_ranges_panel (csrc/panel_kernels.h) beside P calls of frisk_score_ranges (csrc/range_kernels.h), on
+the synthetic batch of tools/ranges_timing.py (16 scaffolds of 4 Mb, Engine.synth seed 7), k = 1..8, and its two short-form
+workloads:
+  grid    every candidate window of w = 5000, i = 1000 passed as ranges
+  mixed   50 000 ranges with seeded log-uniform lengths between 300 and 30 000 bases
+For P in 1, 4, 16 profiles - each the profile of a synthetic genome of its own seed, pushed to the panel -:
+  (a) panel    frisk_last_kernel_ms(ctx, 5) of one panel call
+  (b) single   the sum of frisk_last_kernel_ms(ctx, 4) over P calls of frisk_score_ranges, with profile_set between them
+Each figure is the median of --repeats measurements after one warm-up.  Prints one JSON line per workload and P, and a markdown
+table.
+
+    python tools/panel_timing.py [--repeats 3] [--device 0]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
+
+
+def median_of(fn, repeats):
+    fn()
+    return statistics.median(fn() for _ in range(repeats))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--scaffolds", type=int, default=16)
+    ap.add_argument("--scaffold-len", type=int, default=4000000)
+    ap.add_argument("--profiles", type=int, nargs="+", default=[1, 4, 16])
+    a = ap.parse_args()
+    from frisk_amd.engine import Engine
+    lens = [a.scaffold_len] * a.scaffolds
+    w, inc = 5000, 1000
+    rows = []
+    with Engine(1, 8, device=a.device) as e:
+        profs = []
+        for p in range(max(a.profiles)):                # donor p: a synthetic genome of its own
+            e.synth(lens, 100 + p, island_frac=0.02, n_frac=0.01, lower_frac=0.05)
+            e.profile_reset(); e.profile_add(); e.profile_finalize()
+            profs.append(e.profile_get())
+        e.synth(lens, 7, island_frac=0.02, n_frac=0.01, lower_frac=0.05)
+        e.profile_set(*profs[0])
+        scan = e.scan(w, inc)
+        jump = (scan.status & 4) != 0
+        grid = (scan.seq_index.copy(), np.where(jump, scan.start, scan.start - 1), scan.stop.copy())
+        rng = np.random.default_rng(11)
+        n = 50000
+        ln = np.exp(rng.uniform(np.log(300), np.log(30000), n)).astype(np.int64)
+        s = rng.integers(0, len(lens), n).astype(np.int32)
+        a0 = (rng.random(n) * (a.scaffold_len - ln)).astype(np.int64)
+        mixed = (s, a0, a0 + ln)
+        for P in a.profiles:
+            e.panel_reset()
+            for prof in profs[:P]:
+                e.profile_set(*prof)
+                e.panel_push()
+            for label, (si, st, sp) in (("grid", grid), ("mixed", mixed)):
+                def panel():
+                    e.score_ranges_panel(si, st, sp)
+                    return e.kernel_ms(5)
+
+                def single():
+                    total = 0.0
+                    for prof in profs[:P]:
+                        e.profile_set(*prof)
+                        e.score_ranges(si, st, sp)
+                        total += e.kernel_ms(4)
+                    return total
+                pa, sg = median_of(panel, a.repeats), median_of(single, a.repeats)
+                got, one = e.score_ranges_panel(si, st, sp), e.score_ranges(si, st, sp)     # (the context holds profile P - 1)
+                res = {"workload": label, "profiles": P, "ranges": int(si.size), "bases": int((sp - st).sum()),
+                       "panel_ms": round(pa, 3), "single_ms_sum": round(sg, 3), "panel_over_single": round(pa / sg, 3),
+                       "last_plane_bit_equal": bool(got.kld[P - 1].tobytes() == one.kld.tobytes() and
+                                                    got.status[P - 1].tobytes() == one.status.tobytes())}
+                print(json.dumps(res), flush=True)
+                rows.append(res)
+    print("| workload | ranges | P | (a) one panel call (ms) | (b) P single-profile calls (ms) | (a) / (b) |")
+    print("|---|---|---|---|---|---|")
+    for r in rows:
+        print("| %s | %d | %d | %.2f | %.2f | %.2f |" % (r["workload"], r["ranges"], r["profiles"], r["panel_ms"], r["single_ms_sum"],
+                                                        r["panel_over_single"]))
+
+
+if __name__ == "__main__":
+    main()
