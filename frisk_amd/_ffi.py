@@ -53,6 +53,7 @@ SYMBOLS = [
     ("frisk_seq_synth", C.c_int, [_P, _I64P, C.c_int32, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double]),
     ("frisk_seq_synth2", C.c_int, [_P, _I64P, C.c_int32, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double]),
+    ("frisk_seq_null", C.c_int, [_P, _I64P, C.c_int32, C.c_uint64, C.c_int32]),
     ("frisk_seq_read", C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P]),
     ("frisk_window_vectors", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     ("frisk_score_ranges", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),

@@ -131,7 +131,7 @@ void frisk_destroy(frisk_ctx* c) {
     for (hipStream_t s : streams) if (s) (void)hipStreamSynchronize(s);
     for (hipEvent_t e : c->pin_ev) if (e) (void)hipEventSynchronize(e);
     for (hipStream_t s : streams) if (s) (void)hipStreamDestroy(s);
-    for (hipEvent_t e : {c->ev0, c->ev1, c->evp0, c->evp1, c->staged_ev, c->slot_free_ev, c->ev_fork, c->ev_tail_kernels, c->ev_tail_done})
+    for (hipEvent_t e : {c->ev0, c->ev1, c->evp0, c->evp1, c->evn0, c->evn1, c->staged_ev, c->slot_free_ev, c->ev_fork, c->ev_tail_kernels, c->ev_tail_done})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->pin_ev) if (e) (void)hipEventDestroy(e);
     delete c;       // device and page-locked memory and the batches' piece events go with their owners (frisk_ctx.h)
@@ -153,7 +153,7 @@ void frisk_host_free(frisk_ctx* c, void* ptr) {
 }
 double frisk_last_kernel_ms(const frisk_ctx* cc, int which) {
     frisk_ctx* c = const_cast<frisk_ctx*>(cc);
-    if (!c || which < 0 || which >= 6) return -1.0;
+    if (!c || which < 0 || which >= 7) return -1.0;
     if (which == 1 && c->ms_pending[1]) {           // the profile kernel's events are read on demand: no sync in profile_add
         float ms = 0;
         if (hipEventSynchronize(c->evp1) == hipSuccess && hipEventElapsedTime(&ms, c->evp0, c->evp1) == hipSuccess) c->ms[1] = ms;

@@ -49,7 +49,7 @@ struct frisk_ctx {
     int num_cu = 256;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double ms[6] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0};    // frisk_last_kernel_ms: scan, profile_add, pack / load, window vectors, score ranges, the panel
+    double ms[7] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // frisk_last_kernel_ms: scan, profile_add, pack / load, window vectors, score ranges, the panel, null sequences
     std::string err;
 
     // sequence batches: bat[cur] is the resident one; the other slot receives the next batch while the resident one is
@@ -126,6 +126,7 @@ struct frisk_ctx {
     int32_t panel_n = 0;
     bool ms_pending[3] = {false, false, false};     // events recorded, elapsed time not read yet (frisk_last_kernel_ms)
     hipEvent_t evp0 = nullptr, evp1 = nullptr;      // profile_add kernel
+    hipEvent_t evn0 = nullptr, evn1 = nullptr;      // frisk_seq_null's kernels (created by its first call)
 
     // scan plan + outputs
     DevBuf<ScafDesc> d_desc;

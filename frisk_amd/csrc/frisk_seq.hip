@@ -1,10 +1,12 @@
 // frisk_seq.hip - the sequence half of the C ABI declared in include/frisk_hip.h: how a batch gets onto the device (ASCII, packed, the
 // 0.25 B/base form; loaded into the resident slot, or staged into the other one and committed), the FASTA entry points with the
-// window-tile shard loaders, and a batch's way back to the host.  The context is frisk_ctx.h's; its creation, phase A and the scan
+// window-tile shard loaders, the batches generated on the device (synthetic scaffolds; null sequences from the finalised profile's
+// Markov chain, null_kernels.h), and a batch's way back to the host.  The context is frisk_ctx.h's; its creation, phase A and the scan
 // are in frisk_abi.hip.  gfx950 (MI355X) only.  Build: see __graft_entry__.build_hip().
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +18,7 @@
 #include "frisk_ctx.h"
 #include "seq_kernels.h"
 #include "synth_kernel.h"
+#include "null_kernels.h"
 #include "fasta_index.h"
 #include "fasta_pack2.h"
 
@@ -719,6 +722,64 @@ int frisk_seq_synth2(frisk_ctx* c, const int64_t* lens, int32_t n_seq, uint64_t 
     rc = alloc_packed(c);
     if (rc) return rc;
     return run_pack(c);
+}
+
+// A batch of null sequences drawn from the order-`order` Markov chain of the finalised profile (null_kernels.h): laid out, packed
+// and made resident as frisk_seq_synth2 does it.  The profile is only read.
+int frisk_seq_null(frisk_ctx* c, const int64_t* lens, int32_t n_seq, uint64_t seed, int32_t order) {
+    if (!c) return FRISK_E_ARG;
+    if (n_seq < 0) return fail(c, FRISK_E_ARG, "n_seq < 0");
+    if (n_seq > 0 && !lens) return fail(c, FRISK_E_ARG, "null length table");
+    if (order < 0 || order + 1 < c->kmin || order + 1 > c->kmax)
+        return fail(c, FRISK_E_ARG, "frisk_seq_null: the chain of order r reads the counts of order r + 1, which must lie in kmin .. kmax");
+    std::vector<int64_t> meta(3 * size_t(n_seq) + 1);         // blk0 [n_seq + 1], then off and len [n_seq] each (off: filled below)
+    int64_t blocks = 0, bases = 0;
+    for (int32_t s = 0; s < n_seq; ++s) {
+        if (lens[s] < 0) return fail(c, FRISK_E_ARG, "negative scaffold length");
+        if (lens[s] >= INT64_MAX - 64 - bases) return fail(c, FRISK_E_ARG, "frisk_seq_null: the batch's length does not fit 63 bits");
+        bases += lens[s] + 1;
+        meta[size_t(s)] = blocks;
+        blocks += (lens[s] + NULL_BLOCK - 1) / NULL_BLOCK;
+    }
+    meta[size_t(n_seq)] = blocks;
+    if (!c->profile_final) return fail(c, FRISK_E_STATE, "frisk_seq_null: no finalised profile");
+    HIPC(c, hipSetDevice(c->device));
+    if (!c->evn0) {
+        HIPC(c, hipEventCreate(&c->evn0));
+        HIPC(c, hipEventCreate(&c->evn1));
+    }
+    int rc = layout_batch(c, lens, n_seq);
+    if (rc) return rc;
+    frisk_ctx::Batch& B = c->b();
+    HIPC(c, B.d_ascii.reserve(size_t(B.padded_len)));
+    HIPC(c, hipMemsetAsync(B.d_ascii.p, FRISK_PAD_BYTE, size_t(B.padded_len), c->stream));
+    const int64_t n_ctx = int64_t(1) << (2 * order);
+    DevBuf<uint64_t> d_cum;             // (both freed on every return below; run_pack waits for the kernels that read them)
+    DevBuf<int64_t> d_meta;
+    HIPC(c, d_cum.reserve(size_t(4 * n_ctx), size_t(4 * n_ctx)));
+    HIPC(c, d_meta.reserve(meta.size(), meta.size()));
+    for (int32_t s = 0; s < n_seq; ++s) {
+        meta[size_t(n_seq) + 1 + size_t(s)] = B.seq_off[size_t(s)];
+        meta[2 * size_t(n_seq) + 1 + size_t(s)] = lens[s];
+    }
+    HIPC(c, hipMemcpyAsync(d_meta.p, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipEventRecord(c->evn0, c->stream));
+    null_table_kernel<<<grid_for(n_ctx, 256, c->num_cu * 8), 256, 0, c->stream>>>(c->d_sym.p + table_offset(c->kmin, order + 1), n_ctx, d_cum.p);
+    HIPC(c, hipGetLastError());
+    if (blocks > 0) {
+        null_kernel<<<grid_for(blocks, 64, 1 << 20), 64, 0, c->stream>>>(B.d_ascii.p, d_meta.p, d_meta.p + n_seq + 1, d_meta.p + 2 * size_t(n_seq) + 1,
+                                                                        n_seq, d_cum.p, uint32_t(n_ctx - 1), seed);
+        HIPC(c, hipGetLastError());
+    }
+    HIPC(c, hipEventRecord(c->evn1, c->stream));
+    rc = alloc_packed(c);
+    if (rc) return rc;
+    rc = run_pack(c);
+    if (rc) return rc;
+    float ms = 0;
+    HIPC(c, hipEventElapsedTime(&ms, c->evn0, c->evn1));
+    c->ms[6] = ms;
+    return FRISK_OK;
 }
 
 int frisk_seq_read(frisk_ctx* c, int32_t s, int64_t offset, int64_t n, uint8_t* out) {

@@ -351,6 +351,15 @@ class Engine:
         self.n_seq = len(lens)
         self.seq_lens = lens
 
+    def null_batch(self, lens, seed, order):
+        """frisk_seq_null: make resident a batch of len(lens) sequences drawn on the device from the order-`order` Markov chain of
+        the finalised profile (nullmodel.generate gives the same bytes on the host)."""
+        lens = [int(x) for x in lens]
+        arr = (C.c_int64 * max(len(lens), 1))(*lens)
+        self._check(self._lib.frisk_seq_null(self._ctx, arr, len(lens), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(order)))
+        self.n_seq = len(lens)
+        self.seq_lens = lens
+
     def read_seq(self, index, offset=0, n=None):
         if n is None:
             n = self.seq_lens[index] - offset

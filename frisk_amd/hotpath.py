@@ -347,6 +347,52 @@ class HotPath:
         seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
         return e.score_ranges_panel(seq, start, stop, rip=rip), planes[0], planes[1:]
 
+    NULL_CHUNK = 1 << 18        # ranges per score_ranges call of nullScores (a row's bits do not depend on the call it is in)
+
+    def nullScores(self, args, lengths, draws, seed, mode, order=None):
+        """(kld, valid), both of shape (len(lengths), draws): the KLD of `draws` null sequences at each of the distinct `lengths`,
+        scored by Engine.score_ranges against the context's finalised profile, and whether the draw's row would carry note `.`
+        (kept, with weight, with a max-mer).
+          mode "markov": one Engine.null_batch([max(lengths)] * draws, seed, order) - sequences of the order-`order` chain of the
+                         profile (default kMax - 1), generated on the device; draw j at length L is the prefix (j, 0, L), so the
+                         prefixes of a draw are nested.  The resident batch is replaced.
+          mode "host"  : args.hostSeq is made resident (nothing happens when it is already) and draw j at length L is the slice
+                         nullmodel.host_draws picks; no draw is valid at a length no scaffold reaches."""
+        from . import nullmodel
+        lengths = [int(n) for n in lengths]
+        if len(set(lengths)) != len(lengths) or min(lengths, default=1) < 1:
+            raise ValueError("nullScores: the lengths must be distinct and positive")
+        draws = int(draws)
+        kld = np.full((len(lengths), draws), np.nan)
+        valid = np.zeros((len(lengths), draws), dtype=bool)
+        if not lengths or draws < 1:
+            return kld, valid
+        cell, seq, start, stop = [], [], [], []
+        if mode == "markov":
+            order = self.kMax - 1 if order is None else int(order)
+            self.engine.null_batch([max(lengths)] * draws, seed, order)
+            self._resident, self.names = None, [""] * draws
+            cell = np.arange(len(lengths) * draws)
+            seq, start, stop = np.tile(np.arange(draws), len(lengths)), np.zeros(cell.size), np.repeat(lengths, draws)
+        elif mode == "host":
+            self._load(args.hostSeq)
+            for i, n in enumerate(lengths):
+                s, a = nullmodel.host_draw_arrays(self.engine.seq_lens, n, draws, seed)
+                cell.append(i * draws + np.arange(s.size)); seq.append(s); start.append(a); stop.append(a + n)
+            cell, seq, start, stop = [np.concatenate(x) for x in (cell, seq, start, stop)]
+        else:
+            raise ValueError("nullScores: mode is 'markov' or 'host'")
+        cell = np.asarray(cell, np.int64)
+        seq, start, stop = np.asarray(seq, np.int32), np.asarray(start, np.int64), np.asarray(stop, np.int64)
+        bad = _ffi.ROW_ZERO_WEIGHT | _ffi.ROW_NO_MAXMER
+        for at in range(0, cell.size, self.NULL_CHUNK):
+            cut = slice(at, at + self.NULL_CHUNK)
+            res = self.engine.score_ranges(seq[cut], start[cut], stop[cut])
+            ok = ((res.status & _ffi.ROW_KEPT) != 0) & ((res.status & bad) == 0)
+            kld.reshape(-1)[cell[cut]] = np.where(ok, res.kld, np.nan)
+            valid.reshape(-1)[cell[cut]] = ok
+        return kld, valid
+
     def scanGenome(self, args, querySeq, debug=False):
         """The same as a list of row tuples (tests, small jobs): (rows, result)."""
         table, res = self.scanTable(args, querySeq, debug=debug)

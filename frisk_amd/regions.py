@@ -28,6 +28,25 @@ byte for byte the file of the same run without --donors.  --donorOutfile (in --t
 label> <donor labels, command-line order> nearest margin`, one row per input record; a cell is the KLD as -O would print it under
 that profile (the int 0 for noMaxmer, nan for unresolved / ZeroDivisionError), `nearest` the label of the smallest non-NaN cell
 (the first in column order wins a tie; `.` for none), `margin` the second smallest minus the smallest (`.` with fewer than two).
+
+    python -m frisk_amd.regions -H host.fa --gff genes.gff3 --null markov --nullDraws 200      is this KLD unusual at this length?
+
+The KLD of a slice depends on its length as much as on its content, so windowKLD cannot be read across regions.  --null scores,
+for every distinct region length, --nullDraws null sequences of that length against the same profile (HotPath.nullScores) and
+places each region in the null distribution of its own length:
+    --null markov   sequences drawn on the device from the Markov chain of the host's own k-mer profile (frisk_seq_null,
+                    nullmodel.py; order --nullOrder r, default kmax - 1, kmin <= r + 1 <= kmax): what sampling noise alone does at
+                    this length under the host's k-mer model
+    --null host     slices of the host itself at seeded positions (nullmodel.host_draws): what this genome looks like at this
+                    length, heterogeneity included
+--seed S (default 0) fixes the draws.  -O is byte for byte the file of the same run without --null.  --nullOutfile (in --tempDir,
+default region_null_scores.tsv): header `name start stop length id windowKLD nullN nullMean nullSD excess z p note`, one row per
+input record in input order, windowKLD and note as in -O.  nullN = the null draws whose own note is `.`; nullMean, nullSD (n - 1 in
+the divisor) their mean and standard deviation; excess = windowKLD - nullMean; z = excess / nullSD; p = (1 + #{null >= windowKLD})
+/ (1 + nullN) - ties count against the region.  A field that does not exist is `.`: all six for a record whose note is not `.` or
+without a valid draw, nullSD and z with a single draw, z with nullSD 0.
+The null is matched on the region's plain length, not on its count of valid bases.  Host draws may overlap the region itself, as
+the scanner's percentile includes the window it judges.  --null does not go with --donors.
 """
 import argparse
 import gzip
@@ -61,6 +80,13 @@ def build_parser():
                    "each of them too, in the same pass, and name the nearest profile")
     p.add_argument("--donorOutfile", type=str, default="region_donor_scores.tsv", help="with --donors: the per-donor KLD table, "
                    "written in --tempDir")
+    p.add_argument("--null", type=str, choices=["markov", "host"], default=None, help="place every region in a null distribution of "
+                   "its own length: sequences drawn from the host profile's Markov chain, or slices of the host")
+    p.add_argument("--nullDraws", type=int, default=100, help="with --null: null sequences per distinct region length")
+    p.add_argument("--nullOrder", type=int, default=None, help="with --null markov: order r of the chain (default: kmax - 1)")
+    p.add_argument("--seed", type=int, default=0, help="with --null: seed of the draws")
+    p.add_argument("--nullOutfile", type=str, default="region_null_scores.tsv", help="with --null: the calibrated table, written in "
+                   "--tempDir")
     return p
 
 
@@ -155,6 +181,42 @@ def donor_rows(regions, panel, planes, labels, fmt):
                         ["." if near is None else labels[near], "." if margin is None else fmt(margin)]) + "\n"
 
 
+NULL_COLUMNS = ["name", "start", "stop", "length", "id", "windowKLD", "nullN", "nullMean", "nullSD", "excess", "z", "p", "note"]
+
+
+def null_problem(args, regions):
+    """Why this command line cannot have its --null (a message), or None: checked before any device work."""
+    if args.donors:
+        return "--null does not go with --donors"
+    if args.nullDraws < 1:
+        return "--nullDraws must be at least 1"
+    if args.nullOrder is not None:
+        if args.null == "host":
+            return "--nullOrder goes with --null markov"
+        if not args.minWordSize <= args.nullOrder + 1 <= args.maxWordSize:
+            return "--nullOrder r needs the k-mers of length r + 1: %d <= r + 1 <= %d" % (args.minWordSize, args.maxWordSize)
+    if args.null == "markov" and regions:
+        from . import nullmodel
+        longest = max(b - a for _, a, b, _ in regions)
+        if not nullmodel.batch_fits(args.nullDraws, longest):
+            return "--nullDraws %d sequences of %d bases (the longest region) are more than one batch can hold" % (args.nullDraws, longest)
+    return None
+
+
+def null_rows(regions, res, lengths, kld, valid, fmt):
+    """One line per region of the --null table.  `lengths`: the distinct lengths that were drawn; kld, valid: HotPath.nullScores'."""
+    from . import nullmodel
+    row_of = {n: i for i, n in enumerate(lengths)}
+    for r, (name, a, b, ident) in enumerate(regions):
+        note, cell = region_cell(res.status[r], res.kld[r])
+        fields = [None] * 6
+        if note == ".":
+            i = row_of[b - a]
+            fields = nullmodel.stats(cell, kld[i][valid[i]])
+        yield "\t".join([fmt(v) for v in [name, a + 1, b, b - a]] + [ident, fmt(cell)] +
+                        ["." if v is None else fmt(v) for v in fields] + [note]) + "\n"
+
+
 def _load_pickle(path, log):
     log.info("Importing previously calculated genome kmers from %s", path)
     with open(path, "rb") as fh:
@@ -211,6 +273,9 @@ def main(argv=None):
     except (OSError, ValueError) as err:
         logging.error("[ERROR] %s\n", err)
         return 1
+    if args.null and null_problem(args, regions):
+        logging.error("[ERROR] %s\n", null_problem(args, regions))
+        return 1
     rip = bool(args.RIP) and args.minWordSize <= 2
     if not os.path.isdir(os.path.abspath(args.tempDir)):
         os.makedirs(os.path.abspath(args.tempDir))
@@ -222,6 +287,9 @@ def main(argv=None):
         if args.donors:
             with open(os.path.join(args.tempDir, args.donorOutfile), "w") as fh:
                 fh.write("\t".join(donor_columns(labels)) + "\n")
+        if args.null:
+            with open(os.path.join(args.tempDir, args.nullOutfile), "w") as fh:
+                fh.write("\t".join(NULL_COLUMNS) + "\n")
         log.info("No regions in %s: wrote the header to %s", args.bed or args.gff, out_path)
         return 0
 
@@ -248,12 +316,21 @@ def main(argv=None):
             return 1
         if genomeKmers is None and not args.donors:
             _dump_pickle(genomepickle, hp.profileMaps())
+        if args.null:       # (after the regions: the markov null replaces the resident batch)
+            lengths = sorted({b - a for r, (_, a, b, _) in enumerate(regions) if region_cell(res.status[r], res.kld[r])[0] == "."})
+            null_kld, null_valid = hp.nullScores(args, lengths, args.nullDraws, args.seed, args.null, order=args.nullOrder)
     finally:
         hp.close()
     with open(out_path, "w") as fh:
         fh.write(header)
         fh.writelines(region_rows(regions, res, rip, cli._fmt()))
     log.info("Scored %d regions: %s", len(regions), out_path)
+    if args.null:
+        null_path = os.path.join(args.tempDir, args.nullOutfile)
+        with open(null_path, "w") as fh:
+            fh.write("\t".join(NULL_COLUMNS) + "\n")
+            fh.writelines(null_rows(regions, res, lengths, null_kld, null_valid, cli._fmt()))
+        log.info("Placed them in %s nulls of %d draws per length (%d lengths): %s", args.null, args.nullDraws, len(lengths), null_path)
     if panel is not None:
         donor_path = os.path.join(args.tempDir, args.donorOutfile)
         with open(donor_path, "w") as fh:

@@ -174,6 +174,17 @@ int frisk_seq_synth(frisk_ctx* ctx, const int64_t* lens, int32_t n_seq, uint64_t
 int frisk_seq_synth2(frisk_ctx* ctx, const int64_t* lens, int32_t n_seq, uint64_t seed, double island_frac, double n_frac,
                      double lower_frac, double repeats_per_kb, double period_mix, double sat_frac);
 
+/* Null sequences: fill the resident batch with n_seq sequences drawn ON the device from the order-`order` Markov chain of the
+ * context's FINALISED profile - context c in [0, 4^order) continues with base b in proportion to the symmetric count of the
+ * (order + 1)-mer 4c + b (csrc/null_kernels.h; frisk_amd/nullmodel.py is the specification and reproduces the bytes on the host).
+ * Uppercase A/T/G/C only.  Every base is a pure function of (profile, order, seed, sequence index, position): a sequence is a
+ * prefix of any longer one of the same index.  The batch is laid out, packed and made resident as frisk_seq_synth2's, names "";
+ * the scan plan is invalidated as by any new batch; the profile, the panel and every row buffer are left alone.
+ * FRISK_E_ARG, with nothing launched and the resident batch as it was: order < 0, order + 1 outside kmin .. kmax, a null length
+ * table, a negative length, n_seq < 0.  FRISK_E_STATE: no finalised profile.
+ * frisk_last_kernel_ms(ctx, 6) = the generator kernels' time (table + draw) of the last call. */
+int frisk_seq_null(frisk_ctx* ctx, const int64_t* lens, int32_t n_seq, uint64_t seed, int32_t order);
+
 /* Copy bases [offset, offset+n) of resident scaffold seq_index back as ASCII (canonical letters:
  * A/T/G/C, a/t/g/c, N for every non-ACGT letter) - test / bench-sampling utility. */
 int frisk_seq_read(frisk_ctx* ctx, int32_t seq_index, int64_t offset, int64_t n, uint8_t* out);
@@ -568,7 +579,7 @@ void  frisk_host_free(frisk_ctx* ctx, void* ptr);
 
 /* Timing of the most recent launches on the context's stream, measured with HIP events:
  * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels, 4 frisk_score_ranges' kernels,
- * 5 frisk_score_ranges_panel's kernels.  Returns milliseconds, <0 if none. */
+ * 5 frisk_score_ranges_panel's kernels, 6 frisk_seq_null's generator kernels.  Returns milliseconds, <0 if none. */
 double frisk_last_kernel_ms(const frisk_ctx* ctx, int which);
 
 #ifdef __cplusplus
