@@ -15,6 +15,7 @@ ROW_KEPT, ROW_ZERO_WEIGHT, ROW_JUMPBACK, ROW_NO_MAXMER = 1, 2, 4, 8
 KVEC_MAX_K, KVEC_THREADS, KVEC_GRID_CAP, KVEC_EMPTY_ORDER, KVEC_ORDER_SHIFT = 7, 256, 2048, 1, 8      # frisk_window_vectors
 RANGES_BIG = 0x10000                                                                                 # frisk_score_ranges
 PANEL_MAX, PANEL_TILE = 64, 8                                                                        # frisk_score_ranges_panel
+EXPLAIN_MAX, EXPLAIN_NONE = 64, 0xFFFFFFFF                                                           # frisk_explain_ranges
 
 # every symbol include/frisk_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -61,6 +62,8 @@ SYMBOLS = [
     ("frisk_panel_push", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("frisk_panel_size", C.c_int32, [_P]),
     ("frisk_score_ranges_panel", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    ("frisk_explain_ranges", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint32, C.c_int32, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, _P, _P, _P, _P, _P]),
     ("frisk_profile_reset", C.c_int, [_P]),
     ("frisk_profile_add", C.c_int, [_P, C.c_int, C.c_int64, C.c_int64]),
     ("frisk_seq_padded_len", C.c_int64, [_P]),

@@ -4,7 +4,8 @@
 // queues both launches on the context's stream; a range the short form cannot hold reaches the long form through a device list,
 // without a host round trip.  The context is frisk_ctx.h's; the scan's plan and row buffers are not touched.  gfx950 (MI355X)
 // only.  frisk_score_ranges_panel and the panel's three calls are here too: the same host path with panel_kernels.h's kernels,
-// every profile of the context's panel in one pass.  Build: see __graft_entry__.build_hip().
+// every profile of the context's panel in one pass.  frisk_explain_ranges too: the same host path with explain_kernels.h's kernels,
+// their scratch and the six arrays of the largest KLD terms.  Build: see __graft_entry__.build_hip().
 #include <algorithm>
 #include <numeric>
 #include <string>
@@ -13,6 +14,7 @@
 #include "frisk_ctx.h"
 #include "range_kernels.h"
 #include "panel_kernels.h"
+#include "explain_kernels.h"
 
 namespace {
 
@@ -34,12 +36,31 @@ hipError_t launch_panel_short(const PanelParams& Q, int grid, size_t lds, hipStr
     return hipGetLastError();
 }
 
-// both entry points: `panel` = score against the context's panel (np planes of status and kld) instead of its own profile
-int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
-                 uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri, int64_t* nn) {
+template <bool K8>
+hipError_t launch_explain_short(const ExplainParams& E, int grid, size_t lds, hipStream_t st) {
+    auto kern = explain_short_kernel<K8>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+    kern<<<grid, FRISK_RANGE_NT, lds, st>>>(E);
+    return hipGetLastError();
+}
+
+// frisk_explain_ranges' own arguments (host arrays)
+struct ExplainOut {
+    int32_t top_n;
+    int32_t* n_present;
+    uint32_t *code, *count;
+    double *pw, *pg, *term;
+};
+
+// the three entry points: `panel` = score against the context's panel (np planes of status and kld) instead of its own profile;
+// `ex` = the explain kernels and their outputs (never with `panel`)
+int score_ranges(frisk_ctx* c, const bool panel, const ExplainOut* ex, const int32_t* seq_index, const int64_t* start, const int64_t* stop,
+                 int64_t n, uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri, int64_t* nn) {
     if (!c) return FRISK_E_ARG;
-    const std::string who = panel ? "frisk_score_ranges_panel" : "frisk_score_ranges";
+    const std::string who = ex ? "frisk_explain_ranges" : panel ? "frisk_score_ranges_panel" : "frisk_score_ranges";
     if (n < 0) return fail(c, FRISK_E_ARG, who + ": n < 0");
+    if (ex && (ex->top_n < 1 || ex->top_n > FRISK_EXPLAIN_MAX)) return fail(c, FRISK_E_ARG, who + ": top_n outside 1 .. FRISK_EXPLAIN_MAX");
     const frisk_ctx::Batch& B = c->b();
     if (!B.have_seq) return fail(c, FRISK_E_ARG, who + ": no resident sequence batch");
     if (B.tiled) return fail(c, FRISK_E_ARG, who + ": the resident batch holds tiles, not whole scaffolds");
@@ -49,6 +70,7 @@ int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const
     if (n == 0) return FRISK_OK;
     if (!seq_index || !start || !stop || !status || !kld || !gc || !nn || (rip && (!pi || !si || !cri)))
         return fail(c, FRISK_E_ARG, who + ": null array");
+    if (ex && (!ex->n_present || !ex->code || !ex->count || !ex->pw || !ex->pg || !ex->term)) return fail(c, FRISK_E_ARG, who + ": null array");
     std::vector<int64_t> ranges(size_t(n) * 2);
     for (int64_t r = 0; r < n; ++r) {
         const int32_t s = seq_index[r];
@@ -71,6 +93,11 @@ int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const
     for (int64_t r : order) (all_long || ranges[size_t(2 * r + 1)] > FRISK_RANGE_SHORT_MAX ? long_rows : short_rows).push_back(r);
     const int64_t n_short = int64_t(short_rows.size()), n_long = int64_t(long_rows.size());
     const int64_t long_cap = n_long + (k8 ? n_short : 0);       // every short row of kmax = 8 may be handed over
+    // explain: entries of a workgroup's slice per form - a range of len bases has at most min(len, 4^kmax) distinct max-mers (even:
+    // the 32-bit codes lie behind the terms)
+    auto slice_cap = [&](int64_t longest) { return (std::min<int64_t>(longest, int64_t(1) << (2 * c->kmax)) + 1) / 2 * 2; };
+    const int64_t len_short = n_short ? ranges[size_t(2 * short_rows[0] + 1)] : 0, len_long = n_long ? ranges[size_t(2 * long_rows[0] + 1)] : 0;
+    const int64_t cap_short = slice_cap(len_short), cap_long = slice_cap(std::max(len_long, k8 ? len_short : 0));
 
     HIPC(c, hipSetDevice(c->device));
     if (int rc = settle_stream(c)) return rc;
@@ -80,7 +107,9 @@ int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const
     DevBuf<int64_t> d_ranges, d_short, d_long, d_nn;            // (freed on every return below)
     DevBuf<unsigned int> d_cnt;                                 // [0]: rows handed over to the long form
     DevBuf<uint32_t> d_status;
-    DevBuf<double> d_val;
+    DevBuf<double> d_val, d_stage, d_top;                       // explain: the slices of both forms; pw, pg, term
+    DevBuf<uint32_t> d_topu;                                    // ... code, count
+    DevBuf<int32_t> d_npres;
     HIPC(c, d_ranges.reserve(2 * N, 2 * N));
     HIPC(c, d_short.reserve(size_t(std::max<int64_t>(n_short, 1)), size_t(std::max<int64_t>(n_short, 1))));
     HIPC(c, d_long.reserve(size_t(std::max<int64_t>(long_cap, 1)), size_t(std::max<int64_t>(long_cap, 1))));
@@ -106,33 +135,59 @@ int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const
         P.ig = nullptr;
     }
 
+    ExplainParams E = ExplainParams();
+    const size_t NS = ex ? N * size_t(ex->top_n) : 0;
+    if (ex) {
+        HIPC(c, d_top.reserve(3 * NS, 3 * NS));
+        HIPC(c, d_topu.reserve(2 * NS, 2 * NS));
+        HIPC(c, d_npres.reserve(N, N));
+        E.top_n = ex->top_n; E.n_present = d_npres.p;
+        E.code = d_topu.p; E.count = d_topu.p + NS;
+        E.pw = d_top.p; E.pg = d_top.p + NS; E.term = d_top.p + 2 * NS;
+    }
+
     // the long form's scratch: one slice of 32-bit tables per workgroup (350 KB at 1..8, 89 MB at K = 12), as many workgroups as
     // the device can spare scratch for.  The short rows of kmax = 8 may all be handed over, but hardly any is: they add a few
     // workgroups to the grid, not one each (the grid-stride loop takes whatever the list holds in the end).
     const int64_t stride = (c->nprof + 3) / 4 * 4;
     int64_t want = std::min<int64_t>(n_long + std::min<int64_t>(long_cap - n_long, FRISK_RANGE_HANDOVER_WGS), c->num_cu);
+    const size_t slice_long = ex ? size_t(cap_long) * 12 : 0;   // explain: bytes of a long-form workgroup's slice
     if (long_cap) {
-        if (size_t(want) * size_t(stride) > c->d_big.cap) {
+        if (size_t(want) * size_t(stride) > c->d_big.cap || slice_long) {
             size_t free_b = 0, total_b = 0;
             HIPC(c, hipMemGetInfo(&free_b, &total_b));
-            const int64_t fit = int64_t((free_b / 2 + c->d_big.cap * 4) / (size_t(stride) * 4));
+            const int64_t fit = int64_t((free_b / 2 + c->d_big.cap * 4) / (size_t(stride) * 4 + slice_long));
             want = std::max<int64_t>(1, std::min(want, fit));
         }
         HIPC(c, c->d_big.reserve(size_t(want) * size_t(stride)));
         HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(want) * size_t(stride) * 4, c->stream));
     }
 
+    const RangeLds L = range_lds(c->kmin, c->kmax);
+    // kmax = 8: the order-8 table leaves room for one workgroup per CU; below, three (43.7 KB at 1..7).  The panel kernel holds
+    // a tile's 24 ExactSums in registers (196 VGPRs: two waves per SIMD, i.e. one workgroup per CU at any kmax)
+    const int per_cu = (k8 || panel) ? 1 : 3;
+    const int grid = int(std::min<int64_t>(n_short, int64_t(c->num_cu) * per_cu));
+    if (ex) {           // the short form's slices, then the long form's
+        const size_t words_short = n_short ? size_t(grid) * size_t(cap_short) * 3 / 2 : 0;
+        const size_t words_long = long_cap ? size_t(want) * size_t(cap_long) * 3 / 2 : 0;
+        HIPC(c, d_stage.reserve(words_short + words_long + 1, words_short + words_long + 1));
+        E.stage = d_stage.p;
+    }
+
     HIPC(c, hipEventRecord(c->ev0, c->stream));
+    if (ex) {
+        explain_fill_kernel<<<grid_for(int64_t(NS), 256, 4096), 256, 0, c->stream>>>(E, n);
+        HIPC(c, hipGetLastError());
+    }
     if (n_short) {
         RangeParams S = P;
         S.list = d_short.p; S.n_list = n_short; S.more = nullptr;
         S.out_list = d_long.p + n_long; S.out_count = d_cnt.p;
-        const RangeLds L = range_lds(c->kmin, c->kmax);
-        // kmax = 8: the order-8 table leaves room for one workgroup per CU; below, three (43.7 KB at 1..7).  The panel kernel holds
-        // a tile's 24 ExactSums in registers (196 VGPRs: two waves per SIMD, i.e. one workgroup per CU at any kmax)
-        const int per_cu = (k8 || panel) ? 1 : 3;
-        const int grid = int(std::min<int64_t>(n_short, int64_t(c->num_cu) * per_cu));
-        if (panel) {
+        if (ex) {
+            E.R = S; E.cap = cap_short;
+            HIPC(c, k8 ? launch_explain_short<true>(E, grid, L.total, c->stream) : launch_explain_short<false>(E, grid, L.total, c->stream));
+        } else if (panel) {
             Q.R = S;
             const size_t lds = panel_lds_total(c->kmin, c->kmax);
             HIPC(c, k8 ? launch_panel_short<true>(Q, grid, lds, c->stream) : launch_panel_short<false>(Q, grid, lds, c->stream));
@@ -143,7 +198,11 @@ int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const
     if (long_cap) {     // (kmax = 8 without a long row: a few workgroups that find the hand-over list empty nearly always)
         RangeParams G = P;
         G.list = d_long.p; G.n_list = n_long; G.more = (k8 && n_short) ? d_cnt.p : nullptr;
-        if (panel) {
+        if (ex) {
+            E.R = G; E.cap = cap_long;
+            E.stage = d_stage.p + (n_short ? size_t(grid) * size_t(cap_short) * 3 / 2 : 0);
+            explain_long_kernel<<<int(want), FRISK_RANGE_BIG_NT, 0, c->stream>>>(E, c->d_big.p, stride);
+        } else if (panel) {
             Q.R = G;
             panel_long_kernel<<<int(want), FRISK_RANGE_BIG_NT, 0, c->stream>>>(Q, c->d_big.p, stride);
         } else {
@@ -161,10 +220,18 @@ int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const
         HIPC(c, hipMemcpyAsync(si, P.si, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPC(c, hipMemcpyAsync(cri, P.cri, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
+    if (ex) {
+        HIPC(c, hipMemcpyAsync(ex->n_present, d_npres.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(ex->code, E.code, NS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(ex->count, E.count, NS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(ex->pw, E.pw, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(ex->pg, E.pg, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(ex->term, E.term, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
     HIPC(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->ms[panel ? 5 : 4] = ms;
+    c->ms[ex ? 7 : panel ? 5 : 4] = ms;
     return FRISK_OK;
 }
 
@@ -173,13 +240,21 @@ int score_ranges(frisk_ctx* c, const bool panel, const int32_t* seq_index, const
 extern "C" int frisk_score_ranges(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
                                   uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri,
                                   int64_t* nn) {
-    return score_ranges(c, false, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
+    return score_ranges(c, false, nullptr, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
+}
+
+extern "C" int frisk_explain_ranges(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                                    uint32_t flags, int32_t top_n, uint32_t* status, double* kld, double* gc, double* pi, double* si,
+                                    double* cri, int64_t* nn, int32_t* n_present, uint32_t* code, uint32_t* count, double* pw,
+                                    double* pg, double* term) {
+    const ExplainOut ex = {top_n, n_present, code, count, pw, pg, term};
+    return score_ranges(c, false, &ex, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
 }
 
 extern "C" int frisk_score_ranges_panel(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
                                         uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si,
                                         double* cri, int64_t* nn) {
-    return score_ranges(c, true, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
+    return score_ranges(c, true, nullptr, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
 }
 
 extern "C" int32_t frisk_panel_size(const frisk_ctx* c) { return c ? c->panel_n : 0; }

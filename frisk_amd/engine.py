@@ -613,6 +613,32 @@ class Engine:
                                                        _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn)))
         return r
 
+    def explain_ranges(self, seq_index, start, stop, top_n, rip=False, big=False):
+        """frisk_explain_ranges: score_ranges' columns - the same bits - plus the top_n largest summands of each range's KLD
+        (csrc/explain_kernels.h).  The ScanResult also carries n_present (n,), the distinct max-mers of a kept range, and code,
+        count, pw, pg, term of shape (n, top_n): column j is rank j, rank 0 the largest term, equal terms by ascending code.  A slot
+        is filled only for a range whose status is exactly ROW_KEPT and for j < min(top_n, n_present); every other slot holds code
+        EXPLAIN_NONE, count 0 and NaN.  top_n: 1 .. EXPLAIN_MAX."""
+        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
+        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
+        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        n = int(seq_index.size)
+        if start.size != n or stop.size != n:
+            raise ValueError("seq_index, start and stop must have one entry per range")
+        top_n = int(top_n)
+        width = min(max(top_n, 1), _ffi.EXPLAIN_MAX)       # (a refused top_n: the library says so, nothing is written)
+        new = lambda dt: np.zeros(n, dt)                                   # noqa: E731
+        top = lambda dt: np.zeros((n, width), dt)                          # noqa: E731
+        r = ScanResult(seq_index=seq_index, start=start, stop=stop, status=new(np.uint32), kld=new(np.float64), gc=new(np.float64),
+                       pi=new(np.float64) if rip else None, si=new(np.float64) if rip else None,
+                       cri=new(np.float64) if rip else None, nn=new(np.int64), n_present=new(np.int32), code=top(np.uint32),
+                       count=top(np.uint32), pw=top(np.float64), pg=top(np.float64), term=top(np.float64))
+        flags = (_ffi.SCAN_RIP if rip else 0) | (_ffi.RANGES_BIG if big else 0)
+        self._check(self._lib.frisk_explain_ranges(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, flags, top_n, _ptr(r.status),
+                                                   _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn),
+                                                   _ptr(r.n_present), _ptr(r.code), _ptr(r.count), _ptr(r.pw), _ptr(r.pg), _ptr(r.term)))
+        return r
+
     def scan_stat(self):
         """(counter width of the bulk launch, windows handed 4->8 bit, windows handed on to 16 bit, row segments) of the last scan."""
         return tuple(int(self._lib.frisk_last_scan_stat(self._ctx, i)) for i in range(4))

@@ -299,6 +299,17 @@ class HotPath:
         seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
         return self.engine.score_ranges(seq, start, stop, rip=rip)
 
+    def explainRegions(self, args, querySeq, regions, top_n, genomeKmers=None):
+        """scoreRegions, and for every region the top_n max-mers with the largest summands of its KLD (Engine.explain_ranges: one
+        device call, the score columns bit for bit scoreRegions').  Returns the ScanResult with n_present, code, count, pw, pg and
+        term beside the score columns."""
+        if genomeKmers is not None:
+            self.setGenomeProfile(genomeKmers)
+        else:
+            self.genomeProfileArrays(args)
+        seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
+        return self.engine.explain_ranges(seq, start, stop, top_n, rip=rip)
+
     def _regionArrays(self, args, querySeq, regions):
         """scoreRegions / scoreRegionsPanel: make `querySeq` resident and turn the records into (seq_index, start, stop, rip)."""
         self._load(querySeq)

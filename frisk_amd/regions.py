@@ -47,6 +47,20 @@ the divisor) their mean and standard deviation; excess = windowKLD - nullMean; z
 without a valid draw, nullSD and z with a single draw, z with nullSD 0.
 The null is matched on the region's plain length, not on its count of valid bases.  Host draws may overlap the region itself, as
 the scanner's percentile includes the window it judges.  --null does not go with --donors.
+
+    python -m frisk_amd.regions -H host.fa --bed anomalies.bed --topKmers 20                   which k-mers drive this KLD?
+
+A region's KLD is a sum over its present max-mers (the words of --maxWordSize letters it holds) of term = pw * log2(pw / pg), pw
+and pg the region's and the host's interpolated probabilities of the word.  --topKmers N (1..64, off by default) lists each region's
+N largest terms.  The regions are then scored by the one call that also keeps the terms (HotPath.explainRegions ->
+frisk_explain_ranges, csrc/explain_kernels.h): -O is byte for byte the file of the same run without --topKmers.  --kmerOutfile (in
+--tempDir, default region_kmers.tsv): header `name start stop id rank kmer count pw pg term share`; a region whose note is `.` gets
+min(N, its distinct max-mers) lines, regions in input order, rank from 1 (the largest term; equal terms in the tables' digit order
+A, T, G, C); a region with any other note gets none.  kmer = the word, count = its occurrences in the region (overlapping, the
+region upper-cased), share = term / windowKLD (`.` when the KLD is 0), floats as in -O.  The term of an over-represented word is
+positive, that of a present but under-represented word negative - a KLD is what is left after they cancel, so shares can exceed 1
+and the tail of a short region's list, which holds every word it has, is negative.  --topKmers goes with --null (the terms are
+taken before the null batch replaces the resident one) and not with --donors.
 """
 import argparse
 import gzip
@@ -87,6 +101,10 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0, help="with --null: seed of the draws")
     p.add_argument("--nullOutfile", type=str, default="region_null_scores.tsv", help="with --null: the calibrated table, written in "
                    "--tempDir")
+    p.add_argument("--topKmers", type=int, default=None, help="list the N (1..64) k-mers of --maxWordSize letters with the largest "
+                   "terms of each region's KLD")
+    p.add_argument("--kmerOutfile", type=str, default="region_kmers.tsv", help="with --topKmers: the per-region k-mer table, written "
+                   "in --tempDir")
     return p
 
 
@@ -217,6 +235,37 @@ def null_rows(regions, res, lengths, kld, valid, fmt):
                         ["." if v is None else fmt(v) for v in fields] + [note]) + "\n"
 
 
+KMER_COLUMNS = ["name", "start", "stop", "id", "rank", "kmer", "count", "pw", "pg", "term", "share"]
+
+
+def kmers_problem(args):
+    """Why this command line cannot have its --topKmers (a message), or None: checked before any device work."""
+    if not 1 <= args.topKmers <= _ffi.EXPLAIN_MAX:
+        return "--topKmers takes 1..%d" % _ffi.EXPLAIN_MAX
+    if args.donors:
+        return "--topKmers does not go with --donors"
+    return None
+
+
+def kmer_text(code, k):
+    """The k letters of a table code: digits A, T, G, C = 0..3, first base most significant."""
+    code = int(code)
+    return "".join("ATGC"[(code >> (2 * (k - 1 - i))) & 3] for i in range(k))
+
+
+def kmer_rows(regions, res, k, fmt):
+    """The lines of the --topKmers table: for each region whose note is `.`, its filled slots in rank order."""
+    for r, (name, a, b, ident) in enumerate(regions):
+        note, kld = region_cell(res.status[r], res.kld[r])
+        if note != ".":
+            continue
+        for j in range(min(int(res.n_present[r]), res.code.shape[1])):
+            term = float(res.term[r][j])
+            share = "." if kld == 0 else fmt(term / kld)
+            yield "\t".join([fmt(v) for v in [name, a + 1, b]] + [ident, fmt(j + 1), kmer_text(res.code[r][j], k),
+                             fmt(int(res.count[r][j])), fmt(float(res.pw[r][j])), fmt(float(res.pg[r][j])), fmt(term), share]) + "\n"
+
+
 def _load_pickle(path, log):
     log.info("Importing previously calculated genome kmers from %s", path)
     with open(path, "rb") as fh:
@@ -263,6 +312,9 @@ def main(argv=None):
     if args.gffFeatures and not args.gff:
         logging.error("[ERROR] --gffFeatures goes with --gff\n")
         return 1
+    if args.topKmers is not None and kmers_problem(args):
+        logging.error("[ERROR] %s\n", kmers_problem(args))
+        return 1
     labels = [os.path.basename(p) for p in [args.hostSeq] + list(args.donors or [])]
     if len(set(labels)) != len(labels):
         logging.error("[ERROR] the host and the donors (--donors) must differ in their file names, which label the columns: %s\n",
@@ -290,6 +342,9 @@ def main(argv=None):
         if args.null:
             with open(os.path.join(args.tempDir, args.nullOutfile), "w") as fh:
                 fh.write("\t".join(NULL_COLUMNS) + "\n")
+        if args.topKmers is not None:
+            with open(os.path.join(args.tempDir, args.kmerOutfile), "w") as fh:
+                fh.write("\t".join(KMER_COLUMNS) + "\n")
         log.info("No regions in %s: wrote the header to %s", args.bed or args.gff, out_path)
         return 0
 
@@ -309,6 +364,9 @@ def main(argv=None):
             if args.donors:
                 panel, planes = score_with_donors(args, hp, regions, log)
                 res = panel.plane(planes[0])
+            elif args.topKmers is not None:
+                res = hp.explainRegions(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], args.topKmers,
+                                        genomeKmers=genomeKmers)
             else:
                 res = hp.scoreRegions(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], genomeKmers=genomeKmers)
         except ValueError as err:
@@ -325,6 +383,12 @@ def main(argv=None):
         fh.write(header)
         fh.writelines(region_rows(regions, res, rip, cli._fmt()))
     log.info("Scored %d regions: %s", len(regions), out_path)
+    if args.topKmers is not None:
+        kmer_path = os.path.join(args.tempDir, args.kmerOutfile)
+        with open(kmer_path, "w") as fh:
+            fh.write("\t".join(KMER_COLUMNS) + "\n")
+            fh.writelines(kmer_rows(regions, res, args.maxWordSize, cli._fmt()))
+        log.info("Listed the %d largest KLD terms of each: %s", args.topKmers, kmer_path)
     if args.null:
         null_path = os.path.join(args.tempDir, args.nullOutfile)
         with open(null_path, "w") as fh:

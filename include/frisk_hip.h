@@ -315,6 +315,33 @@ int     frisk_score_ranges_panel(frisk_ctx* ctx, const int32_t* seq_index, const
                                  uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri,
                                  int64_t* nn);
 
+/* ---- the same rows, and the k-mers that drive each row's KLD --------------------------------
+ * "Why does this region score as it does?"  A row's KLD is the sum of the reference's summands (KLD, L465-470) over its present
+ * max-mers, term_k = pw_k * (ln(pw_k / pg_k) / ln 2); frisk_explain_ranges scores the rows as frisk_score_ranges does and keeps
+ * the top_n largest terms of each (csrc/explain_kernels.h: a range is counted once and scored twice).
+ * status, kld, gc, pi, si, cri, nn: bit for bit what frisk_score_ranges writes for the same rows.
+ * n_present[r]: the distinct max-mers of a kept row; 0 for a row the N rule drops.
+ * code, count, pw, pg, term: n * top_n entries each, row-major; slot j of row r is rank j, rank 0 the largest term.  Terms are
+ *   compared as numbers (-0.0 equals +0.0); among equal terms the smaller code comes first.  code: the max-mer in the digit order
+ *   of the tables (A, T, G, C = 0..3, first base most significant); count: its occurrences in the range; pw, pg: the two
+ *   normalised IVOM values the reference's KLD sums over; term: pw * (ln(pw / pg) / ln 2), in that order of operations.
+ *   A slot is filled only when status[r] is exactly FRISK_ROW_KEPT and j < min(top_n, n_present[r]); every other slot holds
+ *   code 0xFFFFFFFF, count 0 and NaN in pw, pg and term.  The terms of over-represented max-mers are positive, those of
+ *   under-represented present ones negative: a row with n_present <= top_n lists them all, and they sum to its kld.
+ *   The selection is a function of the row's set of (term, code) pairs alone: a row's bits depend on the range and the profile,
+ *   not on the other rows, their order, the form or the grid.
+ * flags: FRISK_SCAN_RIP and FRISK_RANGES_BIG as in frisk_score_ranges.  The same row and batch checks, with the same FRISK_E_ARG
+ * and nothing launched; FRISK_E_ARG too for top_n < 1, top_n > FRISK_EXPLAIN_MAX and a null required array (the six arrays here
+ * included).  FRISK_E_STATE: no finalised profile.  n = 0 is FRISK_OK and touches no output.  A streamed batch is waited for.  The
+ * scan's plan and rows, the panel and frisk_score_ranges are left alone.  Memory: 12 bytes per workgroup and entry of
+ * min(longest range, 4^kmax), for the length of the call.
+ * frisk_last_kernel_ms(ctx, 7) = the explain kernels' time of the last call. */
+#define FRISK_EXPLAIN_MAX 64
+int frisk_explain_ranges(frisk_ctx* ctx, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                         uint32_t flags, int32_t top_n,
+                         uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri, int64_t* nn,
+                         int32_t* n_present, uint32_t* code, uint32_t* count, double* pw, double* pg, double* term);
+
 /* Test utility (kmax <= 6): the two distributions IvomBuild returns for each candidate window of [c0,c1) (L1481-1482, L369-457) -
  * window-side and genome-side interpolated probabilities of the window's present max-mers, each normalised to sum 1 -
  * as dense vectors of 4^kmax doubles per candidate (0 for absent max-mers; all 0 for windows the reference drops). */
@@ -579,7 +606,8 @@ void  frisk_host_free(frisk_ctx* ctx, void* ptr);
 
 /* Timing of the most recent launches on the context's stream, measured with HIP events:
  * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels, 4 frisk_score_ranges' kernels,
- * 5 frisk_score_ranges_panel's kernels, 6 frisk_seq_null's generator kernels.  Returns milliseconds, <0 if none. */
+ * 5 frisk_score_ranges_panel's kernels, 6 frisk_seq_null's generator kernels, 7 frisk_explain_ranges' kernels.  Returns
+ * milliseconds, <0 if none. */
 double frisk_last_kernel_ms(const frisk_ctx* ctx, int which);
 
 #ifdef __cplusplus
