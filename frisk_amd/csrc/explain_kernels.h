@@ -1,6 +1,7 @@
 // explain_kernels.h - frisk_explain_ranges: the rows of range_kernels.h, and for each the present max-mers that contribute the
 // largest summands to its KLD (KLD L465-470: term_k = pw_k * (ln(pw_k / pg_k) / ln 2), the sum over the present max-mers).  A range
-// is counted once - stages 1 and 2 are range_kernels.h's own (range_short_tables, range_long_tables) - and scored twice:
+// is counted once - the forms and the row loop are range_kernels.h's own (ShortForm, LongForm, range_row_loop) - and scored twice,
+// by one mode (ExplainMode) on either form:
 //
 //   walk    the order-K table once: the codes of the non-empty bins go to the workgroup's slice of global scratch, compacted by
 //           wave ballots (one LDS atomic per wave and step).  Where in the slice a code lands depends on the arrival order of those
@@ -199,120 +200,35 @@ __device__ inline uint32_t explain_status(uint32_t status, uint32_t nvalid_top, 
     return status;
 }
 
-// ---- short form -------------------------------------------------------------------------------------------------------------
-// f(present, code) for every bin of the order-K table, with every lane of a wave in every call
-template <bool K8, typename F>
-__device__ inline void explain_walk_short(const uint32_t* t8, const uint16_t* small16, uint32_t offK, uint32_t nK, F&& f) {
-    constexpr int NT = FRISK_RANGE_NT;
-    const uint32_t tid = threadIdx.x;
-    if (K8) {
-        for (uint32_t base = 0; base < nK / 8; base += NT) {                // eight bins per read; nK / 8 is a multiple of NT
-            const uint32_t grp = base + tid;
-            const uint4 v = reinterpret_cast<const uint4*>(t8)[grp];
-            if (__ballot((v.x | v.y | v.z | v.w) != 0u) == 0ull) continue;  // (wave-uniform)
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int b = 0; b < 8; ++b) f(((w[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu) != 0u, 8 * grp + b);
-        }
-    } else {
-        for (uint32_t base = 0; base < nK; base += NT) {
-            const uint32_t code = base + tid;
-            f(code < nK && small16[offK + (code < nK ? code : 0u)] != 0, code);
-        }
-    }
-}
-
-template <bool K8>
-__global__ __launch_bounds__(FRISK_RANGE_NT) void explain_short_kernel(const ExplainParams E) {
-    constexpr int NT = FRISK_RANGE_NT, NW = NT / 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ uint32_t tl[8];                  // [0..5]: range_short_tables'; [7]: entries of the slice
-    __shared__ double red[NW * 6];
-    __shared__ ExplainLds<NW> X;
-    const RangeParams& P = E.R;
-    const int kmin = P.kmin;
-    const int kmax = K8 ? 8 : P.kmax;
-    const RangeLds L = range_lds(kmin, kmax);
-    const uint32_t* t8 = reinterpret_cast<const uint32_t*>(lds);
-    const uint16_t* small16 = reinterpret_cast<const uint16_t*>(lds + L.small);
-    const uint32_t nK = 1u << (2 * kmax);
-    const uint32_t offK = K8 ? 0u : uint32_t(table_offset(kmin, kmax));
-    double* st = E.stage + int64_t(blockIdx.x) * (E.cap + E.cap / 2);
-    uint32_t* sc = reinterpret_cast<uint32_t*>(st + E.cap);
-
-    const int64_t n_rows = range_rows(P);
-    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t row = P.list[q];
-        WinTables<K8> T;
-        int64_t S;
-        uint32_t nvalid_top;
-        if (range_short_tables<K8>(P, row, lds, tl, T, S, nvalid_top) != RANGE_ROW_SCORE) continue;
-        auto count = [&](int x, uint32_t c) -> uint32_t { return T.count(x, c); };
-        const uint32_t status0 = range_status(nvalid_top, S, kmin, kmax);
-        double r[FRISK_MAX_K + 1];
-        range_constants(S, r);
+// ---- the mode ---------------------------------------------------------------------------------------------------------------
+// walk, pass 1, range_finish and the selection of one row whose tables are ready (a mode of range_row_loop), on either form
+template <int NW>
+struct ExplainMode {
+    const ExplainParams& E;
+    double* red;                // NW * 6 doubles of LDS
+    ExplainLds<NW>& X;
+    double* st;                 // the workgroup's slice: terms ...
+    uint32_t* sc;               // ... then codes
+    __device__ ExplainMode(const ExplainParams& E_, double* red_, ExplainLds<NW>& X_)
+        : E(E_), red(red_), X(X_), st(E_.stage + int64_t(blockIdx.x) * (E_.cap + E_.cap / 2)), sc(reinterpret_cast<uint32_t*>(st + E_.cap)) {}
+    __device__ void dropped(int64_t) const {}
+    template <typename FORM>
+    __device__ void score(const FORM& form, int64_t row, uint32_t status0, uint32_t nvalid_top, const double* r) const {
+        constexpr int NT = FORM::NT;
+        static_assert(NT == NW * 64, "the form's workgroup");
+        const RangeParams& P = E.R;
+        const int kmin = form.kmin, kmax = form.kmax();
+        uint32_t* tl7 = form.tl + 7;                                        // entries of the slice (cleared by form.tables)
+        auto count = [&](int x, uint32_t c) -> uint32_t { return form.count(x, c); };
 
         // ---- walk: the present codes
-        explain_walk_short<K8>(t8, small16, offK, nK, [&](bool present, uint32_t code) { explain_push(present, code, &tl[7], sc, E.cap); });
+        form.walk([&](bool present, uint32_t code) { explain_push(present, code, tl7, sc, E.cap); });
         __threadfence();
         __syncthreads();
-        const int64_t staged = int64_t(range_uni(tl[7]));
+        const int64_t staged = int64_t(range_uni(*tl7));
         const uint32_t m = uint32_t(staged < E.cap ? staged : E.cap);
 
-        // ---- pass 1: range_short_kernel's stages 3 + 4
-        ExactSum accw = exact_begin(), accg = exact_begin(), acct = exact_begin();
-        for (uint32_t i = threadIdx.x; i < m; i += NT) range_score_maxmer(sc[i], kmin, kmax, r, P.ig, count, accw, accg, acct);
-        range_finish<NW>(P, row, status0, nvalid_top, accw, accg, acct, red);
-        const double Sw = exact_value(accw), Sg = exact_value(accg);
-        if (threadIdx.x == 0) E.n_present[row] = int32_t(m);
-        if (range_uni(explain_status(status0, nvalid_top, Sg)) != ROW_KEPT) continue;
-        explain_select<NT>(E, row, m, st, sc, X,
-                           [&](uint32_t code) { return explain_term(code, kmin, kmax, r, P.ig, count, Sw, Sg); },
-                           [&](uint32_t code) { return count(kmax, code); });
-    }
-}
-
-// ---- long form --------------------------------------------------------------------------------------------------------------
-template <typename F>
-__device__ inline void explain_walk_long(const uint32_t* cnt, int64_t offK, uint32_t nK, F&& f) {
-    for (uint32_t base = 0; base < nK; base += FRISK_RANGE_BIG_NT) {
-        const uint32_t code = base + threadIdx.x;
-        f(code < nK && cnt[offK + (code < nK ? code : 0u)] != 0u, code);
-    }
-}
-
-__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void explain_long_kernel(const ExplainParams E, uint32_t* __restrict__ big, int64_t big_stride) {
-    constexpr int NT = FRISK_RANGE_BIG_NT, NW = NT / 64;
-    __shared__ uint32_t tl[8];                  // [0..4]: range_long_tables'; [7]: entries of the slice
-    __shared__ double red[NW * 6];
-    __shared__ ExplainLds<NW> X;
-    const RangeParams& P = E.R;
-    const int kmin = P.kmin, kmax = P.kmax;
-    uint32_t* cnt = big + int64_t(blockIdx.x) * big_stride;
-    const int64_t offK = table_offset(kmin, kmax);
-    const uint32_t nK = 1u << (2 * kmax);
-    double* st = E.stage + int64_t(blockIdx.x) * (E.cap + E.cap / 2);
-    uint32_t* sc = reinterpret_cast<uint32_t*>(st + E.cap);
-
-    const int64_t n_rows = range_rows(P);
-    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t row = P.list[q];
-        int64_t S;
-        uint32_t nvalid_top;
-        if (range_long_tables(P, row, cnt, big_stride, tl, S, nvalid_top) != RANGE_ROW_SCORE) continue;
-        auto count = [&](int x, uint32_t c) -> uint32_t { return cnt[table_offset(kmin, x) + c]; };
-        const uint32_t status0 = range_status(nvalid_top, S, kmin, kmax);
-        double r[FRISK_MAX_K + 1];
-        range_constants(S, r);
-
-        // ---- walk: the present codes
-        explain_walk_long(cnt, offK, nK, [&](bool present, uint32_t code) { explain_push(present, code, &tl[7], sc, E.cap); });
-        __threadfence();
-        __syncthreads();
-        const int64_t staged = int64_t(range_uni(tl[7]));
-        const uint32_t m = uint32_t(staged < E.cap ? staged : E.cap);
-
-        // ---- pass 1: range_long_kernel's
+        // ---- pass 1: PlainMode's stages 3 + 4
         ExactSum accw = exact_begin(), accg = exact_begin(), acct = exact_begin();
         for (uint32_t i = threadIdx.x; i < m; i += NT) range_score_maxmer(sc[i], kmin, kmax, r, P.ig, count, accw, accg, acct);
         range_finish<NW>(P, row, status0, nvalid_top, accw, accg, acct, red);   // (its barrier: pass 1 has read the tables)
@@ -322,6 +238,25 @@ __global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void explain_long_kernel(const 
             explain_select<NT>(E, row, m, st, sc, X,
                                [&](uint32_t code) { return explain_term(code, kmin, kmax, r, P.ig, count, Sw, Sg); },
                                [&](uint32_t code) { return count(kmax, code); });
-        range_zero_tables(cnt, big_stride);     // (behind a barrier: every read of the tables is done)
     }
+};
+
+template <bool K8>
+__global__ __launch_bounds__(FRISK_RANGE_NT) void explain_short_kernel(const ExplainParams E) {
+    constexpr int NW = FRISK_RANGE_NT / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ uint32_t tl[8];
+    __shared__ double red[NW * 6];
+    __shared__ ExplainLds<NW> X;
+    ShortForm<K8> form(E.R, lds, tl);
+    range_row_loop(E.R, form, ExplainMode<NW>(E, red, X));
+}
+
+__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void explain_long_kernel(const ExplainParams E, uint32_t* __restrict__ big, int64_t big_stride) {
+    constexpr int NW = FRISK_RANGE_BIG_NT / 64;
+    __shared__ uint32_t tl[8];
+    __shared__ double red[NW * 6];
+    __shared__ ExplainLds<NW> X;
+    LongForm form(E.R, big, big_stride, tl);
+    range_row_loop(E.R, form, ExplainMode<NW>(E, red, X));
 }

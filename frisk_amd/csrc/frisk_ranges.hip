@@ -1,237 +1,161 @@
-// frisk_ranges.hip - frisk_score_ranges of the C ABI (include/frisk_hip.h): the scan loop's columns (KLD, GC, RIP indices) of
-// arbitrary ranges of the resident batch against the context's finalised profile (range_kernels.h).  The host checks the rows,
-// sorts them longest first (the workgroups of a launch take its list by grid stride), splits them between the two forms and
-// queues both launches on the context's stream; a range the short form cannot hold reaches the long form through a device list,
-// without a host round trip.  The context is frisk_ctx.h's; the scan's plan and row buffers are not touched.  gfx950 (MI355X)
-// only.  frisk_score_ranges_panel and the panel's three calls are here too: the same host path with panel_kernels.h's kernels,
-// every profile of the context's panel in one pass.  frisk_explain_ranges too: the same host path with explain_kernels.h's kernels,
-// their scratch and the six arrays of the largest KLD terms.  Build: see __graft_entry__.build_hip().
+// frisk_ranges.hip - the region scorer of the C ABI (include/frisk_hip.h): frisk_score_ranges, frisk_score_ranges_panel and
+// frisk_explain_ranges - the scan loop's columns (KLD, GC, RIP indices) of arbitrary ranges of the resident batch against the
+// context's finalised profile (range_kernels.h), against every profile of its panel in one pass (panel_kernels.h), and with the
+// largest KLD terms of each range (explain_kernels.h) - and the panel's three calls.  What the host decides is range_plan.h's: the
+// row checks, the rows longest first (the workgroups of a launch take its list by grid stride) and their split between the two
+// forms.  An entry point checks its call, plans it, and composes the steps below with its own kernels, buffers and timing slot:
+// upload the plan, reserve the long form's scratch, queue both launches on the context's stream - a range the short form cannot
+// hold reaches the long form through a device list, without a host round trip -, copy the columns back.  The context is
+// frisk_ctx.h's; the scan's plan and row buffers are not touched.  gfx950 (MI355X) only.  Build: see __graft_entry__.build_hip().
 #include <algorithm>
-#include <numeric>
-#include <string>
-#include <vector>
 
 #include "frisk_ctx.h"
+#include "range_plan.h"
 #include "range_kernels.h"
 #include "panel_kernels.h"
 #include "explain_kernels.h"
 
 namespace {
 
-template <bool K8>
-hipError_t launch_short(const RangeParams& P, int grid, size_t lds, hipStream_t st) {
-    auto kern = range_short_kernel<K8>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+// a short-form launch, the K = 8 instantiation or the other: the dynamic LDS is beyond the default limit
+template <typename KERNEL, typename PARAMS>
+hipError_t launch_with_lds(frisk_ctx* c, KERNEL kernel_k8, KERNEL kernel, const PARAMS& params, int grid, size_t lds) {
+    if (c->kmax == 8) kernel = kernel_k8;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
     if (e != hipSuccess) return e;
-    kern<<<grid, FRISK_RANGE_NT, lds, st>>>(P);
+    kernel<<<grid, FRISK_RANGE_NT, lds, c->stream>>>(params);
     return hipGetLastError();
 }
 
-template <bool K8>
-hipError_t launch_panel_short(const PanelParams& Q, int grid, size_t lds, hipStream_t st) {
-    auto kern = panel_short_kernel<K8>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-    kern<<<grid, FRISK_RANGE_NT, lds, st>>>(Q);
-    return hipGetLastError();
-}
-
-template <bool K8>
-hipError_t launch_explain_short(const ExplainParams& E, int grid, size_t lds, hipStream_t st) {
-    auto kern = explain_short_kernel<K8>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-    kern<<<grid, FRISK_RANGE_NT, lds, st>>>(E);
-    return hipGetLastError();
-}
-
-// frisk_explain_ranges' own arguments (host arrays)
-struct ExplainOut {
-    int32_t top_n;
-    int32_t* n_present;
-    uint32_t *code, *count;
-    double *pw, *pg, *term;
+// the arguments the three entry points share
+struct RangeCall {
+    const int32_t* seq_index;
+    const int64_t *start, *stop;
+    int64_t n;
+    uint32_t flags;
+    uint32_t* status;
+    double *kld, *gc, *pi, *si, *cri;
+    int64_t* nn;
+    bool rip() const { return (flags & FRISK_SCAN_RIP) != 0; }
+    bool arrays_given() const { return seq_index && start && stop && status && kld && gc && nn && (!rip() || (pi && si && cri)); }
 };
 
-// the three entry points: `panel` = score against the context's panel (np planes of status and kld) instead of its own profile;
-// `ex` = the explain kernels and their outputs (never with `panel`)
-int score_ranges(frisk_ctx* c, const bool panel, const ExplainOut* ex, const int32_t* seq_index, const int64_t* start, const int64_t* stop,
-                 int64_t n, uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri, int64_t* nn) {
-    if (!c) return FRISK_E_ARG;
-    const std::string who = ex ? "frisk_explain_ranges" : panel ? "frisk_score_ranges_panel" : "frisk_score_ranges";
-    if (n < 0) return fail(c, FRISK_E_ARG, who + ": n < 0");
-    if (ex && (ex->top_n < 1 || ex->top_n > FRISK_EXPLAIN_MAX)) return fail(c, FRISK_E_ARG, who + ": top_n outside 1 .. FRISK_EXPLAIN_MAX");
+// the device side of a call: the plan's arrays and the score columns (freed on every return)
+struct RangeBufs {
+    DevBuf<int64_t> ranges, short_rows, long_rows, nn;
+    DevBuf<unsigned int> cnt;           // [0]: rows handed over to the long form
+    DevBuf<uint32_t> status;            // `planes` planes
+    DevBuf<double> val;                 // `planes` planes of kld, then gc [pi si cri]
+};
+
+// What every entry point checks before it plans: the call's own refusal (`early`, nullptr without), the resident batch, the
+// flags, the state the entry point needs (`state_ok`, else FRISK_E_STATE with `state_msg`) and the arrays.  FRISK_OK: go on;
+// RANGE_NOTHING_TO_DO: n = 0, the entry point returns FRISK_OK; else the refusal.
+enum { RANGE_NOTHING_TO_DO = 1 };
+int check_call(frisk_ctx* c, const std::string& who, const RangeCall& A, const char* early, bool state_ok, const char* state_msg,
+               bool more_arrays_given) {
+    if (A.n < 0) return fail(c, FRISK_E_ARG, who + ": n < 0");
+    if (early) return fail(c, FRISK_E_ARG, who + early);
     const frisk_ctx::Batch& B = c->b();
     if (!B.have_seq) return fail(c, FRISK_E_ARG, who + ": no resident sequence batch");
     if (B.tiled) return fail(c, FRISK_E_ARG, who + ": the resident batch holds tiles, not whole scaffolds");
-    const bool rip = (flags & FRISK_SCAN_RIP) != 0;
-    if (rip && !(c->kmin <= 2 && c->kmax >= 2)) return fail(c, FRISK_E_ARG, "FRISK_SCAN_RIP needs kmin <= 2 <= kmax");
-    if (panel ? c->panel_n == 0 : !c->profile_final) return fail(c, FRISK_E_STATE, who + (panel ? ": the panel is empty" : ": no finalised profile"));
-    if (n == 0) return FRISK_OK;
-    if (!seq_index || !start || !stop || !status || !kld || !gc || !nn || (rip && (!pi || !si || !cri)))
-        return fail(c, FRISK_E_ARG, who + ": null array");
-    if (ex && (!ex->n_present || !ex->code || !ex->count || !ex->pw || !ex->pg || !ex->term)) return fail(c, FRISK_E_ARG, who + ": null array");
-    std::vector<int64_t> ranges(size_t(n) * 2);
-    for (int64_t r = 0; r < n; ++r) {
-        const int32_t s = seq_index[r];
-        if (s < 0 || s >= B.n_seq) return fail(c, FRISK_E_ARG, who + ": sequence index out of range in row " + std::to_string(r));
-        if (start[r] < 0 || stop[r] <= start[r] || stop[r] > B.seq_len[size_t(s)] || stop[r] - start[r] > int64_t(0x7FFFFFFF))
-            return fail(c, FRISK_E_ARG, who + ": range outside the scaffold (or empty, or of 2^31 bases or more) in row " + std::to_string(r));
-        ranges[size_t(2 * r)] = B.seq_off[size_t(s)] + start[r];
-        ranges[size_t(2 * r + 1)] = stop[r] - start[r];
-    }
-    // longest first (ties by row: the order is a function of the call alone), then one list per form
-    std::vector<int64_t> order(static_cast<size_t>(n));
-    std::iota(order.begin(), order.end(), int64_t(0));
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        const int64_t la = ranges[size_t(2 * a + 1)], lb = ranges[size_t(2 * b + 1)];
-        return la != lb ? la > lb : a < b;
-    });
-    const bool k8 = c->kmax == 8;
-    const bool all_long = (flags & FRISK_RANGES_BIG) != 0 || c->kmax > 8;
-    std::vector<int64_t> short_rows, long_rows;
-    for (int64_t r : order) (all_long || ranges[size_t(2 * r + 1)] > FRISK_RANGE_SHORT_MAX ? long_rows : short_rows).push_back(r);
-    const int64_t n_short = int64_t(short_rows.size()), n_long = int64_t(long_rows.size());
-    const int64_t long_cap = n_long + (k8 ? n_short : 0);       // every short row of kmax = 8 may be handed over
-    // explain: entries of a workgroup's slice per form - a range of len bases has at most min(len, 4^kmax) distinct max-mers (even:
-    // the 32-bit codes lie behind the terms)
-    auto slice_cap = [&](int64_t longest) { return (std::min<int64_t>(longest, int64_t(1) << (2 * c->kmax)) + 1) / 2 * 2; };
-    const int64_t len_short = n_short ? ranges[size_t(2 * short_rows[0] + 1)] : 0, len_long = n_long ? ranges[size_t(2 * long_rows[0] + 1)] : 0;
-    const int64_t cap_short = slice_cap(len_short), cap_long = slice_cap(std::max(len_long, k8 ? len_short : 0));
+    if (A.rip() && !(c->kmin <= 2 && c->kmax >= 2)) return fail(c, FRISK_E_ARG, "FRISK_SCAN_RIP needs kmin <= 2 <= kmax");
+    if (!state_ok) return fail(c, FRISK_E_STATE, who + state_msg);
+    if (A.n == 0) return RANGE_NOTHING_TO_DO;
+    if (!A.arrays_given() || !more_arrays_given) return fail(c, FRISK_E_ARG, who + ": null array");
+    return FRISK_OK;
+}
 
+// Plan the call's rows (range_plan.h; a bad row is refused here), then take the device and wait for a streamed batch.
+// per_cu_short: three workgroups of the short form per CU below kmax = 8 (43.7 KB of LDS at 1..7); one for a kernel that is held
+// to one by its registers
+int begin_call(frisk_ctx* c, const std::string& who, const RangeCall& A, int per_cu_short, int top_n, RangePlan& plan) {
+    const frisk_ctx::Batch& B = c->b();
+    const bool all_long = (A.flags & FRISK_RANGES_BIG) != 0 || c->kmax > 8;
+    plan = plan_ranges(B.n_seq, B.seq_len.data(), B.seq_off.data(), A.seq_index, A.start, A.stop, A.n, c->kmax, all_long, c->num_cu,
+                       per_cu_short, top_n);
+    if (plan.error_code) return fail(c, plan.error_code, who + ": " + plan.error);
     HIPC(c, hipSetDevice(c->device));
-    if (int rc = settle_stream(c)) return rc;
-    const size_t N = size_t(n);
-    const size_t np = panel ? size_t(c->panel_n) : 1;            // planes of status and kld
-    const int ncol = rip ? 4 : 1;                               // gc [pi si cri], behind the planes of kld
-    DevBuf<int64_t> d_ranges, d_short, d_long, d_nn;            // (freed on every return below)
-    DevBuf<unsigned int> d_cnt;                                 // [0]: rows handed over to the long form
-    DevBuf<uint32_t> d_status;
-    DevBuf<double> d_val, d_stage, d_top;                       // explain: the slices of both forms; pw, pg, term
-    DevBuf<uint32_t> d_topu;                                    // ... code, count
-    DevBuf<int32_t> d_npres;
-    HIPC(c, d_ranges.reserve(2 * N, 2 * N));
-    HIPC(c, d_short.reserve(size_t(std::max<int64_t>(n_short, 1)), size_t(std::max<int64_t>(n_short, 1))));
-    HIPC(c, d_long.reserve(size_t(std::max<int64_t>(long_cap, 1)), size_t(std::max<int64_t>(long_cap, 1))));
-    HIPC(c, d_nn.reserve(N, N));
-    HIPC(c, d_cnt.reserve(4, 4));
-    HIPC(c, d_status.reserve(np * N, np * N));
-    HIPC(c, d_val.reserve(N * (np + size_t(ncol)), N * (np + size_t(ncol))));
-    HIPC(c, hipMemcpyAsync(d_ranges.p, ranges.data(), 2 * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    if (n_short) HIPC(c, hipMemcpyAsync(d_short.p, short_rows.data(), size_t(n_short) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    if (n_long) HIPC(c, hipMemcpyAsync(d_long.p, long_rows.data(), size_t(n_long) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemsetAsync(d_cnt.p, 0, 4 * sizeof(unsigned int), c->stream));
+    return settle_stream(c);
+}
 
-    RangeParams P = RangeParams();
-    P.codes = B.d_codes.p; P.inv = B.d_inv.p; P.low = B.d_low.p; P.ig = c->d_ig.p; P.ranges = d_ranges.p;
-    P.kmin = c->kmin; P.kmax = c->kmax; P.rip = rip ? 1u : 0u;
-    P.status = d_status.p; P.nn = d_nn.p; P.kld = d_val.p; P.gc = d_val.p + np * N;
-    if (rip) { P.pi = P.gc + N; P.si = P.gc + 2 * N; P.cri = P.gc + 3 * N; }
-    PanelParams Q = PanelParams();
-    if (panel) {
-        for (int t = 0; t * FRISK_PANEL_TILE < c->panel_n; ++t) Q.tile[t] = c->panel_tile[t].p;
-        Q.n_prof = c->panel_n;
-        Q.plane = n;
-        P.ig = nullptr;
-    }
+// Reserve the buffers, queue the copies of the plan's arrays and clear the hand-over counter; P: the kernels' common arguments,
+// with `planes` planes of status and kld (the first at P.status / P.kld).
+int upload_plan(frisk_ctx* c, const RangeCall& A, const RangePlan& plan, size_t planes, RangeBufs& D, RangeParams& P) {
+    const frisk_ctx::Batch& B = c->b();
+    const size_t N = size_t(A.n);
+    const size_t ncol = A.rip() ? 4 : 1;
+    const size_t n_short = size_t(plan.n_short()), n_long = size_t(plan.n_long()), long_cap = size_t(plan.long_cap);
+    HIPC(c, D.ranges.reserve(2 * N, 2 * N));
+    HIPC(c, D.short_rows.reserve(std::max<size_t>(n_short, 1), std::max<size_t>(n_short, 1)));
+    HIPC(c, D.long_rows.reserve(std::max<size_t>(long_cap, 1), std::max<size_t>(long_cap, 1)));
+    HIPC(c, D.nn.reserve(N, N));
+    HIPC(c, D.cnt.reserve(4, 4));
+    HIPC(c, D.status.reserve(planes * N, planes * N));
+    HIPC(c, D.val.reserve(N * (planes + ncol), N * (planes + ncol)));
+    HIPC(c, hipMemcpyAsync(D.ranges.p, plan.ranges.data(), 2 * N * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (n_short) HIPC(c, hipMemcpyAsync(D.short_rows.p, plan.short_rows.data(), n_short * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (n_long) HIPC(c, hipMemcpyAsync(D.long_rows.p, plan.long_rows.data(), n_long * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemsetAsync(D.cnt.p, 0, 4 * sizeof(unsigned int), c->stream));
+    P = RangeParams();
+    P.codes = B.d_codes.p; P.inv = B.d_inv.p; P.low = B.d_low.p; P.ig = c->d_ig.p; P.ranges = D.ranges.p;
+    P.kmin = c->kmin; P.kmax = c->kmax; P.rip = A.rip() ? 1u : 0u;
+    P.status = D.status.p; P.nn = D.nn.p; P.kld = D.val.p; P.gc = D.val.p + planes * N;
+    if (A.rip()) { P.pi = P.gc + N; P.si = P.gc + 2 * N; P.cri = P.gc + 3 * N; }
+    return FRISK_OK;
+}
 
-    ExplainParams E = ExplainParams();
-    const size_t NS = ex ? N * size_t(ex->top_n) : 0;
-    if (ex) {
-        HIPC(c, d_top.reserve(3 * NS, 3 * NS));
-        HIPC(c, d_topu.reserve(2 * NS, 2 * NS));
-        HIPC(c, d_npres.reserve(N, N));
-        E.top_n = ex->top_n; E.n_present = d_npres.p;
-        E.code = d_topu.p; E.count = d_topu.p + NS;
-        E.pw = d_top.p; E.pg = d_top.p + NS; E.term = d_top.p + 2 * NS;
-    }
+// the two launches' lists: the short form appends behind the long form's own rows
+RangeParams short_list(RangeParams P, const RangePlan& plan, const RangeBufs& D) {
+    P.list = D.short_rows.p; P.n_list = plan.n_short(); P.more = nullptr;
+    P.out_list = D.long_rows.p + plan.n_long(); P.out_count = D.cnt.p;
+    return P;
+}
+RangeParams long_list(RangeParams P, const RangePlan& plan, const RangeBufs& D) {
+    P.list = D.long_rows.p; P.n_list = plan.n_long();
+    P.more = plan.long_cap > plan.n_long() ? D.cnt.p : nullptr;     // (kmax = 8 with short rows)
+    return P;
+}
 
-    // the long form's scratch: one slice of 32-bit tables per workgroup (350 KB at 1..8, 89 MB at K = 12), as many workgroups as
-    // the device can spare scratch for.  The short rows of kmax = 8 may all be handed over, but hardly any is: they add a few
-    // workgroups to the grid, not one each (the grid-stride loop takes whatever the list holds in the end).
-    const int64_t stride = (c->nprof + 3) / 4 * 4;
-    int64_t want = std::min<int64_t>(n_long + std::min<int64_t>(long_cap - n_long, FRISK_RANGE_HANDOVER_WGS), c->num_cu);
-    const size_t slice_long = ex ? size_t(cap_long) * 12 : 0;   // explain: bytes of a long-form workgroup's slice
-    if (long_cap) {
-        if (size_t(want) * size_t(stride) > c->d_big.cap || slice_long) {
-            size_t free_b = 0, total_b = 0;
-            HIPC(c, hipMemGetInfo(&free_b, &total_b));
-            const int64_t fit = int64_t((free_b / 2 + c->d_big.cap * 4) / (size_t(stride) * 4 + slice_long));
-            want = std::max<int64_t>(1, std::min(want, fit));
-        }
-        HIPC(c, c->d_big.reserve(size_t(want) * size_t(stride)));
-        HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(want) * size_t(stride) * 4, c->stream));
+// The long form's scratch: one slice of `stride` 32-bit words per workgroup (350 KB at 1..8, 89 MB at K = 12) in the context's
+// d_big, all-zero, for as many workgroups (`wgs`) as the device can spare scratch for; slice_bytes: what a workgroup needs beside
+// it.  Nothing without a long-form launch.
+int reserve_long_scratch(frisk_ctx* c, const RangePlan& plan, size_t slice_bytes, int64_t& wgs, int64_t& stride) {
+    stride = (c->nprof + 3) / 4 * 4;
+    wgs = plan.want_long;
+    if (!plan.long_cap) return FRISK_OK;
+    if (size_t(wgs) * size_t(stride) > c->d_big.cap || slice_bytes) {
+        size_t free_b = 0, total_b = 0;
+        HIPC(c, hipMemGetInfo(&free_b, &total_b));
+        wgs = fit_long_workgroups(wgs, stride, slice_bytes, free_b, c->d_big.cap);
     }
+    HIPC(c, c->d_big.reserve(size_t(wgs) * size_t(stride)));
+    HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(wgs) * size_t(stride) * 4, c->stream));
+    return FRISK_OK;
+}
 
-    const RangeLds L = range_lds(c->kmin, c->kmax);
-    // kmax = 8: the order-8 table leaves room for one workgroup per CU; below, three (43.7 KB at 1..7).  The panel kernel holds
-    // a tile's 24 ExactSums in registers (196 VGPRs: two waves per SIMD, i.e. one workgroup per CU at any kmax)
-    const int per_cu = (k8 || panel) ? 1 : 3;
-    const int grid = int(std::min<int64_t>(n_short, int64_t(c->num_cu) * per_cu));
-    if (ex) {           // the short form's slices, then the long form's
-        const size_t words_short = n_short ? size_t(grid) * size_t(cap_short) * 3 / 2 : 0;
-        const size_t words_long = long_cap ? size_t(want) * size_t(cap_long) * 3 / 2 : 0;
-        HIPC(c, d_stage.reserve(words_short + words_long + 1, words_short + words_long + 1));
-        E.stage = d_stage.p;
-    }
-
-    HIPC(c, hipEventRecord(c->ev0, c->stream));
-    if (ex) {
-        explain_fill_kernel<<<grid_for(int64_t(NS), 256, 4096), 256, 0, c->stream>>>(E, n);
-        HIPC(c, hipGetLastError());
-    }
-    if (n_short) {
-        RangeParams S = P;
-        S.list = d_short.p; S.n_list = n_short; S.more = nullptr;
-        S.out_list = d_long.p + n_long; S.out_count = d_cnt.p;
-        if (ex) {
-            E.R = S; E.cap = cap_short;
-            HIPC(c, k8 ? launch_explain_short<true>(E, grid, L.total, c->stream) : launch_explain_short<false>(E, grid, L.total, c->stream));
-        } else if (panel) {
-            Q.R = S;
-            const size_t lds = panel_lds_total(c->kmin, c->kmax);
-            HIPC(c, k8 ? launch_panel_short<true>(Q, grid, lds, c->stream) : launch_panel_short<false>(Q, grid, lds, c->stream));
-        } else {
-            HIPC(c, k8 ? launch_short<true>(S, grid, L.total, c->stream) : launch_short<false>(S, grid, L.total, c->stream));
-        }
-    }
-    if (long_cap) {     // (kmax = 8 without a long row: a few workgroups that find the hand-over list empty nearly always)
-        RangeParams G = P;
-        G.list = d_long.p; G.n_list = n_long; G.more = (k8 && n_short) ? d_cnt.p : nullptr;
-        if (ex) {
-            E.R = G; E.cap = cap_long;
-            E.stage = d_stage.p + (n_short ? size_t(grid) * size_t(cap_short) * 3 / 2 : 0);
-            explain_long_kernel<<<int(want), FRISK_RANGE_BIG_NT, 0, c->stream>>>(E, c->d_big.p, stride);
-        } else if (panel) {
-            Q.R = G;
-            panel_long_kernel<<<int(want), FRISK_RANGE_BIG_NT, 0, c->stream>>>(Q, c->d_big.p, stride);
-        } else {
-            range_long_kernel<<<int(want), FRISK_RANGE_BIG_NT, 0, c->stream>>>(G, c->d_big.p, stride);
-        }
-        HIPC(c, hipGetLastError());
-    }
+// end of the timed interval; the score columns to the caller's arrays (queued)
+int copy_back(frisk_ctx* c, const RangeCall& A, const RangeParams& P, size_t planes) {
+    const size_t N = size_t(A.n);
     HIPC(c, hipEventRecord(c->ev1, c->stream));
-    HIPC(c, hipMemcpyAsync(status, d_status.p, np * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(nn, d_nn.p, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(kld, P.kld, np * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(gc, P.gc, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (rip) {
-        HIPC(c, hipMemcpyAsync(pi, P.pi, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(si, P.si, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(cri, P.cri, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(A.status, P.status, planes * N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(A.nn, P.nn, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(A.kld, P.kld, planes * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(A.gc, P.gc, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (A.rip()) {
+        HIPC(c, hipMemcpyAsync(A.pi, P.pi, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(A.si, P.si, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(A.cri, P.cri, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
-    if (ex) {
-        HIPC(c, hipMemcpyAsync(ex->n_present, d_npres.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(ex->code, E.code, NS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(ex->count, E.count, NS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(ex->pw, E.pw, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(ex->pg, E.pg, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(ex->term, E.term, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
+    return FRISK_OK;
+}
+
+// wait for the call; the kernels' time between the two events goes to frisk_last_kernel_ms(ctx, slot)
+int finish_call(frisk_ctx* c, int slot) {
     HIPC(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPC(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->ms[ex ? 7 : panel ? 5 : 4] = ms;
+    c->ms[slot] = ms;
     return FRISK_OK;
 }
 
@@ -240,21 +164,118 @@ int score_ranges(frisk_ctx* c, const bool panel, const ExplainOut* ex, const int
 extern "C" int frisk_score_ranges(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
                                   uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri,
                                   int64_t* nn) {
-    return score_ranges(c, false, nullptr, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
+    if (!c) return FRISK_E_ARG;
+    const std::string who = "frisk_score_ranges";
+    const RangeCall A = {seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn};
+    if (int rc = check_call(c, who, A, nullptr, c->profile_final, ": no finalised profile", true)) return rc == RANGE_NOTHING_TO_DO ? FRISK_OK : rc;
+    RangePlan plan;
+    if (int rc = begin_call(c, who, A, 3, 0, plan)) return rc;
+    RangeBufs D;
+    RangeParams P;
+    int64_t wgs = 0, stride = 0;
+    if (int rc = upload_plan(c, A, plan, 1, D, P)) return rc;
+    if (int rc = reserve_long_scratch(c, plan, 0, wgs, stride)) return rc;
+    HIPC(c, hipEventRecord(c->ev0, c->stream));
+    if (plan.n_short()) {
+        const size_t lds = range_lds(c->kmin, c->kmax).total;
+        const RangeParams S = short_list(P, plan, D);
+        HIPC(c, launch_with_lds(c, range_short_kernel<true>, range_short_kernel<false>, S, plan.grid_short, lds));
+    }
+    if (plan.long_cap) {        // (kmax = 8 without a long row: a few workgroups that find the hand-over list empty nearly always)
+        range_long_kernel<<<int(wgs), FRISK_RANGE_BIG_NT, 0, c->stream>>>(long_list(P, plan, D), c->d_big.p, stride);
+        HIPC(c, hipGetLastError());
+    }
+    if (int rc = copy_back(c, A, P, 1)) return rc;
+    return finish_call(c, 4);
+}
+
+extern "C" int frisk_score_ranges_panel(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                                        uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si,
+                                        double* cri, int64_t* nn) {
+    if (!c) return FRISK_E_ARG;
+    const std::string who = "frisk_score_ranges_panel";
+    const RangeCall A = {seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn};
+    if (int rc = check_call(c, who, A, nullptr, c->panel_n != 0, ": the panel is empty", true)) return rc == RANGE_NOTHING_TO_DO ? FRISK_OK : rc;
+    // the short kernel holds a tile's 24 ExactSums in registers (196 VGPRs: two waves per SIMD, i.e. one workgroup per CU at any kmax)
+    RangePlan plan;
+    if (int rc = begin_call(c, who, A, 1, 0, plan)) return rc;
+    RangeBufs D;
+    PanelParams Q = PanelParams();
+    int64_t wgs = 0, stride = 0;
+    if (int rc = upload_plan(c, A, plan, size_t(c->panel_n), D, Q.R)) return rc;
+    Q.R.ig = nullptr;           // the tiles take its place
+    for (int t = 0; t * FRISK_PANEL_TILE < c->panel_n; ++t) Q.tile[t] = c->panel_tile[t].p;
+    Q.n_prof = c->panel_n;
+    Q.plane = n;
+    const RangeParams P = Q.R;
+    if (int rc = reserve_long_scratch(c, plan, 0, wgs, stride)) return rc;
+    HIPC(c, hipEventRecord(c->ev0, c->stream));
+    if (plan.n_short()) {
+        const size_t lds = panel_lds_total(c->kmin, c->kmax);
+        Q.R = short_list(P, plan, D);
+        HIPC(c, launch_with_lds(c, panel_short_kernel<true>, panel_short_kernel<false>, Q, plan.grid_short, lds));
+    }
+    if (plan.long_cap) {
+        Q.R = long_list(P, plan, D);
+        panel_long_kernel<<<int(wgs), FRISK_RANGE_BIG_NT, 0, c->stream>>>(Q, c->d_big.p, stride);
+        HIPC(c, hipGetLastError());
+    }
+    if (int rc = copy_back(c, A, P, size_t(c->panel_n))) return rc;
+    return finish_call(c, 5);
 }
 
 extern "C" int frisk_explain_ranges(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
                                     uint32_t flags, int32_t top_n, uint32_t* status, double* kld, double* gc, double* pi, double* si,
                                     double* cri, int64_t* nn, int32_t* n_present, uint32_t* code, uint32_t* count, double* pw,
                                     double* pg, double* term) {
-    const ExplainOut ex = {top_n, n_present, code, count, pw, pg, term};
-    return score_ranges(c, false, &ex, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
-}
-
-extern "C" int frisk_score_ranges_panel(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
-                                        uint32_t flags, uint32_t* status, double* kld, double* gc, double* pi, double* si,
-                                        double* cri, int64_t* nn) {
-    return score_ranges(c, true, nullptr, seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn);
+    if (!c) return FRISK_E_ARG;
+    const std::string who = "frisk_explain_ranges";
+    const RangeCall A = {seq_index, start, stop, n, flags, status, kld, gc, pi, si, cri, nn};
+    const char* bad_top = top_n < 1 || top_n > FRISK_EXPLAIN_MAX ? ": top_n outside 1 .. FRISK_EXPLAIN_MAX" : nullptr;
+    if (int rc = check_call(c, who, A, bad_top, c->profile_final, ": no finalised profile", n_present && code && count && pw && pg && term)) return rc == RANGE_NOTHING_TO_DO ? FRISK_OK : rc;
+    RangePlan plan;
+    if (int rc = begin_call(c, who, A, 3, top_n, plan)) return rc;
+    RangeBufs D;
+    DevBuf<double> d_stage, d_top;      // the slices of both forms; pw, pg, term
+    DevBuf<uint32_t> d_topu;            // code, count
+    DevBuf<int32_t> d_npres;
+    ExplainParams E = ExplainParams();
+    int64_t wgs = 0, stride = 0;
+    if (int rc = upload_plan(c, A, plan, 1, D, E.R)) return rc;
+    const RangeParams P = E.R;
+    const size_t N = size_t(n), NS = N * size_t(top_n);
+    HIPC(c, d_top.reserve(3 * NS, 3 * NS));
+    HIPC(c, d_topu.reserve(2 * NS, 2 * NS));
+    HIPC(c, d_npres.reserve(N, N));
+    E.top_n = top_n; E.n_present = d_npres.p;
+    E.code = d_topu.p; E.count = d_topu.p + NS;
+    E.pw = d_top.p; E.pg = d_top.p + NS; E.term = d_top.p + 2 * NS;
+    // a slice entry is 12 bytes: a term and a 32-bit code.  The short form's slices, then the long form's
+    if (int rc = reserve_long_scratch(c, plan, size_t(plan.cap_long) * 12, wgs, stride)) return rc;
+    const size_t words_short = plan.n_short() ? size_t(plan.grid_short) * size_t(plan.cap_short) * 3 / 2 : 0;
+    const size_t words_long = plan.long_cap ? size_t(wgs) * size_t(plan.cap_long) * 3 / 2 : 0;
+    HIPC(c, d_stage.reserve(words_short + words_long + 1, words_short + words_long + 1));
+    HIPC(c, hipEventRecord(c->ev0, c->stream));
+    explain_fill_kernel<<<grid_for(int64_t(NS), 256, 4096), 256, 0, c->stream>>>(E, n);
+    HIPC(c, hipGetLastError());
+    if (plan.n_short()) {
+        const size_t lds = range_lds(c->kmin, c->kmax).total;
+        E.R = short_list(P, plan, D); E.cap = plan.cap_short; E.stage = d_stage.p;
+        HIPC(c, launch_with_lds(c, explain_short_kernel<true>, explain_short_kernel<false>, E, plan.grid_short, lds));
+    }
+    if (plan.long_cap) {
+        E.R = long_list(P, plan, D); E.cap = plan.cap_long; E.stage = d_stage.p + words_short;
+        explain_long_kernel<<<int(wgs), FRISK_RANGE_BIG_NT, 0, c->stream>>>(E, c->d_big.p, stride);
+        HIPC(c, hipGetLastError());
+    }
+    if (int rc = copy_back(c, A, P, 1)) return rc;
+    HIPC(c, hipMemcpyAsync(n_present, d_npres.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(code, E.code, NS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(count, E.count, NS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(pw, E.pw, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(pg, E.pg, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(term, E.term, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return finish_call(c, 7);
 }
 
 extern "C" int32_t frisk_panel_size(const frisk_ctx* c) { return c ? c->panel_n : 0; }

@@ -1,18 +1,19 @@
 // panel_kernels.h - frisk_score_ranges_panel: the rows of range_kernels.h against a PANEL of genome-side tables in one pass.  A
-// range is counted once - stages 1 and 2 are range_kernels.h's own (range_short_tables, range_long_tables) - and only stages
-// 3 + 4 are new: what a present max-mer takes from the range (W, A: eight prefix counts, the orphan lookup) is computed once, what
-// it takes from a profile (one genome-side value, a product, div_exact, log_pos, three exact additions) once per profile.
+// range is counted once - the forms and the row loop are range_kernels.h's own (ShortForm, LongForm, range_row_loop) - and only
+// stages 3 + 4, the two modes here, are new: what a present max-mer takes from the range (W, A: eight prefix counts, the orphan
+// lookup) is computed once, what it takes from a profile (one genome-side value, a product, div_exact, log_pos, three exact
+// additions) once per profile.
 //
 // Layout of the panel: tiles of FRISK_PANEL_TILE profiles, a tile = [code][FRISK_PANEL_TILE] doubles, so the values a lane needs
 // for one max-mer are 64 contiguous bytes.  A tile's unused slots hold 1.0 (never NaN); their sums are not written.  A panel of
 // more than one tile walks the range's order-K table once per tile.
 //
-// Short form (the geometry of range_short_kernel): the walk does not score.  A wave appends the codes of its share's non-empty bins
-// to a wave-private list in LDS - the position from ballots over the lanes, 16-bit codes - and whenever the list holds 64 or more
-// it scores 64 of them, one per lane, with every lane busy; the rest is flushed behind the walk.  (range_short_kernel scores inside
-// the walk: at K = 8 the FP64 body runs 128 times per range with a twelfth of its lanes active.)  No workgroup barrier inside the
-// walk.  Long form (range_long_kernel's): the profile loop over cnt[offK + code] != 0, FRISK_PANEL_TILE_LONG profiles at a time -
-// 1024 threads leave a lane 128 registers, and a profile's three ExactSums take 12.
+// Short form (PanelShortMode, the geometry of range_short_kernel): the walk does not score.  A wave appends the codes of its
+// share's non-empty bins to a wave-private list in LDS - the position from ballots over the lanes, 16-bit codes - and whenever the
+// list holds 64 or more it scores 64 of them, one per lane, with every lane busy; the rest is flushed behind the walk.  (PlainMode
+// scores inside the walk: at K = 8 the FP64 body runs 128 times per range with a twelfth of its lanes active.)  No workgroup
+// barrier inside the walk.  Long form (PanelLongMode): the profile loop inside the walk, FRISK_PANEL_TILE_LONG profiles at a time -
+// 1024 threads leave a lane 128 registers, and a profile's three ExactSums take 12.  The short form holds a tile's 24 in 196 VGPRs.
 //
 // Why plane p is bit for bit the single-profile row: ExactSum totals do not depend on which lane scored which max-mer
 // (scan_kernel.h, at FRISK_EXACT_BIAS), and every other operation on a max-mer is range_score_maxmer's, in its order
@@ -66,38 +67,20 @@ __device__ inline void panel_wave_order() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// ---- short form -------------------------------------------------------------------------------------------------------------
-template <bool K8>
-__global__ __launch_bounds__(FRISK_RANGE_NT) void panel_short_kernel(const PanelParams Q) {
-    constexpr int NT = FRISK_RANGE_NT, NW = NT / 64, TP = FRISK_PANEL_TILE;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ uint32_t tl[8];
-    __shared__ double red[TP * NW * 6];         // one slice per profile of the tile: its reductions need no barrier between them
-    const RangeParams& P = Q.R;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int kmin = P.kmin;
-    const int kmax = K8 ? 8 : P.kmax;
-    const RangeLds L = range_lds(kmin, kmax);
-    const uint32_t* t8 = reinterpret_cast<const uint32_t*>(lds);
-    const uint16_t* small16 = reinterpret_cast<const uint16_t*>(lds + L.small);
-    uint16_t* mylist = reinterpret_cast<uint16_t*>(lds + panel_lds_list(kmin, kmax)) + (tid >> 6) * FRISK_PANEL_LIST;
-    const uint32_t nK = 1u << (2 * kmax);
-    const uint32_t offK = K8 ? 0u : uint32_t(table_offset(kmin, kmax));
-
-    const int64_t n_rows = range_rows(P);
-    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t row = P.list[q];
-        WinTables<K8> T;
-        int64_t S;
-        uint32_t nvalid_top;
-        const int what = range_short_tables<K8>(P, row, lds, tl, T, S, nvalid_top);
-        if (what == RANGE_ROW_DROPPED && tid == 0) panel_write_unresolved(Q, row);
-        if (what != RANGE_ROW_SCORE) continue;
-        auto count = [&](int x, uint32_t c) -> uint32_t { return T.count(x, c); };
-        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
-        double r[FRISK_MAX_K + 1];
-        range_constants(S, r);
-
+// ---- the two scoring bodies -------------------------------------------------------------------------------------------------
+// (modes of range_row_loop; `red`: one slice of NW * 6 doubles per profile scored together - their reductions need no barrier
+// between them)
+struct PanelShortMode {
+    const PanelParams& Q;
+    double* red;
+    uint16_t* mylist;           // the wave's list
+    __device__ void dropped(int64_t row) const { if (threadIdx.x == 0) panel_write_unresolved(Q, row); }
+    template <bool K8>
+    __device__ void score(const ShortForm<K8>& form, int64_t row, uint32_t status, uint32_t nvalid_top, const double* r) const {
+        constexpr int NW = FRISK_RANGE_NT / 64, TP = FRISK_PANEL_TILE;
+        const int lane = threadIdx.x & 63;
+        const int kmin = form.kmin, kmax = form.kmax();
+        auto count = [&](int x, uint32_t c) -> uint32_t { return form.count(x, c); };
         for (int t0 = 0; t0 < Q.n_prof; t0 += TP) {
             const double* __restrict__ g = Q.tile[t0 / TP];
             ExactSum accw[TP], accg[TP], acct[TP];
@@ -128,62 +111,32 @@ __global__ __launch_bounds__(FRISK_RANGE_NT) void panel_short_kernel(const Panel
                 }
                 panel_wave_order();
             };
-            if (K8) {
-                for (uint32_t base = 0; base < nK / 8; base += NT) {        // eight bins per lane and step: at most 512 new entries
-                    const uint32_t grp = base + tid;
-                    const uint4 v = reinterpret_cast<const uint4*>(t8)[grp];
-                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int b = 0; b < 8; ++b) push(((w[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu) != 0u, 8 * grp + b);
-                    drain();
-                }
-            } else {
-                for (uint32_t base = 0; base < nK; base += NT) {            // one bin per lane and step
-                    const uint32_t code = base + tid;
-                    push(code < nK && small16[offK + (code < nK ? code : 0u)] != 0, code);
-                    drain();
-                }
-            }
+            form.walk(push, drain);             // a step appends at most 8 bins x 64 lanes to under 64 left over
             if (uint32_t(lane) < nlist) score(mylist[lane]);                // the remainder, under 64
             panel_wave_order();
 #pragma unroll
             for (int j = 0; j < TP; ++j)
                 if (t0 + j < Q.n_prof)
-                    range_finish<NW>(P, (t0 + j) * Q.plane + row, status, nvalid_top, accw[j], accg[j], acct[j], red + j * NW * 6);
+                    range_finish<NW>(Q.R, (t0 + j) * Q.plane + row, status, nvalid_top, accw[j], accg[j], acct[j], red + j * NW * 6);
         }
     }
-}
+};
 
-// ---- long form --------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void panel_long_kernel(const PanelParams Q, uint32_t* __restrict__ big, int64_t big_stride) {
-    constexpr int NT = FRISK_RANGE_BIG_NT, NW = NT / 64, TP = FRISK_PANEL_TILE, TL = FRISK_PANEL_TILE_LONG;
-    __shared__ uint32_t tl[8];
-    __shared__ double red[TL * NW * 6];
-    const RangeParams& P = Q.R;
-    const int tid = threadIdx.x;
-    const int kmin = P.kmin, kmax = P.kmax;
-    uint32_t* cnt = big + int64_t(blockIdx.x) * big_stride;
-    const int64_t offK = table_offset(kmin, kmax);
-    const uint32_t nK = 1u << (2 * kmax);
-    const int64_t n_rows = range_rows(P);
-    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t row = P.list[q];
-        int64_t S;
-        uint32_t nvalid_top;
-        const int what = range_long_tables(P, row, cnt, big_stride, tl, S, nvalid_top);
-        if (what == RANGE_ROW_DROPPED && tid == 0) panel_write_unresolved(Q, row);
-        if (what != RANGE_ROW_SCORE) continue;
-        auto count = [&](int x, uint32_t c) -> uint32_t { return cnt[table_offset(kmin, x) + c]; };
-        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
-        double r[FRISK_MAX_K + 1];
-        range_constants(S, r);
+struct PanelLongMode {
+    const PanelParams& Q;
+    double* red;
+    __device__ void dropped(int64_t row) const { if (threadIdx.x == 0) panel_write_unresolved(Q, row); }
+    __device__ void score(const LongForm& form, int64_t row, uint32_t status, uint32_t nvalid_top, const double* r) const {
+        constexpr int NW = FRISK_RANGE_BIG_NT / 64, TP = FRISK_PANEL_TILE, TL = FRISK_PANEL_TILE_LONG;
+        const int kmin = form.kmin, kmax = form.kmax();
+        auto count = [&](int x, uint32_t c) -> uint32_t { return form.count(x, c); };
         for (int t0 = 0; t0 < Q.n_prof; t0 += TL) {
             const double* __restrict__ g = Q.tile[t0 / TP] + (t0 % TP);
             ExactSum accw[TL], accg[TL], acct[TL];
 #pragma unroll
             for (int j = 0; j < TL; ++j) accw[j] = accg[j] = acct[j] = exact_begin();
-            for (uint32_t code = tid; code < nK; code += NT) {
-                if (cnt[offK + code] == 0) continue;
+            form.walk([&](bool present, uint32_t code) {
+                if (!present) return;
                 unsigned long long W;
                 double A;
                 range_maxmer_window(code, kmin, kmax, r, count, W, A);
@@ -191,12 +144,28 @@ __global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void panel_long_kernel(const Pa
                 const double* gv = g + size_t(code) * TP;
 #pragma unroll
                 for (int j = 0; j < TL; ++j) range_maxmer_add(A, Wd, gv[j], accw[j], accg[j], acct[j]);
-            }
+            });
 #pragma unroll
             for (int j = 0; j < TL; ++j)
                 if (t0 + j < Q.n_prof)
-                    range_finish<NW>(P, (t0 + j) * Q.plane + row, status, nvalid_top, accw[j], accg[j], acct[j], red + j * NW * 6);
+                    range_finish<NW>(Q.R, (t0 + j) * Q.plane + row, status, nvalid_top, accw[j], accg[j], acct[j], red + j * NW * 6);
         }
-        range_zero_tables(cnt, big_stride);     // (behind range_finish's barrier: every read of the tables is done)
     }
+};
+
+template <bool K8>
+__global__ __launch_bounds__(FRISK_RANGE_NT) void panel_short_kernel(const PanelParams Q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ uint32_t tl[8];
+    __shared__ double red[FRISK_PANEL_TILE * (FRISK_RANGE_NT / 64) * 6];
+    ShortForm<K8> form(Q.R, lds, tl);
+    uint16_t* mylist = reinterpret_cast<uint16_t*>(lds + panel_lds_list(form.kmin, form.kmax())) + (threadIdx.x >> 6) * FRISK_PANEL_LIST;
+    range_row_loop(Q.R, form, PanelShortMode{Q, red, mylist});
+}
+
+__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void panel_long_kernel(const PanelParams Q, uint32_t* __restrict__ big, int64_t big_stride) {
+    __shared__ uint32_t tl[8];
+    __shared__ double red[FRISK_PANEL_TILE_LONG * (FRISK_RANGE_BIG_NT / 64) * 6];
+    LongForm form(Q.R, big, big_stride, tl);
+    range_row_loop(Q.R, form, PanelLongMode{Q, red});
 }

@@ -18,17 +18,21 @@
 //   long   kmax >= 9, length > 65 535, handed-over ranges, FRISK_RANGES_BIG: 32-bit tables of all orders in a per-workgroup slice
 //          of global scratch, with scan_big_kernel.h's fences around the atomics and its zeroing behind each range.
 //
+// A FORM hides the table format (ShortForm<K8>, LongForm: NT, tables, count, walk, release).  A MODE is what is done with a row
+// whose tables are ready: PlainMode here scores inside the walk (at K = 8 in a loop of its own, see there); panel_kernels.h and
+// explain_kernels.h bring theirs.  The row loop (range_row_loop) is written once for every form and mode; a __global__ entry
+// point declares its LDS, makes a form and a mode and runs the loop.
+//
 // FP64 throughout, no MFMA, no floating-point atomics.
 #pragma once
 #include "scan_kernel.h"
+#include "range_plan.h"     // FRISK_RANGE_SHORT_MAX, FRISK_RANGE_HANDOVER_WGS: what the host decides
 
 #pragma clang fp contract(off)
 
 #define FRISK_RANGE_NT 512          // short form: threads per workgroup
 #define FRISK_RANGE_BIG_NT 1024     // long form
 #define FRISK_RANGE_ORPHANS 64      // short form, kmax = 8: entries of the orphan list in LDS
-#define FRISK_RANGE_SHORT_MAX 65535 // longest range of the short form (16-bit counters)
-#define FRISK_RANGE_HANDOVER_WGS 8   // long form: workgroups launched for the rows the short form may hand over
 
 struct RangeParams {
     const uint32_t* codes;
@@ -173,24 +177,36 @@ __device__ inline uint32_t range_status(uint32_t nvalid_top, int64_t S, int kmin
 // N rule drops it
 enum { RANGE_ROW_SCORE = 0, RANGE_ROW_HANDED = 1, RANGE_ROW_DROPPED = 2 };
 
+struct NoStep { __device__ void operator()() const {} };     // walk(f) without a per-step hook
+
 // ---- short form -------------------------------------------------------------------------------------------------------------
-// Stages 1 and 2 of one row, every thread of the workgroup: clear, count, composition, the N rule, marginalisation; gc / RIP / nn
-// of a kept row and every column of a dropped one are written here.  `tl`: 8 words of LDS.  Ends behind a barrier: the tables
-// (T) may be read.  Shared with panel_kernels.h.
 template <bool K8>
-__device__ inline int range_short_tables(const RangeParams& P, int64_t row, unsigned char* lds, uint32_t* tl, WinTables<K8>& T,
-                                         int64_t& S, uint32_t& nvalid_top) {
-    constexpr int NT = FRISK_RANGE_NT;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int kmin = P.kmin;
-    const int kmax = K8 ? 8 : P.kmax;
-    const int ks = K8 ? 6 : kmax;                       // highest order kept in the small tables
-    const RangeLds L = range_lds(kmin, kmax);
-    uint32_t* t8 = reinterpret_cast<uint32_t*>(lds);
-    uint32_t* small32 = reinterpret_cast<uint32_t*>(lds + L.small);
-    uint16_t* small16 = reinterpret_cast<uint16_t*>(lds + L.small);
-    uint16_t* orph = reinterpret_cast<uint16_t*>(lds + L.orphans);
-    {
+struct ShortForm {
+    static constexpr int NT = FRISK_RANGE_NT;
+    unsigned char* lds;         // range_lds(kmin, kmax)
+    uint32_t* tl;               // 8 words of LDS: [0..5] the row's counters, [7] the mode's
+    int kmin, kmax_;
+    WinTables<K8> T;
+
+    __device__ ShortForm(const RangeParams& P, unsigned char* lds_, uint32_t* tl_) : lds(lds_), tl(tl_), kmin(P.kmin), kmax_(P.kmax) {}
+    __device__ int kmax() const { return K8 ? 8 : kmax_; }
+    // occurrences of the x-mer c in the row
+    __device__ uint32_t count(int x, uint32_t c) const { return T.count(x, c); }
+
+    // Stages 1 and 2 of one row, every thread of the workgroup: clear, count, composition, the N rule, marginalisation; gc / RIP /
+    // nn of a kept row and every column of a dropped one are written here.  Ends behind a barrier: the tables may be read.
+    __device__ int tables(const RangeParams& P, int64_t row, int64_t& S, uint32_t& nvalid_top) {
+        const int tid = threadIdx.x, lane = tid & 63;
+        // the last row's view ends here: carried round the row loop it keeps scalar registers live through stage 1, and the
+        // scoring bodies then read spilled ones back (1 % of the short kernels' time, measured)
+        T = WinTables<K8>();
+        const int kmax = this->kmax();
+        const int ks = K8 ? 6 : kmax;                       // highest order kept in the small tables
+        const RangeLds L = range_lds(kmin, kmax);
+        uint32_t* t8 = reinterpret_cast<uint32_t*>(lds);
+        uint32_t* small32 = reinterpret_cast<uint32_t*>(lds + L.small);
+        uint16_t* small16 = reinterpret_cast<uint16_t*>(lds + L.small);
+        uint16_t* orph = reinterpret_cast<uint16_t*>(lds + L.orphans);
         const int64_t g0 = P.ranges[2 * row];
         const int n = int(P.ranges[2 * row + 1]);       // <= FRISK_RANGE_SHORT_MAX
         // ---- clear: 128 KiB over 512 threads is 16 uint4 stores each
@@ -279,61 +295,41 @@ __device__ inline int range_short_tables(const RangeParams& P, int64_t row, unsi
             if (n_orph > 3) T.o3 = orph[3];
         }
         T.kmin = kmin;
-        auto count = [&](int x, uint32_t c) -> uint32_t { return T.count(x, c); };
-        if (tid == 0) range_write_composition(P, row, S, upG + upC, nn, count);
+        if (tid == 0) range_write_composition(P, row, S, upG + upC, nn, [&](int x, uint32_t c) { return count(x, c); });
+        return RANGE_ROW_SCORE;
     }
-    return RANGE_ROW_SCORE;
-}
 
-template <bool K8>
-__global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const RangeParams P) {
-    constexpr int NT = FRISK_RANGE_NT, NW = NT / 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ uint32_t tl[8];
-    __shared__ double red[NW * 6];
-    const int tid = threadIdx.x;
-    const int kmin = P.kmin;
-    const int kmax = K8 ? 8 : P.kmax;
-    const RangeLds L = range_lds(kmin, kmax);
-    const uint32_t* t8 = reinterpret_cast<const uint32_t*>(lds);
-    const uint16_t* small16 = reinterpret_cast<const uint16_t*>(lds + L.small);
-    const uint32_t nK = 1u << (2 * kmax);
-
-    const int64_t n_rows = range_rows(P);
-    for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t row = P.list[q];
-        WinTables<K8> T;
-        int64_t S;
-        uint32_t nvalid_top;
-        if (range_short_tables<K8>(P, row, lds, tl, T, S, nvalid_top) != RANGE_ROW_SCORE) continue;
-        auto count = [&](int x, uint32_t c) -> uint32_t { return T.count(x, c); };
-        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
-
-        // ---- stages 3 + 4: every non-empty bin of the order-K table is a present max-mer
-        double r[FRISK_MAX_K + 1];
-        range_constants(S, r);
-        ExactSum accw = exact_begin(), accg = exact_begin(), acct = exact_begin();
+    // f(present, code) for every bin of the order-K table, step() behind each step of the workgroup over it.  Every lane of a
+    // wave is in every call of f; a step whose bins are empty in the whole wave is skipped (wave-uniform), step() with it.  No
+    // workgroup barrier.
+    template <typename F, typename STEP = NoStep>
+    __device__ void walk(F&& f, STEP&& step = STEP()) const {
+        const uint32_t tid = threadIdx.x;
+        const uint32_t nK = 1u << (2 * kmax());
         if (K8) {
-            for (uint32_t grp = tid; grp < nK / 8; grp += NT) {             // eight bins per read
-                const uint4 v = reinterpret_cast<const uint4*>(t8)[grp];
-                if ((v.x | v.y | v.z | v.w) == 0u) continue;
+            const uint4* t8 = reinterpret_cast<const uint4*>(lds);
+            for (uint32_t base = 0; base < nK / 8; base += NT) {            // eight bins per read; nK / 8 is a multiple of NT
+                const uint32_t grp = base + tid;
+                const uint4 v = t8[grp];
+                if (__ballot((v.x | v.y | v.z | v.w) != 0u) == 0ull) continue;
                 const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-                for (int b = 0; b < 8; ++b) {
-                    if (((w[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu) == 0u) continue;
-                    range_score_maxmer(8 * grp + b, kmin, kmax, r, P.ig, count, accw, accg, acct);
-                }
+                for (int b = 0; b < 8; ++b) f(((w[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu) != 0u, 8 * grp + b);
+                step();
             }
         } else {
-            const uint32_t offK = uint32_t(table_offset(kmin, kmax));
-            for (uint32_t code = tid; code < nK; code += NT) {
-                if (small16[offK + code] == 0) continue;
-                range_score_maxmer(code, kmin, kmax, r, P.ig, count, accw, accg, acct);
+            const uint16_t* top = T.small16 + uint32_t(table_offset(kmin, kmax()));
+            for (uint32_t base = 0; base < nK; base += NT) {                // one bin per lane and step
+                const uint32_t code = base + tid;
+                f(code < nK && top[code < nK ? code : 0u] != 0, code);
+                step();
             }
         }
-        range_finish<NW>(P, row, status, nvalid_top, accw, accg, acct, red);
     }
-}
+
+    // the tables are cleared at the head of the next row
+    __device__ void release() const {}
+};
 
 // ---- long form --------------------------------------------------------------------------------------------------------------
 // `big`: one slice of `big_stride` 32-bit words per workgroup, all-zero at launch and between ranges
@@ -343,14 +339,23 @@ __device__ inline void range_zero_tables(uint32_t* cnt, int64_t big_stride) {
     __threadfence();
 }
 
-// Stages 1 and 2 of one row on the workgroup's slice `cnt`, as range_short_tables; a dropped row's slice is zeroed again here, a
-// scored row's by the caller behind its last read.  Shared with panel_kernels.h.
-__device__ inline int range_long_tables(const RangeParams& P, int64_t row, uint32_t* cnt, int64_t big_stride, uint32_t* tl, int64_t& S,
-                                        uint32_t& nvalid_top) {
-    constexpr int NT = FRISK_RANGE_BIG_NT;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int kmin = P.kmin, kmax = P.kmax;
-    {
+struct LongForm {
+    static constexpr int NT = FRISK_RANGE_BIG_NT;
+    uint32_t* cnt;              // the workgroup's slice
+    int64_t big_stride;
+    uint32_t* tl;               // 8 words of LDS: [0..4] the row's counters, [7] the mode's
+    int kmin, kmax_;
+
+    __device__ LongForm(const RangeParams& P, uint32_t* big, int64_t big_stride_, uint32_t* tl_)
+        : cnt(big + int64_t(blockIdx.x) * big_stride_), big_stride(big_stride_), tl(tl_), kmin(P.kmin), kmax_(P.kmax) {}
+    __device__ int kmax() const { return kmax_; }
+    __device__ uint32_t count(int x, uint32_t c) const { return cnt[table_offset(kmin, x) + c]; }
+
+    // Stages 1 and 2 of one row on the workgroup's slice, as ShortForm::tables; a dropped row's slice is zeroed again here, a
+    // scored row's by release() behind its last read.
+    __device__ int tables(const RangeParams& P, int64_t row, int64_t& S, uint32_t& nvalid_top) {
+        const int kmax = this->kmax();
+        const int tid = threadIdx.x, lane = tid & 63;
         const int64_t g0 = P.ranges[2 * row], n = P.ranges[2 * row + 1];
         if (tid < 8) tl[tid] = 0;
         __syncthreads();
@@ -407,37 +412,95 @@ __device__ inline int range_long_tables(const RangeParams& P, int64_t row, uint3
             }
             __syncthreads();
         }
-        auto count = [&](int x, uint32_t c) -> uint32_t { return cnt[table_offset(kmin, x) + c]; };
-        if (tid == 0) range_write_composition(P, row, S, upG + upC, nn, count);
+        if (tid == 0) range_write_composition(P, row, S, upG + upC, nn, [&](int x, uint32_t c) { return count(x, c); });
+        return RANGE_ROW_SCORE;
     }
-    return RANGE_ROW_SCORE;
-}
 
-__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void range_long_kernel(const RangeParams P, uint32_t* __restrict__ big, int64_t big_stride) {
-    constexpr int NT = FRISK_RANGE_BIG_NT, NW = NT / 64;
-    __shared__ uint32_t tl[8];
-    __shared__ double red[NW * 6];
-    const int tid = threadIdx.x;
-    const int kmin = P.kmin, kmax = P.kmax;
-    uint32_t* cnt = big + int64_t(blockIdx.x) * big_stride;
-    const int64_t offK = table_offset(kmin, kmax);
-    const uint32_t nK = 1u << (2 * kmax);
+    // as ShortForm::walk, one bin per lane and step
+    template <typename F, typename STEP = NoStep>
+    __device__ void walk(F&& f, STEP&& step = STEP()) const {
+        const uint32_t nK = 1u << (2 * kmax());
+        const uint32_t* top = cnt + table_offset(kmin, kmax());
+        for (uint32_t base = 0; base < nK; base += NT) {
+            const uint32_t code = base + threadIdx.x;
+            f(code < nK && top[code < nK ? code : 0u] != 0u, code);
+            step();
+        }
+    }
+
+    // behind a barrier: every read of the row's tables is done
+    __device__ void release() const { range_zero_tables(cnt, big_stride); }
+};
+
+// ---- the row loop -----------------------------------------------------------------------------------------------------------
+// Every row of the launch's list that falls to this workgroup: the form's tables, then the mode.  mode.dropped(row): a row the N
+// rule drops, behind range_write_unresolved.  mode.score(form, row, status, nvalid_top, r): a row whose tables are ready; every
+// thread calls, and it ends behind a barrier after its last read of the tables (range_finish's, or a later one) - release()
+// follows.  Every branch here is on a workgroup-uniform scalar: the loop's bounds and what tables() returns.
+template <typename FORM, typename MODE>
+__device__ inline void range_row_loop(const RangeParams& P, FORM& form, MODE&& mode) {
     const int64_t n_rows = range_rows(P);
     for (int64_t q = blockIdx.x; q < n_rows; q += gridDim.x) {
         const int64_t row = P.list[q];
         int64_t S;
         uint32_t nvalid_top;
-        if (range_long_tables(P, row, cnt, big_stride, tl, S, nvalid_top) != RANGE_ROW_SCORE) continue;
-        auto count = [&](int x, uint32_t c) -> uint32_t { return cnt[table_offset(kmin, x) + c]; };
-        const uint32_t status = range_status(nvalid_top, S, kmin, kmax);
+        const int what = form.tables(P, row, S, nvalid_top);
+        if (what == RANGE_ROW_DROPPED) mode.dropped(row);
+        if (what != RANGE_ROW_SCORE) continue;
+        const uint32_t status = range_status(nvalid_top, S, form.kmin, form.kmax());
         double r[FRISK_MAX_K + 1];
         range_constants(S, r);
-        ExactSum accw = exact_begin(), accg = exact_begin(), acct = exact_begin();
-        for (uint32_t code = tid; code < nK; code += NT) {
-            if (cnt[offK + code] == 0) continue;
-            range_score_maxmer(code, kmin, kmax, r, P.ig, count, accw, accg, acct);
-        }
-        range_finish<NW>(P, row, status, nvalid_top, accw, accg, acct, red);    // (its barrier: every read of the tables is done)
-        range_zero_tables(cnt, big_stride);
+        mode.score(form, row, status, nvalid_top, r);
+        form.release();
     }
+}
+
+// stages 3 + 4 of frisk_score_ranges: every non-empty bin of the order-K table is a present max-mer, scored inside the walk
+struct PlainMode {
+    const RangeParams& P;
+    double* red;                // FORM::NT / 64 * 6 doubles of LDS
+    __device__ void dropped(int64_t) const {}
+    template <typename FORM>
+    __device__ void score(const FORM& form, int64_t row, uint32_t status, uint32_t nvalid_top, const double* r) const {
+        auto count = [&](int x, uint32_t c) -> uint32_t { return form.count(x, c); };
+        ExactSum accw = exact_begin(), accg = exact_begin(), acct = exact_begin();
+        if constexpr (std::is_same<FORM, ShortForm<true>>::value) {
+            // Not through walk(), which is the same walk: with the scoring body handed to it as a lambda the K = 8 grid and
+            // mixed workloads of tools/ranges_timing.py run 4 % longer (measured against this loop).  What the compiler is seen
+            // to do differently there: a max-mer's six prefix-table addresses are formed in front of each of their loads, once
+            // per bin, where this loop forms them once per group of eight.
+            const uint4* t8 = reinterpret_cast<const uint4*>(form.lds);
+            for (uint32_t grp = threadIdx.x; grp < (1u << 16) / 8; grp += FORM::NT) {       // eight bins per read
+                const uint4 v = t8[grp];
+                if ((v.x | v.y | v.z | v.w) == 0u) continue;
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    if (((w[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu) == 0u) continue;
+                    range_score_maxmer(8 * grp + b, form.kmin, 8, r, P.ig, count, accw, accg, acct);
+                }
+            }
+        } else {
+            form.walk([&](bool present, uint32_t code) {
+                if (present) range_score_maxmer(code, form.kmin, form.kmax(), r, P.ig, count, accw, accg, acct);
+            });
+        }
+        range_finish<FORM::NT / 64>(P, row, status, nvalid_top, accw, accg, acct, red);
+    }
+};
+
+template <bool K8>
+__global__ __launch_bounds__(FRISK_RANGE_NT) void range_short_kernel(const RangeParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ uint32_t tl[8];
+    __shared__ double red[FRISK_RANGE_NT / 64 * 6];
+    ShortForm<K8> form(P, lds, tl);
+    range_row_loop(P, form, PlainMode{P, red});
+}
+
+__global__ __launch_bounds__(FRISK_RANGE_BIG_NT) void range_long_kernel(const RangeParams P, uint32_t* __restrict__ big, int64_t big_stride) {
+    __shared__ uint32_t tl[8];
+    __shared__ double red[FRISK_RANGE_BIG_NT / 64 * 6];
+    LongForm form(P, big, big_stride, tl);
+    range_row_loop(P, form, PlainMode{P, red});
 }

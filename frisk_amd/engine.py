@@ -372,12 +372,8 @@ class Engine:
         the engine's own) of bases [start[r], stop[r]) - 0-based, half-open - of resident scaffold seq_index[r]; nn[r] = its
         positions that are not uppercase A/T/G/C; status[r] & _ffi.KVEC_EMPTY_ORDER: the range holds no valid word of some order.
         batch_rows > 0 forces that many rows per launch (0: the library's default)."""
-        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
-        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
-        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        seq_index, start, stop = self._range_rows(seq_index, start, stop)
         n = int(seq_index.size)
-        if start.size != n or stop.size != n:
-            raise ValueError("seq_index, start and stop must have one entry per range")
         f = sum((4 ** x + (2 ** x if x % 2 == 0 else 0)) // 2 for x in range(int(kmin), int(kmax) + 1)) if 1 <= kmin <= kmax else 0
         X, nn, status = np.empty((n, f), np.float64), np.empty(n, np.int64), np.empty(n, np.uint32)
         self._check(self._lib.frisk_window_vectors(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, int(kmin), int(kmax),
@@ -556,22 +552,33 @@ class Engine:
         self._check(self._lib.frisk_scan_ivom(self._ctx, int(w), int(inc), flags, int(c0), int(c1), max(n, 1), _ptr(wi), _ptr(gi)))
         return wi[:n], gi[:n]
 
+    # the region calls (csrc/frisk_ranges.hip): their three row arrays as the library reads them, and their score columns
+    @staticmethod
+    def _range_rows(seq_index, start, stop):
+        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
+        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
+        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        if start.size != seq_index.size or stop.size != seq_index.size:
+            raise ValueError("seq_index, start and stop must have one entry per range")
+        return seq_index, start, stop
+
+    @staticmethod
+    def _score_columns(n, rip, planes=None):
+        """status, kld, gc, pi / si / cri (None without rip) and nn of n ranges; status and kld of shape (planes, n) for a panel."""
+        new = lambda dt: np.zeros(n, dt)                                   # noqa: E731
+        per_profile = new if planes is None else (lambda dt: np.zeros((planes, n), dt))
+        return dict(status=per_profile(np.uint32), kld=per_profile(np.float64), gc=new(np.float64), pi=new(np.float64) if rip else None,
+                    si=new(np.float64) if rip else None, cri=new(np.float64) if rip else None, nn=new(np.int64))
+
     def score_ranges(self, seq_index, start, stop, rip=False, big=False):
         """frisk_score_ranges: the scan loop's columns of bases [start[r], stop[r]) - 0-based, half-open - of resident scaffold
         seq_index[r], each range scored as the slice it is against the finalised profile.  Returns a ScanResult with seq_index,
         start, stop (as given), status, kld, gc, pi / si / cri (None without rip) and nn (positions that are not uppercase
         A/C/G/T); `kept` is False for a range the N filter drops.  big=True (test hook): every range through the global-scratch
         form - the same bits."""
-        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
-        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
-        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        seq_index, start, stop = self._range_rows(seq_index, start, stop)
         n = int(seq_index.size)
-        if start.size != n or stop.size != n:
-            raise ValueError("seq_index, start and stop must have one entry per range")
-        new = lambda dt: np.zeros(n, dt)                                   # noqa: E731
-        r = ScanResult(seq_index=seq_index, start=start, stop=stop, status=new(np.uint32), kld=new(np.float64), gc=new(np.float64),
-                       pi=new(np.float64) if rip else None, si=new(np.float64) if rip else None,
-                       cri=new(np.float64) if rip else None, nn=new(np.int64))
+        r = ScanResult(seq_index=seq_index, start=start, stop=stop, **self._score_columns(n, rip))
         flags = (_ffi.SCAN_RIP if rip else 0) | (_ffi.RANGES_BIG if big else 0)
         self._check(self._lib.frisk_score_ranges(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, flags, _ptr(r.status),
                                                  _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn)))
@@ -597,17 +604,9 @@ class Engine:
         """frisk_score_ranges_panel: score_ranges against every profile of the panel in one pass - each range is counted once.
         Returns a PanelResult: status and kld of shape (P, n), plane p bit for bit the score_ranges rows under profile p; gc,
         pi / si / cri (None without rip), nn, seq_index, start, stop as in score_ranges (they do not depend on the profile)."""
-        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
-        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
-        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        seq_index, start, stop = self._range_rows(seq_index, start, stop)
         n = int(seq_index.size)
-        if start.size != n or stop.size != n:
-            raise ValueError("seq_index, start and stop must have one entry per range")
-        planes = self.panel_size
-        new = lambda dt: np.zeros(n, dt)                                   # noqa: E731
-        r = PanelResult(seq_index=seq_index, start=start, stop=stop, status=np.zeros((planes, n), np.uint32),
-                        kld=np.zeros((planes, n), np.float64), gc=new(np.float64), pi=new(np.float64) if rip else None,
-                        si=new(np.float64) if rip else None, cri=new(np.float64) if rip else None, nn=new(np.int64))
+        r = PanelResult(seq_index=seq_index, start=start, stop=stop, **self._score_columns(n, rip, planes=self.panel_size))
         flags = (_ffi.SCAN_RIP if rip else 0) | (_ffi.RANGES_BIG if big else 0)
         self._check(self._lib.frisk_score_ranges_panel(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, flags, _ptr(r.status),
                                                        _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn)))
@@ -619,20 +618,13 @@ class Engine:
         count, pw, pg, term of shape (n, top_n): column j is rank j, rank 0 the largest term, equal terms by ascending code.  A slot
         is filled only for a range whose status is exactly ROW_KEPT and for j < min(top_n, n_present); every other slot holds code
         EXPLAIN_NONE, count 0 and NaN.  top_n: 1 .. EXPLAIN_MAX."""
-        seq_index = np.ascontiguousarray(seq_index, dtype=np.int32).ravel()
-        start = np.ascontiguousarray(start, dtype=np.int64).ravel()
-        stop = np.ascontiguousarray(stop, dtype=np.int64).ravel()
+        seq_index, start, stop = self._range_rows(seq_index, start, stop)
         n = int(seq_index.size)
-        if start.size != n or stop.size != n:
-            raise ValueError("seq_index, start and stop must have one entry per range")
         top_n = int(top_n)
         width = min(max(top_n, 1), _ffi.EXPLAIN_MAX)       # (a refused top_n: the library says so, nothing is written)
-        new = lambda dt: np.zeros(n, dt)                                   # noqa: E731
         top = lambda dt: np.zeros((n, width), dt)                          # noqa: E731
-        r = ScanResult(seq_index=seq_index, start=start, stop=stop, status=new(np.uint32), kld=new(np.float64), gc=new(np.float64),
-                       pi=new(np.float64) if rip else None, si=new(np.float64) if rip else None,
-                       cri=new(np.float64) if rip else None, nn=new(np.int64), n_present=new(np.int32), code=top(np.uint32),
-                       count=top(np.uint32), pw=top(np.float64), pg=top(np.float64), term=top(np.float64))
+        r = ScanResult(seq_index=seq_index, start=start, stop=stop, n_present=np.zeros(n, np.int32), code=top(np.uint32),
+                       count=top(np.uint32), pw=top(np.float64), pg=top(np.float64), term=top(np.float64), **self._score_columns(n, rip))
         flags = (_ffi.SCAN_RIP if rip else 0) | (_ffi.RANGES_BIG if big else 0)
         self._check(self._lib.frisk_explain_ranges(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, flags, top_n, _ptr(r.status),
                                                    _ptr(r.kld), _ptr(r.gc), _ptr(r.pi), _ptr(r.si), _ptr(r.cri), _ptr(r.nn),

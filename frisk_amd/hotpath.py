@@ -286,16 +286,21 @@ class HotPath:
             raise err
         return table, res
 
+    def _installProfile(self, args, genomeKmers):
+        """The host profile of a region call: installed from `genomeKmers` (the pickled form) or, without it, computed from
+        args.hostSeq."""
+        if genomeKmers is not None:
+            self.setGenomeProfile(genomeKmers)
+        else:
+            self.genomeProfileArrays(args)
+
     def scoreRegions(self, args, querySeq, regions, genomeKmers=None):
         """The loop body L1478-1494 on arbitrary regions instead of the window grid: `regions` = (scaffold name, start, stop)
         records, 0-based and half-open, each scored as the slice it is (Engine.score_ranges).  The profile is installed from
         `genomeKmers` (the pickled form) or, without it, computed from args.hostSeq; then `querySeq` is made resident by the
         native reader.  Returns the ScanResult, rows in the order of `regions`.  A record that names an unknown scaffold or
         reaches past its end raises ValueError naming the record - it is not clipped."""
-        if genomeKmers is not None:
-            self.setGenomeProfile(genomeKmers)
-        else:
-            self.genomeProfileArrays(args)
+        self._installProfile(args, genomeKmers)
         seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
         return self.engine.score_ranges(seq, start, stop, rip=rip)
 
@@ -303,10 +308,7 @@ class HotPath:
         """scoreRegions, and for every region the top_n max-mers with the largest summands of its KLD (Engine.explain_ranges: one
         device call, the score columns bit for bit scoreRegions').  Returns the ScanResult with n_present, code, count, pw, pg and
         term beside the score columns."""
-        if genomeKmers is not None:
-            self.setGenomeProfile(genomeKmers)
-        else:
-            self.genomeProfileArrays(args)
+        self._installProfile(args, genomeKmers)
         seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
         return self.engine.explain_ranges(seq, start, stop, top_n, rip=rip)
 

@@ -266,6 +266,13 @@ def kmer_rows(regions, res, k, fmt):
                              fmt(int(res.count[r][j])), fmt(float(res.pw[r][j])), fmt(float(res.pg[r][j])), fmt(term), share]) + "\n"
 
 
+def write_table(path, columns, rows=()):
+    """A table of the command line: the header, then the rows' lines."""
+    with open(path, "w") as fh:
+        fh.write("\t".join(columns) + "\n")
+        fh.writelines(rows)
+
+
 def _load_pickle(path, log):
     log.info("Importing previously calculated genome kmers from %s", path)
     with open(path, "rb") as fh:
@@ -312,8 +319,9 @@ def main(argv=None):
     if args.gffFeatures and not args.gff:
         logging.error("[ERROR] --gffFeatures goes with --gff\n")
         return 1
-    if args.topKmers is not None and kmers_problem(args):
-        logging.error("[ERROR] %s\n", kmers_problem(args))
+    problem = kmers_problem(args) if args.topKmers is not None else None
+    if problem:
+        logging.error("[ERROR] %s\n", problem)
         return 1
     labels = [os.path.basename(p) for p in [args.hostSeq] + list(args.donors or [])]
     if len(set(labels)) != len(labels):
@@ -325,26 +333,23 @@ def main(argv=None):
     except (OSError, ValueError) as err:
         logging.error("[ERROR] %s\n", err)
         return 1
-    if args.null and null_problem(args, regions):
-        logging.error("[ERROR] %s\n", null_problem(args, regions))
+    problem = null_problem(args, regions) if args.null else None
+    if problem:
+        logging.error("[ERROR] %s\n", problem)
         return 1
     rip = bool(args.RIP) and args.minWordSize <= 2
     if not os.path.isdir(os.path.abspath(args.tempDir)):
         os.makedirs(os.path.abspath(args.tempDir))
-    out_path = os.path.join(args.tempDir, args.outfile)
-    header = "\t".join(columns(rip)) + "\n"
+    out_path, kmer_path, null_path, donor_path = (os.path.join(args.tempDir, f) for f in (args.outfile, args.kmerOutfile, args.nullOutfile,
+                                                                                         args.donorOutfile))
     if not regions:
-        with open(out_path, "w") as fh:
-            fh.write(header)
+        write_table(out_path, columns(rip))
         if args.donors:
-            with open(os.path.join(args.tempDir, args.donorOutfile), "w") as fh:
-                fh.write("\t".join(donor_columns(labels)) + "\n")
+            write_table(donor_path, donor_columns(labels))
         if args.null:
-            with open(os.path.join(args.tempDir, args.nullOutfile), "w") as fh:
-                fh.write("\t".join(NULL_COLUMNS) + "\n")
+            write_table(null_path, NULL_COLUMNS)
         if args.topKmers is not None:
-            with open(os.path.join(args.tempDir, args.kmerOutfile), "w") as fh:
-                fh.write("\t".join(KMER_COLUMNS) + "\n")
+            write_table(kmer_path, KMER_COLUMNS)
         log.info("No regions in %s: wrote the header to %s", args.bed or args.gff, out_path)
         return 0
 
@@ -379,27 +384,16 @@ def main(argv=None):
             null_kld, null_valid = hp.nullScores(args, lengths, args.nullDraws, args.seed, args.null, order=args.nullOrder)
     finally:
         hp.close()
-    with open(out_path, "w") as fh:
-        fh.write(header)
-        fh.writelines(region_rows(regions, res, rip, cli._fmt()))
+    write_table(out_path, columns(rip), region_rows(regions, res, rip, cli._fmt()))
     log.info("Scored %d regions: %s", len(regions), out_path)
     if args.topKmers is not None:
-        kmer_path = os.path.join(args.tempDir, args.kmerOutfile)
-        with open(kmer_path, "w") as fh:
-            fh.write("\t".join(KMER_COLUMNS) + "\n")
-            fh.writelines(kmer_rows(regions, res, args.maxWordSize, cli._fmt()))
+        write_table(kmer_path, KMER_COLUMNS, kmer_rows(regions, res, args.maxWordSize, cli._fmt()))
         log.info("Listed the %d largest KLD terms of each: %s", args.topKmers, kmer_path)
     if args.null:
-        null_path = os.path.join(args.tempDir, args.nullOutfile)
-        with open(null_path, "w") as fh:
-            fh.write("\t".join(NULL_COLUMNS) + "\n")
-            fh.writelines(null_rows(regions, res, lengths, null_kld, null_valid, cli._fmt()))
+        write_table(null_path, NULL_COLUMNS, null_rows(regions, res, lengths, null_kld, null_valid, cli._fmt()))
         log.info("Placed them in %s nulls of %d draws per length (%d lengths): %s", args.null, args.nullDraws, len(lengths), null_path)
     if panel is not None:
-        donor_path = os.path.join(args.tempDir, args.donorOutfile)
-        with open(donor_path, "w") as fh:
-            fh.write("\t".join(donor_columns(labels)) + "\n")
-            fh.writelines(donor_rows(regions, panel, planes, labels, cli._fmt()))
+        write_table(donor_path, donor_columns(labels), donor_rows(regions, panel, planes, labels, cli._fmt()))
         log.info("Scored them against %d donor genomes: %s", len(args.donors), donor_path)
     return 0
 

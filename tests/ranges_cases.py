@@ -98,6 +98,36 @@ def expected(kmin, kmax):
     return rows, expect_rows(scaffolds(), profile(kmin, kmax), _ig(kmin, kmax), rows, kmin, kmax)
 
 
+OWN = object()          # engine(): this module's scaffolds / their profile
+
+
+def engine(kmin, kmax, seqs=OWN, prof=OWN):
+    """An Engine with `seqs` resident (default: scaffolds(); None: no batch) and the profile `prof` = (sym, meta) installed (default:
+    profile(kmin, kmax); None: no profile)."""
+    from frisk_amd.engine import Engine
+    e = Engine(kmin, kmax)
+    if seqs is not None:
+        e.load(scaffolds() if seqs is OWN else seqs)
+    if prof is not None:
+        sym, meta = profile(kmin, kmax) if prof is OWN else prof
+        e.profile_set(sym, *[int(v) for v in meta])
+    return e
+
+
+def score_columns(rip):
+    return ["status", "nn", "kld", "gc"] + (["pi", "si", "cri"] if rip else [])
+
+
+def same_columns(a, b, cols, ia=None, ib=None, what=""):
+    """Asserts that the columns `cols` of two results hold the same bytes (rows ia of a against rows ib of b); returns True."""
+    for c in cols:
+        x, y = getattr(a, c), getattr(b, c)
+        x = x if ia is None else x[ia]
+        y = y if ib is None else y[ib]
+        assert np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes(), (what, c)
+    return True
+
+
 def classes(exp):
     """(dropped by the N rule, without a max-mer, ZeroDivisionError, degenerate) counts of oracle rows."""
     return (sum(e["status"] == 0 for e in exp), sum(e["flag"] == H.NO_MAXMER for e in exp),

@@ -21,26 +21,11 @@ TOP = ["n_present", "code", "count", "pw", "pg", "term"]
 NONE = 0xFFFFFFFF
 
 
-def _engine(kmin, kmax):
-    from frisk_amd.engine import Engine
-    e = Engine(kmin, kmax)
-    e.load(R.scaffolds())
-    sym, meta = R.profile(kmin, kmax)
-    e.profile_set(sym, *[int(v) for v in meta])
-    return e
-
-
 def _cols(rip):
     return SCORE + (["pi", "si", "cri"] if rip else []) + TOP          # thirteen with rip
 
 
-def _same(a, b, cols, ia=None, ib=None):
-    for c in cols:
-        x, y = getattr(a, c), getattr(b, c)
-        x = x if ia is None else x[ia]
-        y = y if ib is None else y[ib]
-        assert np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes(), c
-    return True
+_same = R.same_columns
 
 
 def _empty(res, r, j0=0):
@@ -110,7 +95,7 @@ CASES = [(kmin, kmax, 64) for kmin, kmax in R.ORDERS + [(1, 3), (2, 2)]] + [(1, 
 def test_range_set_against_the_per_kmer_oracle(kmin, kmax, top_n, big):
     rows, exp = X.expected(kmin, kmax)
     rip = kmin <= 2 <= kmax
-    with _engine(kmin, kmax) as e:
+    with R.engine(kmin, kmax) as e:
         res = e.explain_ranges(*R.arrays(rows), top_n, rip=rip, big=big)
         ms = e.kernel_ms(7)
         score = e.score_ranges(*R.arrays(rows), rip=rip, big=big)
@@ -138,7 +123,7 @@ def test_orphan_hand_over_gives_the_same_bytes():
     rows = [(2, 0, 640), (2, 0, 650), (2, 0, 65535), (2, 10, 650), (0, 100, 700)]
     exp = X.explain_rows(R.scaffolds(), R.profile(1, 8), rows, 1, 8)
     assert all(x is not None and x["flag"] == H.OK for x in exp)
-    with _engine(1, 8) as e:
+    with R.engine(1, 8) as e:
         auto = e.explain_ranges(*R.arrays(rows), 64, rip=True)
         big = e.explain_ranges(*R.arrays(rows), 64, rip=True, big=True)
     check_explain("explain orphan hand-over", auto, exp, 8, 64)
@@ -152,7 +137,7 @@ def test_rows_do_not_depend_on_the_call(kmin, kmax):
     rows, _ = X.expected(kmin, kmax)
     s, a, b = R.arrays(rows)
     n, top_n, cols = len(rows), 16, _cols(True)
-    with _engine(kmin, kmax) as e:
+    with R.engine(kmin, kmax) as e:
         scan0 = e.scan(5000, 1000, rip=True)
         score0 = e.score_ranges(s, a, b, rip=True)
         first = e.explain_ranges(s, a, b, top_n, rip=True)

@@ -56,10 +56,7 @@ def _profile(kmin, kmax, which):
 
 
 def _engine(kmin, kmax, prof):
-    from frisk_amd.engine import Engine
-    e = Engine(kmin, kmax)
-    e.profile_set(prof[0], *[int(v) for v in prof[1]])
-    return e
+    return R.engine(kmin, kmax, seqs=None, prof=prof)
 
 
 def _batch(e):
@@ -102,8 +99,7 @@ def test_purity_and_reproducibility():
 
 
 # ------------------------------------------------------------------------------------------------------------------- state
-def _same(a, b, cols):
-    return all(getattr(a, c).tobytes() == getattr(b, c).tobytes() for c in cols)
+_same = R.same_columns
 
 
 def test_the_call_leaves_profile_panel_and_rows_alone():

@@ -21,19 +21,11 @@ SCAN_COLS = ("seq_index", "start", "stop", "status", "kld", "gc", "pi", "si", "c
 
 
 def _engine(kmin, kmax):
-    from frisk_amd.engine import Engine
-    e = Engine(kmin, kmax)
-    e.load(R.scaffolds())
-    return e
-
-
-def _cols(res, rip):
-    return [c for c in COLS if rip or c not in ("pi", "si", "cri")]
+    return R.engine(kmin, kmax, prof=None)
 
 
 def _same(a, b, rip, what=""):
-    for c in _cols(a, rip):
-        assert getattr(a, c).tobytes() == getattr(b, c).tobytes(), (what, c)
+    R.same_columns(a, b, R.score_columns(rip), what=what)
 
 
 def _singles(e, profs, s, a, b, rip, big=False):
@@ -106,8 +98,7 @@ def _take(res, idx):
 
 
 def _same_panel(a, b, what=""):
-    for c in COLS:
-        assert np.ascontiguousarray(getattr(a, c)).tobytes() == np.ascontiguousarray(getattr(b, c)).tobytes(), (what, c)
+    R.same_columns(a, b, COLS, what=what)
 
 
 @pytest.mark.parametrize("kmin,kmax", [(1, 8), (2, 9)])

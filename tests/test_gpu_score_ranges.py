@@ -16,18 +16,8 @@ from oracle import frisk_oracle_np as N
 pytestmark = pytest.mark.gpu
 
 
-def _engine(kmin, kmax, seqs=None, prof=None):
-    from frisk_amd.engine import Engine
-    e = Engine(kmin, kmax)
-    e.load(R.scaffolds() if seqs is None else seqs)
-    sym, meta = R.profile(kmin, kmax) if prof is None else prof
-    e.profile_set(sym, *[int(v) for v in meta])
-    return e
-
-
 def _same_rows(a, b, rip):
-    cols = ["status", "nn", "kld", "gc"] + (["pi", "si", "cri"] if rip else [])
-    return all(getattr(a, c).tobytes() == getattr(b, c).tobytes() for c in cols)
+    return R.same_columns(a, b, R.score_columns(rip))
 
 
 def _take(res, idx, rip):
@@ -43,7 +33,7 @@ def _take(res, idx, rip):
 def test_range_set_against_the_oracles(kmin, kmax, big):
     rows, exp = R.expected(kmin, kmax)
     rip = kmin <= 2 <= kmax
-    with _engine(kmin, kmax) as e:
+    with R.engine(kmin, kmax) as e:
         res = e.score_ranges(*R.arrays(rows), rip=rip, big=big)
         ms = e.kernel_ms(4)
     assert ms > 0.0
@@ -57,7 +47,7 @@ def test_one_range_at_k10():
     ig = N.genome_ivom_table(prof[0], prof[1], 1, 10)
     exp = R.expect_rows(R.scaffolds(), prof, ig, rows, 1, 10)
     assert exp[0]["flag"] == H.OK
-    with _engine(1, 10, prof=prof) as e:
+    with R.engine(1, 10, prof=prof) as e:
         R.check("ranges k=1..10", e.score_ranges(*R.arrays(rows), rip=True), exp)
         R.check("ranges k=1..10 big", e.score_ranges(*R.arrays(rows), rip=True, big=True), exp)
 
@@ -70,7 +60,7 @@ def test_orphan_list_hands_over_to_the_long_form():
     prof = R.profile(1, 8)
     exp = R.expect_rows(R.scaffolds(), prof, R._ig(1, 8), rows, 1, 8)
     assert all(x["flag"] == H.OK for x in exp)
-    with _engine(1, 8) as e:
+    with R.engine(1, 8) as e:
         auto = e.score_ranges(*R.arrays(rows), rip=True)
         big = e.score_ranges(*R.arrays(rows), rip=True, big=True)
     R.check("orphan hand-over", auto, exp)
@@ -117,7 +107,7 @@ def test_rows_do_not_depend_on_the_call(kmin, kmax):
     rip = True
     s, a, b = R.arrays(rows)
     n = len(rows)
-    with _engine(kmin, kmax) as e:
+    with R.engine(kmin, kmax) as e:
         before = e.scan(5000, 1000, rip=True)
         first = e.score_ranges(s, a, b, rip=rip)
         again = e.score_ranges(s, a, b, rip=rip)
@@ -192,7 +182,7 @@ def test_rejected_calls_launch_nothing_and_leave_the_state():
 def test_a_stop_of_2_31_is_refused():
     """Refused by the scaffold bound: the clause for ranges of 2^31 bases or more needs a 2 Gb scaffold and has no test."""
     from frisk_amd import _ffi
-    with _engine(1, 6) as e:
+    with R.engine(1, 6) as e:
         with pytest.raises(_ffi.FriskHipError) as err:
             e.score_ranges([0], [0], [1 << 31])
         assert err.value.code == _ffi.E_ARG

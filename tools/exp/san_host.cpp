@@ -1,7 +1,8 @@
 // (CPU) the library's host-only headers under AddressSanitizer + UBSan (GPU sanitizers are not available on the pool): random batches
 // through the 2-bit packer (against a letter-by-letter restatement), bitmap -> runs, the HMM fit / Viterbi on random series of awkward
 // lengths, the scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes, named shapes against values worked out by
-// hand, and the window-tile planner (scan_tiles.h): every rank's tiles of random shapes together.
+// hand, the window-tile planner (scan_tiles.h): every rank's tiles of random shapes together, and the region scorer's plan
+// (range_plan.h): invariants over seeded random batches, named cases, the refusals with their rows, and the memory fit.
 // build + run:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifrisk_amd/csrc
 //               tools/exp/san_host.cpp -o build/san/san_host -lpthread -lz && build/san/san_host
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include "fasta_pack2.h"
 #include "scan_schedule.h"
 #include "scan_tiles.h"
+#include "range_plan.h"
 #include <fstream>
 #include <unistd.h>
 
@@ -225,7 +227,168 @@ static long long check_scan_tiles() {             // -> shapes planned
     return shapes;
 }
 
+// The region scorer's plan (range_plan.h).  Invariants of an accepted plan: the two lists partition the rows, each longest first with
+// ties by row; a short row is at most FRISK_RANGE_SHORT_MAX bases; long_cap = n_long, plus n_short only at kmax = 8; the slice
+// capacities are even and hold min(longest, 4^kmax); the grids follow the rules; the fit stays within 1 .. want.
+static void check_one_plan(const RangePlan& R, const std::vector<int64_t>& seq_off, const std::vector<int32_t>& si, const std::vector<int64_t>& a,
+                           const std::vector<int64_t>& b, int kmax, bool all_long, int num_cu, int per_cu, int top_n) {
+    const int64_t n = int64_t(si.size());
+    CHECK(R.error_code == FRISK_OK && R.error.empty());
+    if (R.error_code != FRISK_OK) return;
+    CHECK(int64_t(R.ranges.size()) == 2 * n && R.n_short() + R.n_long() == n);
+    if (int64_t(R.ranges.size()) != 2 * n || R.n_short() + R.n_long() != n) return;
+    std::vector<int> seen(static_cast<size_t>(n), 0);
+    int64_t longest_short = 0, longest_long = 0;
+    for (int form = 0; form < 2; ++form) {
+        const std::vector<int64_t>& rows = form ? R.long_rows : R.short_rows;
+        for (size_t i = 0; i < rows.size(); ++i) {
+            const int64_t r = rows[i];
+            CHECK(0 <= r && r < n);
+            if (r < 0 || r >= n) return;
+            ++seen[size_t(r)];
+            const int64_t len = R.ranges[size_t(2 * r + 1)];
+            CHECK(R.ranges[size_t(2 * r)] == seq_off[size_t(si[size_t(r)])] + a[size_t(r)] && len == b[size_t(r)] - a[size_t(r)] && len >= 1);
+            CHECK((form == 1) == (all_long || len > FRISK_RANGE_SHORT_MAX));
+            if (i > 0) {
+                const int64_t p = rows[i - 1], plen = R.ranges[size_t(2 * p + 1)];
+                CHECK(plen > len || (plen == len && p < r));
+            }
+            int64_t& longest = form ? longest_long : longest_short;
+            longest = std::max(longest, len);
+        }
+    }
+    for (int k : seen) CHECK(k == 1);
+    const bool k8 = kmax == 8;
+    CHECK(R.long_cap == R.n_long() + (k8 ? R.n_short() : 0));
+    const int64_t nK = int64_t(1) << (2 * kmax);
+    if (top_n > 0) {
+        CHECK(R.cap_short % 2 == 0 && R.cap_short >= std::min(longest_short, nK) && R.cap_short <= std::min(longest_short, nK) + 1);
+        const int64_t held = std::max(longest_long, k8 ? longest_short : 0);
+        CHECK(R.cap_long % 2 == 0 && R.cap_long >= std::min(held, nK) && R.cap_long <= std::min(held, nK) + 1);
+    } else {
+        CHECK(R.cap_short == 0 && R.cap_long == 0);
+    }
+    CHECK(R.grid_short == int(std::min<int64_t>(R.n_short(), int64_t(num_cu) * (k8 ? 1 : per_cu))));
+    CHECK(R.want_long <= num_cu && R.want_long <= R.long_cap && R.want_long >= std::min<int64_t>(R.n_long(), num_cu));
+    CHECK((R.want_long == 0) == (R.long_cap == 0));
+    if (R.want_long > 0) {
+        const int64_t stride = (nK * 4 / 3 + 3) / 4 * 4;
+        for (size_t slice : {size_t(0), size_t(R.cap_long) * 12}) for (size_t free_b : {size_t(0), size_t(1) << 20, size_t(1) << 34, size_t(1) << 40})
+            for (size_t have : {size_t(0), size_t(stride), size_t(R.want_long) * size_t(stride)}) {
+                const int64_t fit = fit_long_workgroups(R.want_long, stride, slice, free_b, have);
+                CHECK(1 <= fit && fit <= R.want_long);
+                if (free_b == (size_t(1) << 40)) CHECK(fit == R.want_long);
+                if (free_b == 0 && slice == 0) CHECK(fit == std::max<int64_t>(1, std::min<int64_t>(R.want_long, int64_t(have / size_t(stride)))));
+            }
+    }
+}
+
+static long long check_range_plan() {             // -> plans made
+    long long plans = 0;
+    const int64_t two31 = int64_t(1) << 31;
+    // (a) seeded random batches: scaffolds of up to 200 000 bases, lengths crowded at both sides of the short form's limit
+    std::mt19937_64 rng(20240901);
+    int64_t both_forms = 0, tied = 0;
+    for (int round = 0; round < 3000; ++round) {
+        const int n_seq = 1 + int(rng() % 5);
+        std::vector<int64_t> seq_len(static_cast<size_t>(n_seq)), seq_off(static_cast<size_t>(n_seq));
+        int64_t off = 0;
+        for (int s = 0; s < n_seq; ++s) {
+            seq_len[size_t(s)] = 1 + int64_t(rng() % 200000);
+            seq_off[size_t(s)] = off;
+            off += seq_len[size_t(s)] + 1;
+        }
+        const int64_t n = int64_t(rng() % 40);
+        std::vector<int32_t> si(static_cast<size_t>(n));
+        std::vector<int64_t> a(static_cast<size_t>(n)), b(static_cast<size_t>(n));
+        for (int64_t r = 0; r < n; ++r) {
+            const int32_t s = int32_t(rng() % uint64_t(n_seq));
+            const int64_t size = seq_len[size_t(s)];
+            int64_t len = 1 + int64_t(rng() % uint64_t(size));
+            if (rng() % 3 == 0) len = std::min<int64_t>(size, 65533 + int64_t(rng() % 6));
+            if (rng() % 4 == 0 && r > 0) len = std::min<int64_t>(size, b[size_t(r - 1)] - a[size_t(r - 1)]);       // a tie
+            si[size_t(r)] = s;
+            a[size_t(r)] = int64_t(rng() % uint64_t(size - len + 1));
+            b[size_t(r)] = a[size_t(r)] + len;
+        }
+        const int kmax = 1 + int(rng() % 12), num_cu = 1 + int(rng() % 300), per_cu = (rng() & 1) ? 3 : 1;
+        const bool all_long = kmax > 8 || rng() % 4 == 0;
+        const int top_n = (rng() & 1) ? 1 + int(rng() % 64) : 0;
+        const RangePlan R = plan_ranges(n_seq, seq_len.data(), seq_off.data(), si.data(), a.data(), b.data(), n, kmax, all_long, num_cu, per_cu, top_n);
+        check_one_plan(R, seq_off, si, a, b, kmax, all_long, num_cu, per_cu, top_n);
+        both_forms += R.n_short() > 0 && R.n_long() > 0;
+        for (size_t i = 1; i < R.short_rows.size(); ++i) tied += R.ranges[size_t(2 * R.short_rows[i] + 1)] == R.ranges[size_t(2 * R.short_rows[i - 1] + 1)];
+        ++plans;
+    }
+    CHECK(both_forms > 300 && tied > 300);                      // (the sweep reaches them)
+    // (b) named cases on one batch: a scaffold of 2^31 + 10 bases behind one of 100 000 (no sequence is read)
+    const std::vector<int64_t> seq_len = {100000, two31 + 10}, seq_off = {0, 100001};
+    auto plan = [&](const std::vector<int32_t>& si, const std::vector<int64_t>& a, const std::vector<int64_t>& b, int kmax, bool all_long = false,
+                    int top_n = 0, int per_cu = 3) {
+        ++plans;
+        return plan_ranges(2, seq_len.data(), seq_off.data(), si.data(), a.data(), b.data(), int64_t(si.size()), kmax, all_long, 256, per_cu, top_n);
+    };
+    {   // n = 0: an empty plan, nothing to launch
+        const RangePlan R = plan({}, {}, {}, 8);
+        check_one_plan(R, seq_off, {}, {}, {}, 8, false, 256, 3, 0);
+        CHECK(R.grid_short == 0 && R.want_long == 0 && R.long_cap == 0);
+    }
+    for (int kmax : {8, 7, 9}) {        // a single row
+        const RangePlan R = plan({0}, {5}, {505}, kmax, kmax > 8, 4);
+        check_one_plan(R, seq_off, {0}, {5}, {505}, kmax, kmax > 8, 256, 3, 4);
+        CHECK(R.ranges == (std::vector<int64_t>{5, 500}));
+        if (kmax == 8) CHECK(R.n_short() == 1 && R.long_cap == 1 && R.grid_short == 1 && R.want_long == 1 && R.cap_short == 500 && R.cap_long == 500);
+        if (kmax == 7) CHECK(R.n_short() == 1 && R.long_cap == 0 && R.grid_short == 1 && R.want_long == 0 && R.cap_short == 500 && R.cap_long == 0);
+        if (kmax == 9) CHECK(R.n_long() == 1 && R.long_cap == 1 && R.grid_short == 0 && R.want_long == 1 && R.cap_short == 0 && R.cap_long == 500);
+    }
+    for (int kmax : {8, 7}) {           // 65 535 and 65 536 bases: either side of FRISK_RANGE_SHORT_MAX; 65 535 is odd, 4^7 = 16 384
+        const std::vector<int32_t> si = {0, 0};
+        const std::vector<int64_t> a = {10, 0}, b = {10 + 65535, 65536};
+        const RangePlan R = plan(si, a, b, kmax, false, 64);
+        check_one_plan(R, seq_off, si, a, b, kmax, false, 256, 3, 64);
+        CHECK(R.short_rows == std::vector<int64_t>{0} && R.long_rows == std::vector<int64_t>{1});
+        CHECK(R.long_cap == (kmax == 8 ? 2 : 1) && R.want_long == R.long_cap);
+        CHECK(R.cap_short == (kmax == 8 ? 65536 : 16384) && R.cap_long == (kmax == 8 ? 65536 : 16384));
+        const RangePlan B = plan(si, a, b, kmax, true);        // all_long: both rows to the long form, the longer first
+        check_one_plan(B, seq_off, si, a, b, kmax, true, 256, 3, 0);
+        CHECK(B.n_short() == 0 && B.long_rows == (std::vector<int64_t>{1, 0}) && B.long_cap == 2 && B.want_long == 2 && B.grid_short == 0);
+    }
+    {   // equal lengths: ties go by row, whatever the positions; 600 short rows on 256 CUs at three, or one, workgroups per CU
+        std::vector<int32_t> si(600, 0);
+        std::vector<int64_t> a(600), b(600);
+        for (size_t r = 0; r < 600; ++r) { a[r] = int64_t(599 - r) * 7; b[r] = a[r] + (r % 3 == 0 ? 400 : 300); }
+        for (int kmax : {7, 8}) for (int per_cu : {3, 1}) {
+            const RangePlan R = plan(si, a, b, kmax, false, 0, per_cu);
+            check_one_plan(R, seq_off, si, a, b, kmax, false, 256, per_cu, 0);
+            CHECK(R.short_rows[0] == 0 && R.short_rows[1] == 3 && R.short_rows[199] == 597 && R.short_rows[200] == 1 && R.short_rows[201] == 2);
+            CHECK(R.grid_short == (kmax == 8 || per_cu == 1 ? 256 : 600));
+            CHECK(R.want_long == (kmax == 8 ? FRISK_RANGE_HANDOVER_WGS : 0) && R.long_cap == (kmax == 8 ? 600 : 0));
+        }
+    }
+    {   // 2^31 - 1 bases are taken (the long form), 2^31 are refused, with the row
+        const RangePlan R = plan({0, 1}, {0, 3}, {100, 3 + two31 - 1}, 8);
+        check_one_plan(R, seq_off, {0, 1}, {0, 3}, {100, 3 + two31 - 1}, 8, false, 256, 3, 0);
+        CHECK(R.long_rows == std::vector<int64_t>{1} && R.ranges[2] == 100001 + 3 && R.ranges[3] == two31 - 1);
+        const RangePlan X = plan({0, 1}, {0, 3}, {100, 3 + two31}, 8);
+        CHECK(X.error_code == FRISK_E_ARG && X.error == "range outside the scaffold (or empty, or of 2^31 bases or more) in row 1");
+        CHECK(X.ranges.empty() && X.short_rows.empty() && X.long_rows.empty());
+    }
+    {   // the refusals, each with the first bad row
+        const std::string idx = "sequence index out of range in row ", rng_ = "range outside the scaffold (or empty, or of 2^31 bases or more) in row ";
+        CHECK(plan({0, 2}, {0, 0}, {10, 10}, 8).error == idx + "1");
+        CHECK(plan({0, 0, -1}, {0, 0, 0}, {10, 10, 10}, 8).error == idx + "2");
+        CHECK(plan({0, 0}, {0, 10}, {10, 10}, 8).error == rng_ + "1");                 // empty
+        CHECK(plan({0}, {10}, {9}, 8).error == rng_ + "0");
+        CHECK(plan({0}, {-1}, {9}, 8).error == rng_ + "0");
+        CHECK(plan({0, 0, 0, 0}, {0, 0, 0, 5}, {10, 10, 100000, 100001}, 8).error == rng_ + "3");     // past the scaffold's end
+        CHECK(plan({0, 1, 0}, {0, 0, 0}, {10, 100001, 100001}, 8).error == rng_ + "2");               // (the other scaffold's length does not count)
+        CHECK(plan({0, 2}, {0, 0}, {10, 10}, 8).error_code == FRISK_E_ARG && plan({0}, {10}, {9}, 9, true, 5).error_code == FRISK_E_ARG);
+    }
+    return plans;
+}
+
 int main() {
+    const long long range_plans = check_range_plan();
     const long long plans = check_scan_schedule();
     const long long tile_shapes = check_scan_tiles();
     std::mt19937_64 rng(12345);
@@ -369,6 +532,6 @@ int main() {
         }
         ::unlink(path.c_str());
     }
-    std::printf("%s (%d failed checks; %lld scan schedules; %lld tile plans; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, tile_shapes, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
+    std::printf("%s (%d failed checks; %lld scan schedules; %lld tile plans; %lld range plans; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, tile_shapes, range_plans, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
     return fails ? 1 : 0;
 }

@@ -14,44 +14,30 @@ import json
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
 
-from ranges_timing import median_ms  # noqa: E402
+import region_workloads as RW  # noqa: E402
 
 TOPS = (1, 16, 64)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--scaffolds", type=int, default=16)
-    ap.add_argument("--scaffold-len", type=int, default=4000000)
+    RW.add_arguments(ap)
     a = ap.parse_args()
     from frisk_amd.engine import Engine
     lens = [a.scaffold_len] * a.scaffolds
-    w, inc = 5000, 1000
+    w, inc = RW.W, RW.INC
     rows = []
     with Engine(1, 8, device=a.device) as e:
-        e.synth(lens, 7, island_frac=0.02, n_frac=0.01, lower_frac=0.05)
-        e.profile_reset(); e.profile_add(); e.profile_finalize()
-        scan = e.scan(w, inc)
-        jump = (scan.status & 4) != 0
-        grid = (scan.seq_index.copy(), np.where(jump, scan.start, scan.start - 1), scan.stop.copy())
-        rng = np.random.default_rng(11)
-        n = 50000
-        ln = np.exp(rng.uniform(np.log(300), np.log(30000), n)).astype(np.int64)
-        s = rng.integers(0, len(lens), n).astype(np.int32)
-        a0 = (rng.random(n) * (a.scaffold_len - ln)).astype(np.int64)
-        mixed = (s, a0, a0 + ln)
-        whole = (np.arange(len(lens), dtype=np.int32), np.zeros(len(lens), np.int64), np.asarray(lens, np.int64))
-        for label, (si, st, sp) in (("grid", grid), ("mixed", mixed), ("long", whole)):
-            score_ms = median_ms(lambda: e.score_ranges(si, st, sp), lambda: e.kernel_ms(4), a.repeats)
+        RW.synth_batch(e, lens)
+        RW.own_profile(e)
+        workloads = (("grid", RW.grid_of(e.scan(w, inc))), ("mixed", RW.mixed(len(lens), a.scaffold_len)), ("long", RW.whole(lens)))
+        for label, (si, st, sp) in workloads:
+            score_ms = RW.median_ms(lambda: e.score_ranges(si, st, sp), lambda: e.kernel_ms(4), a.repeats)
             res = {"workload": label, "ranges": int(si.size), "bases": int((sp - st).sum()), "score_kernel_ms": round(score_ms, 3)}
             for top_n in TOPS:
-                ms = median_ms(lambda: e.explain_ranges(si, st, sp, top_n), lambda: e.kernel_ms(7), a.repeats)
+                ms = RW.median_ms(lambda: e.explain_ranges(si, st, sp, top_n), lambda: e.kernel_ms(7), a.repeats)
                 res["explain_kernel_ms_top%d" % top_n] = round(ms, 3)
                 res["ratio_top%d" % top_n] = round(ms / score_ms, 2)
             got, ref = e.explain_ranges(si, st, sp, 1), e.score_ranges(si, st, sp)

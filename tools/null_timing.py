@@ -22,26 +22,25 @@ import numpy as np
 
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
 
+import region_workloads as RW  # noqa: E402
+
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--scaffolds", type=int, default=16)
-    ap.add_argument("--scaffold-len", type=int, default=4000000)
+    RW.add_arguments(ap)
     ap.add_argument("--regions", type=int, default=10000)
     ap.add_argument("--draws", type=int, default=100)
     a = ap.parse_args()
     from frisk_amd.hotpath import HotPath
     lens = [a.scaffold_len] * a.scaffolds
     rng = np.random.default_rng(11)
-    lengths = sorted({int(x) for x in np.exp(rng.uniform(np.log(300), np.log(30000), a.regions))})
+    lengths = sorted({int(x) for x in RW.log_uniform_lengths(rng, a.regions)})
     hp = HotPath(1, 8, device=a.device)
     e = hp.engine
     rows = []
     try:
-        e.synth(lens, 7, island_frac=0.02, n_frac=0.01, lower_frac=0.05)
-        e.profile_reset(); e.profile_add(); e.profile_finalize()
+        RW.synth_batch(e, lens)
+        RW.own_profile(e)
         hp._resident, hp.names = "synthetic", [""] * len(lens)         # (the host null scores the resident batch as the host)
         args = SimpleNamespace(hostSeq="synthetic")
         scored = {"ms": 0.0}

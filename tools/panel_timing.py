@@ -15,54 +15,37 @@ table.
 import argparse
 import json
 import os
-import statistics
 import sys
-
-import numpy as np
 
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
 
-
-def median_of(fn, repeats):
-    fn()
-    return statistics.median(fn() for _ in range(repeats))
+import region_workloads as RW  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--scaffolds", type=int, default=16)
-    ap.add_argument("--scaffold-len", type=int, default=4000000)
+    RW.add_arguments(ap)
     ap.add_argument("--profiles", type=int, nargs="+", default=[1, 4, 16])
     a = ap.parse_args()
     from frisk_amd.engine import Engine
     lens = [a.scaffold_len] * a.scaffolds
-    w, inc = 5000, 1000
+    w, inc = RW.W, RW.INC
     rows = []
     with Engine(1, 8, device=a.device) as e:
         profs = []
         for p in range(max(a.profiles)):                # donor p: a synthetic genome of its own
-            e.synth(lens, 100 + p, island_frac=0.02, n_frac=0.01, lower_frac=0.05)
-            e.profile_reset(); e.profile_add(); e.profile_finalize()
+            RW.synth_batch(e, lens, seed=100 + p)
+            RW.own_profile(e)
             profs.append(e.profile_get())
-        e.synth(lens, 7, island_frac=0.02, n_frac=0.01, lower_frac=0.05)
+        RW.synth_batch(e, lens)
         e.profile_set(*profs[0])
-        scan = e.scan(w, inc)
-        jump = (scan.status & 4) != 0
-        grid = (scan.seq_index.copy(), np.where(jump, scan.start, scan.start - 1), scan.stop.copy())
-        rng = np.random.default_rng(11)
-        n = 50000
-        ln = np.exp(rng.uniform(np.log(300), np.log(30000), n)).astype(np.int64)
-        s = rng.integers(0, len(lens), n).astype(np.int32)
-        a0 = (rng.random(n) * (a.scaffold_len - ln)).astype(np.int64)
-        mixed = (s, a0, a0 + ln)
+        workloads = (("grid", RW.grid_of(e.scan(w, inc))), ("mixed", RW.mixed(len(lens), a.scaffold_len)))
         for P in a.profiles:
             e.panel_reset()
             for prof in profs[:P]:
                 e.profile_set(*prof)
                 e.panel_push()
-            for label, (si, st, sp) in (("grid", grid), ("mixed", mixed)):
+            for label, (si, st, sp) in workloads:
                 def panel():
                     e.score_ranges_panel(si, st, sp)
                     return e.kernel_ms(5)
@@ -74,7 +57,7 @@ def main():
                         e.score_ranges(si, st, sp)
                         total += e.kernel_ms(4)
                     return total
-                pa, sg = median_of(panel, a.repeats), median_of(single, a.repeats)
+                pa, sg = RW.median_ms(panel, None, a.repeats), RW.median_ms(single, None, a.repeats)
                 got, one = e.score_ranges_panel(si, st, sp), e.score_ranges(si, st, sp)     # (the context holds profile P - 1)
                 res = {"workload": label, "profiles": P, "ranges": int(si.size), "bases": int((sp - st).sum()),
                        "panel_ms": round(pa, 3), "single_ms_sum": round(sg, 3), "panel_over_single": round(pa / sg, 3),

@@ -12,50 +12,31 @@ markdown table.
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
 
-
-def median_ms(fn, ms, repeats):
-    fn()
-    out = []
-    for _ in range(repeats):
-        fn()
-        out.append(ms())
-    return statistics.median(out)
+import region_workloads as RW  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--scaffolds", type=int, default=16)
-    ap.add_argument("--scaffold-len", type=int, default=4000000)
+    RW.add_arguments(ap)
     a = ap.parse_args()
     from frisk_amd.engine import Engine
     lens = [a.scaffold_len] * a.scaffolds
-    w, inc = 5000, 1000
+    w, inc = RW.W, RW.INC
     rows = []
     with Engine(1, 8, device=a.device) as e:
-        e.synth(lens, 7, island_frac=0.02, n_frac=0.01, lower_frac=0.05)
-        e.profile_reset(); e.profile_add(); e.profile_finalize()
+        RW.synth_batch(e, lens)
+        RW.own_profile(e)
         scan = e.scan(w, inc)
-        scan_ms = median_ms(lambda: e.scan(w, inc, pinned=True), lambda: e.kernel_ms(0), a.repeats)
-        jump = (scan.status & 4) != 0
-        grid = (scan.seq_index.copy(), np.where(jump, scan.start, scan.start - 1), scan.stop.copy())
-        rng = np.random.default_rng(11)
-        n = 50000
-        ln = np.exp(rng.uniform(np.log(300), np.log(30000), n)).astype(np.int64)
-        s = rng.integers(0, len(lens), n).astype(np.int32)
-        a0 = (rng.random(n) * (a.scaffold_len - ln)).astype(np.int64)
-        mixed = (s, a0, a0 + ln)
-        whole = (np.arange(len(lens), dtype=np.int32), np.zeros(len(lens), np.int64), np.asarray(lens, np.int64))
-        for label, (si, st, sp) in (("grid", grid), ("mixed", mixed), ("long", whole)):
-            ms = median_ms(lambda: e.score_ranges(si, st, sp), lambda: e.kernel_ms(4), a.repeats)
+        scan_ms = RW.median_ms(lambda: e.scan(w, inc, pinned=True), lambda: e.kernel_ms(0), a.repeats)
+        workloads = (("grid", RW.grid_of(scan)), ("mixed", RW.mixed(len(lens), a.scaffold_len)), ("long", RW.whole(lens)))
+        for label, (si, st, sp) in workloads:
+            ms = RW.median_ms(lambda: e.score_ranges(si, st, sp), lambda: e.kernel_ms(4), a.repeats)
             res = {"workload": label, "ranges": int(si.size), "bases": int((sp - st).sum()), "kernel_ms": round(ms, 3),
                    "ranges_per_s": round(si.size / (ms * 1e-3), 1)}
             if label == "grid":
