@@ -1,6 +1,6 @@
-// frisk_abi.hip - host side of libfrisk_hip.so: the context's creation and destruction, its small getters, the profile (phase A) and
-// the scan of the C ABI declared in include/frisk_hip.h.  The context itself is frisk_ctx.h's; the sequence and FASTA entry points are
-// in frisk_seq.hip.  The scan kernels are launched through scan_launch.h (scan_launch.hip, scan8_launch.hip, scan8_launch4.hip); the
+// frisk_abi.hip - host side of libfrisk_hip.so: the context's creation and destruction, its small getters, the profile (phase A: its
+// launches are planned in profile_plan.h) and the scan of the C ABI declared in include/frisk_hip.h.  The context itself is
+// frisk_ctx.h's; the sequence and FASTA entry points are in frisk_seq.hip.  The scan kernels are launched through scan_launch.h (scan_launch.hip, scan8_launch.hip, scan8_launch4.hip); the
 // entry points that take no context (HMM, projection, clustering) are in frisk_analysis.hip.  gfx950 (MI355X) only.  Build: see
 // __graft_entry__.build_hip().
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 
 #include "frisk_ctx.h"
 #include "profile_kernels.h"
+#include "profile_plan.h"
 #include "scan_launch.h"
 #include "scan_schedule.h"
 #include "scan_tiles.h"             // plan_scaffold
@@ -172,6 +173,7 @@ int frisk_profile_reset(frisk_ctx* c) {
 }
 
 static int profile_add_range(frisk_ctx* c, int mask_host, bool one_pass, int64_t p0, int64_t p1, bool first = true, bool last = true);
+static int launch_profile(frisk_ctx* c, const ProfileLaunch& L, int mask_host, int64_t p0, int64_t p1, bool first, bool last);
 
 int frisk_profile_add(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1) {
     if (!c) return FRISK_E_ARG;
@@ -195,20 +197,14 @@ int frisk_profile_add(frisk_ctx* c, int mask_host, int64_t p0, int64_t p1) {
     }
     frisk_ctx::Batch& SB = c->b();
     if (SB.streaming && p0 < 0 && p1 < 0 && !SB.piece_end.empty()) {
-        // a streamed batch counted as a whole: phase A follows the copies piece by piece - the kernel of piece i runs while piece
-        // i + 1 crosses PCIe, only the last piece's kernel is left when the upload ends.  A lane that counts the positions of
-        // bitmap word q reads word q + 1 of the masks and code word 2 q + 2, so piece i's kernel stops one word short of its end.
+        // a streamed batch counted as a whole: phase A follows the copies piece by piece (plan_profile_pieces), each launch behind
+        // the events of the pieces it reads
         HIPC(c, hipSetDevice(c->device));
-        const size_t np = SB.piece_end.size();
-        int64_t done = 0;
-        for (size_t i = 0; i < np; ++i) {
-            HIPC(c, hipStreamWaitEvent(c->stream, SB.piece_ev[i], 0));
-            const int64_t upto = i + 1 == np ? SB.padded_len : (SB.piece_end[i] - 1) * 32;
-            if (upto > done || i + 1 == np || i == 0) {
-                int rc = profile_add_range(c, mask_host, one_pass, done, std::max(done, upto), i == 0, i + 1 == np);
-                if (rc) return rc;
-                done = std::max(done, upto);
-            }
+        size_t waited = 0;
+        for (const ProfilePiece& L : plan_profile_pieces(SB.piece_end, SB.padded_len)) {
+            for (; waited <= L.piece; ++waited) HIPC(c, hipStreamWaitEvent(c->stream, SB.piece_ev[waited], 0));
+            int rc = profile_add_range(c, mask_host, one_pass, L.p0, L.p1, L.first, L.last);
+            if (rc) return rc;
         }
         SB.streaming = false;
         return FRISK_OK;
@@ -222,55 +218,35 @@ static int profile_add_range(frisk_ctx* c, int mask_host, bool one_pass, int64_t
     if (p0 < 0 || p1 > c->b().padded_len || p0 > p1) return fail(c, FRISK_E_ARG, "position range outside the batch");
     HIPC(c, hipSetDevice(c->device));
     c->profile_final = false;
-    if (c->kmax > 8) {          // 4^K counters do not fit a CU: one global atomic per position (profile_kernels.h)
-        const int64_t nw = p1 > p0 ? ((p1 + 31) >> 5) - (p0 >> 5) : 0;
-        if (first) HIPC(c, hipEventRecord(c->evp0, c->stream));
-        if (nw > 0)
-            profile_add_big_kernel<<<grid_for(nw, 256, c->num_cu * 8), 256, 0, c->stream>>>(
-                c->b().d_codes.p, c->b().d_inv.p, c->b().d_low.p, p0, p1, c->kmin, c->kmax, mask_host ? 1 : 0, int(c->nprof),
-                reinterpret_cast<unsigned long long*>(c->d_raw.p));
-        HIPC(c, hipGetLastError());
-        if (last) { HIPC(c, hipEventRecord(c->evp1, c->stream)); c->ms_pending[1] = true; }
-        return FRISK_OK;
-    }
-    // K = 8, a long range (a whole resident genome): 16-bit counters, ONE walk over the sequence (profile_add16_kernel; a wrapped
-    // counter sends its workgroup to the two-half form).  The walk halves, the flush doubles (65 536 fields per workgroup instead of
-    // 32 768 bins): measured 2.42 -> 1.33 ms on the 3.29 Gb shape, 0.345 -> 0.55 ms on the 410 Mb shard (tools/exp/prof_ab.py) - so from
-    // 2^30 positions per launch on.  (one_pass = FRISK_PROFILE_ONE_PASS forces it: the tests' way to the overflow path.)
-    if (c->kmax == 8 && (one_pass || p1 - p0 >= (int64_t(1) << 30))) {
-        const int64_t span16 = p1 - p0;
-        const int64_t nwords16 = span16 > 0 ? ((p1 + 31) >> 5) - (p0 >> 5) : 0;
-        int64_t nch = std::min<int64_t>(std::max<int64_t>(1, span16 / 65536), int64_t(c->num_cu));
-        const int64_t chunk_len16 = (nwords16 + nch - 1) / std::max<int64_t>(nch, 1);
-        nch = chunk_len16 > 0 ? (nwords16 + chunk_len16 - 1) / chunk_len16 : 0;
-        if (first) HIPC(c, hipEventRecord(c->evp0, c->stream));
-        if (span16 > 0) {
-            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(profile_add16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-            profile_add16_kernel<<<int(nch), FRISK_PROF_NT, 131072, c->stream>>>(c->b().d_codes.p, c->b().d_inv.p, c->b().d_low.p, p0, p1, c->kmin,
-                                                                                 mask_host ? 1 : 0, int(c->nprof), chunk_len16,
-                                                                                 reinterpret_cast<unsigned long long*>(c->d_raw.p));
-        }
-        HIPC(c, hipGetLastError());
-        if (last) { HIPC(c, hipEventRecord(c->evp1, c->stream)); c->ms_pending[1] = true; }
-        return FRISK_OK;
-    }
-    // order-K table privatised in LDS (u32): split in two halves at K = 8 (256 KiB does not fit a CU)
-    const int halves = (c->kmax == 8) ? 2 : 1;
-    const size_t lds = (size_t(1) << (2 * c->kmax)) / size_t(halves) * 4;
-    const int64_t span = p1 - p0;
-    const int64_t nwords = span > 0 ? ((p1 + 31) >> 5) - (p0 >> 5) : 0;     // a lane takes one 32-position bitmap word
-    constexpr int64_t wg_per_cu = 1;        // measured on the 410 Mb shard: 1 -> 0.34 ms, 2 -> 0.41, 4 -> 0.51 (the flush of the private tables dominates)
-    int64_t nchunks = std::min<int64_t>(std::max<int64_t>(1, span / 65536), int64_t(c->num_cu) * wg_per_cu / halves);
-    const int64_t chunk_len = (nwords + nchunks - 1) / std::max<int64_t>(nchunks, 1);   // in words
-    nchunks = chunk_len > 0 ? (nwords + chunk_len - 1) / chunk_len : 0;
+    return launch_profile(c, plan_profile_launch(c->kmax, c->num_cu, p0, p1, one_pass), mask_host ? 1 : 0, p0, p1, first, last);
+}
+
+// One planned launch (profile_plan.h) on the context's stream, between the events of frisk_last_kernel_ms(1): the start event with
+// the first launch of a call, the end event with its last.  An empty range launches nothing; its events are recorded all the same.
+static int launch_profile(frisk_ctx* c, const ProfileLaunch& L, int mask_host, int64_t p0, int64_t p1, bool first, bool last) {
+    static_assert(PROFILE_LDS_THREADS == FRISK_PROF_NT, "the plan's workgroup is the kernels'");
+    const frisk_ctx::Batch& B = c->b();
+    const uint32_t *codes = B.d_codes.p, *inv = B.d_inv.p, *low = B.d_low.p;
+    auto raw = reinterpret_cast<unsigned long long*>(c->d_raw.p);
+    const int kmin = c->kmin, kmax = c->kmax, nprof = int(c->nprof);
     if (first) HIPC(c, hipEventRecord(c->evp0, c->stream));
-    if (span > 0) {
-        auto raw = reinterpret_cast<unsigned long long*>(c->d_raw.p);
-        HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(profile_add_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(std::max<size_t>(lds, 16))));
-        profile_add_kernel<<<int(nchunks) * halves, FRISK_PROF_NT, std::max<size_t>(lds, 16), c->stream>>>(
-            c->b().d_codes.p, c->b().d_inv.p, c->b().d_low.p, p0, p1, c->kmin, c->kmax, mask_host ? 1 : 0, int(c->nprof), halves,
-            chunk_len, raw);
+    if (L.grid > 0) {
+        const void* kernel = L.form == PROFILE_FORM_BIG ? reinterpret_cast<const void*>(profile_add_big_kernel)
+                           : L.form == PROFILE_FORM_ONE_PASS ? reinterpret_cast<const void*>(profile_add16_kernel)
+                                                             : reinterpret_cast<const void*>(profile_add_kernel);
+        if (L.lds_bytes) HIPC(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(L.lds_bytes)));
+        switch (L.form) {
+            case PROFILE_FORM_BIG:
+                profile_add_big_kernel<<<L.grid, L.threads, L.lds_bytes, c->stream>>>(codes, inv, low, p0, p1, kmin, kmax, mask_host, nprof, raw);
+                break;
+            case PROFILE_FORM_ONE_PASS:
+                profile_add16_kernel<<<L.grid, L.threads, L.lds_bytes, c->stream>>>(codes, inv, low, p0, p1, kmin, mask_host, nprof, L.chunk_words, raw);
+                break;
+            case PROFILE_FORM_LDS:
+                profile_add_kernel<<<L.grid, L.threads, L.lds_bytes, c->stream>>>(codes, inv, low, p0, p1, kmin, kmax, mask_host, nprof, L.halves,
+                                                                                 L.chunk_words, raw);
+                break;
+        }
     }
     HIPC(c, hipGetLastError());
     if (last) {

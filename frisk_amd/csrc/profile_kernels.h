@@ -13,18 +13,180 @@
 // which is exact, including scaffold ends and N-adjacent positions.  `raw` = the D tables (profile
 // layout) followed by {totalLen, #K-mer start positions, nnTotal, 0}; everything in it is a plain sum
 // over positions, hence summable across batches and across GPUs.
-// The order-K table (all but a vanishing share of the updates) is privatised per workgroup in LDS as 32-bit
-// counters and flushed once with one global atomic per non-empty bin.  4^8 x 4 B = 256 KiB does not fit a
-// CU's 160 KiB, so at K = 8 the k-mer space is split in two halves by the leading bit of the code and a
-// workgroup makes its pass over its chunk for ONE half (grid = chunks x halves; the sequence is 0.5 B/base,
-// reading it twice is free).  Orders below K (positions next to an invalid base or a scaffold end) go straight
-// to global atomics, as do the three scalars (one atomic per wave).  Half 0 alone counts those.
 // A lane owns one 32-position WORD of the bitmaps (7 loads: two words of each bitmap, three of the codes); the
 // run flags of its 32 positions come from whole-word shifts, the codes from constant shifts, so a position costs
-// about ten instructions instead of its own three unaligned fetches.
+// about ten instructions instead of its own three unaligned fetches.  That walk is written once (load_word,
+// run_starts, code_at, add_runs, ProfScalars; walk_words for the forms with a table in LDS); the three kernels
+// differ in where a position with a full-length word (run >= K) is counted:
+//   profile_add_kernel      32-bit counters in LDS, flushed once with one global atomic per non-empty bin.  4^8 x 4 B =
+//                           256 KiB does not fit a CU's 160 KiB, so at K = 8 the k-mer space is split in two halves by the
+//                           leading bit of the code and a workgroup makes its pass over its chunk for ONE half (grid =
+//                           chunks x halves; the sequence is 0.5 B/base, reading it twice is free);
+//   profile_add16_kernel    K = 8: 16-bit fields in LDS, all of 4^8 in one walk;
+//   profile_add_big_kernel  K > 8: the global table, like every shorter run.
+// Orders below K (positions next to an invalid base or a scaffold end: a vanishing share) go straight to global atomics,
+// as do the three scalars (one atomic per wave); of the workgroups that walk a chunk more than once, the first walk alone
+// counts those.  Which form a range takes, and its grid: profile_plan.h.
 // ------------------------------------------------------------------------------------------------
 #define FRISK_PROF_NT 1024
 
+// the resident batch and the positions [p0, p1) of one launch
+struct ProfRange {
+    const uint32_t* __restrict__ codes;
+    const uint32_t* __restrict__ inv;
+    const uint32_t* __restrict__ low;
+    int64_t p0, p1;
+    int mask_host;
+    __device__ int64_t w_first() const { return p0 >> 5; }                 // bitmap words that hold [p0, p1)
+    __device__ int64_t w_end() const { return (p1 + 31) >> 5; }
+    __device__ void chunk(int64_t i, int64_t chunk_words, int64_t& wb, int64_t& we) const {    // the words of chunk i
+        wb = w_first() + i * chunk_words;
+        we = wb + chunk_words;
+        if (we > w_end()) we = w_end();
+    }
+};
+
+// the k most significant bits of a word (k clamped to 0..32)
+__device__ __forceinline__ uint32_t topbits(int64_t k) {
+    k = k < 0 ? 0 : (k > 32 ? 32 : k);
+    return uint32_t(0xFFFFFFFF00000000ull >> k);
+}
+
+// One 32-position word of the bitmaps as its lane sees it.  Position base+j (base = 32 wq) is bit 31-j of a 32-bit mask and
+// bit 63-j of a 64-bit one, whose low half is the next word's positions: what a run that starts in this word can reach.
+struct ProfWord {
+    uint32_t inr;           // positions of the word inside [p0, p1)
+    uint32_t other;         // not an uppercase A/T/G/C (countN, L106-118)
+    uint64_t V;             // countable bases: valid, and under --maskHost not soft-masked
+    uint64_t NP;            // not a PAD
+    uint64_t lo64, hi64;    // the codes from position base on, and from base+16 on
+};
+
+__device__ __forceinline__ ProfWord load_word(const ProfRange& r, int64_t wq) {
+    const int64_t base = wq << 5;                                           // position of bit 31 of this word
+    const uint32_t i0 = r.inv[wq], i1 = r.inv[wq + 1], l0 = r.low[wq], l1 = r.low[wq + 1];
+    const uint32_t c0 = r.codes[2 * wq], c1 = r.codes[2 * wq + 1], c2 = r.codes[2 * wq + 2];
+    const uint32_t e0 = i0 | (r.mask_host ? l0 : 0u), e1 = i1 | (r.mask_host ? l1 : 0u);
+    ProfWord W;
+    W.inr = topbits(r.p1 - base) & ~topbits(r.p0 - base);
+    W.other = i0 | l0;
+    W.V = ~((uint64_t(e0) << 32) | e1);
+    W.NP = ~((uint64_t(i0 & l0) << 32) | (i1 & l1));
+    W.lo64 = (uint64_t(c0) << 32) | c1;
+    W.hi64 = (uint64_t(c1) << 32) | c2;
+    return W;
+}
+
+// The positions that start a run of k set bits of M.  K8: k is 8, in three doubling steps.
+template <bool K8>
+__device__ __forceinline__ uint64_t run_starts(uint64_t M, int k) {
+    uint64_t F = M;
+    if (K8) { F &= F << 1; F &= F << 2; F &= F << 4; }
+    else for (int s = 1; s < k; ++s) F &= M << s;
+    return F;
+}
+
+// BITS (16, or 24 for the orders above 8) of code from position j of the word on; by constant shifts where j is a constant
+template <int BITS>
+__device__ __forceinline__ uint32_t code_at(const ProfWord& W, int j) {
+    return uint32_t((j < 16 ? W.lo64 : W.hi64) >> (64 - BITS - 2 * (j & 15))) & ((1u << BITS) - 1u);
+}
+
+// The positions `todo` of a word (countable ones) straight to the global tables: each to the table of order run = min(its run, kmax),
+// when that is an order of the profile.  For the forms with a table in LDS these are the few positions whose run is shorter than kmax.
+template <int BITS>
+__device__ __forceinline__ void add_runs(const ProfWord& W, uint32_t todo, int kmin, int kmax, unsigned long long* __restrict__ raw) {
+    while (todo) {
+        const int j = __clz(int(todo));
+        todo &= ~(0x80000000u >> j);                                        // (clears the top bit)
+        int run = __clzll((long long)(~(W.V << j)));                        // countable bases from here on (<= 32 visible)
+        run = run < kmax ? run : kmax;
+        if (run >= kmin) atomicAdd(&raw[table_offset(kmin, run) + (code_at<BITS>(W, j) >> (BITS - 2 * run))], 1ull);
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {     // lane 0 of each wave holds the wave's sum
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+// The three scalars of raw's tail, summed by a lane over its words; flush(): one atomic per wave and scalar
+struct ProfScalars {
+    unsigned long long tot = 0, kpos = 0, nn = 0;
+    template <bool K8>
+    __device__ __forceinline__ void add(const ProfWord& W, int kmax) {
+        const uint64_t G = run_starts<K8>(W.NP, kmax);                      // a K-mer can start here (L329): no PAD in reach
+        const uint32_t real = uint32_t(W.NP >> 32) & W.inr;
+        tot += __popc(real);
+        nn += __popc(real & W.other);
+        kpos += __popc(uint32_t(G >> 32) & W.inr);
+    }
+    __device__ __forceinline__ void flush(unsigned long long* __restrict__ tail) {     // tail = raw + nprof; all lanes of the wave call
+        tot = wave_sum(tot);
+        kpos = wave_sum(kpos);
+        nn = wave_sum(nn);
+        if ((threadIdx.x & 63) == 0) {
+            if (tot) atomicAdd(&tail[0], tot);
+            if (kpos) atomicAdd(&tail[1], kpos);
+            if (nn) atomicAdd(&tail[2], nn);
+        }
+    }
+};
+
+// A workgroup's table of `nwords` 32-bit words in LDS: zeroed, and (as 32-bit counters) added to the global bins dst[0 .. nwords)
+__device__ __forceinline__ void clear_table(uint32_t* hist, uint32_t nwords) {
+    for (uint32_t b = threadIdx.x; b < nwords / 4; b += blockDim.x) reinterpret_cast<uint4*>(hist)[b] = make_uint4(0, 0, 0, 0);
+    if (nwords < 4) for (uint32_t b = threadIdx.x; b < nwords; b += blockDim.x) hist[b] = 0;
+}
+__device__ __forceinline__ void flush_table32(const uint32_t* hist, uint32_t nbins, unsigned long long* __restrict__ dst) {
+    for (uint32_t b = threadIdx.x; b < nbins; b += blockDim.x) {
+        const uint32_t v = hist[b];
+        if (v) atomicAdd(&dst[b], (unsigned long long)v);
+    }
+}
+
+// Where the two-half form counts a full-length word: in the 32-bit counter of its code, if the code's leading bit is this half's
+// (one half: every code).  The bins of half h are raw[offK + h * nbins ...].
+struct HalfTable {
+    uint32_t* hist;
+    uint32_t nbins, halfbit, mine;
+    int shK;
+    __device__ __forceinline__ HalfTable(uint32_t* hist_, int kmax, int halves, int half)
+        : hist(hist_), nbins((1u << (2 * kmax)) / uint32_t(halves)), halfbit(halves == 2 ? nbins : 0u), mine(half ? halfbit : 0u),
+          shK(16 - 2 * kmax) {}
+    __device__ __forceinline__ void operator()(uint32_t c16) const {
+        const uint32_t code = c16 >> shK;
+        if ((code & halfbit) == mine) atomicAdd(&hist[code & (nbins - 1)], 1u);
+    }
+};
+
+// One walk of a workgroup over the words [wb, we), a lane a word: every position that starts a full-length word goes to full(16
+// bits of code, of which the leading 2 kmax are that word); with `rest`, everything that bypasses the table as well - the shorter
+// runs and the three scalars.  -> (rest) the full-length positions this lane counted.
+template <bool K8, class Full>
+__device__ __forceinline__ unsigned long long walk_words(const ProfRange& r, int64_t wb, int64_t we, int kmin, int kmax, bool rest,
+                                                         unsigned long long* __restrict__ raw, int nprof, const Full& full) {
+    ProfScalars S;
+    unsigned long long counted = 0;
+    for (int64_t wq = wb + threadIdx.x; wq < we; wq += blockDim.x) {
+        const ProfWord W = load_word(r, wq);
+        const uint64_t F = run_starts<K8>(W.V, kmax);                       // ... that start a run of kmax countable bases
+        const uint32_t fullm = uint32_t(F >> 32) & W.inr;
+#pragma unroll
+        for (int j = 0; j < 32; ++j)
+            if (fullm & (0x80000000u >> j)) full(code_at<16>(W, j));
+        if (rest) {
+            counted += uint32_t(__popc(fullm));
+            add_runs<16>(W, uint32_t(W.V >> 32) & ~uint32_t(F >> 32) & W.inr, kmin, kmax, raw);
+            S.add<K8>(W, kmax);
+        }
+    }
+    if (rest) S.flush(raw + nprof);
+    return counted;
+}
+
+// kmax <= 8: the order-K table privatised per workgroup as 32-bit counters, in one or (K = 8) two halves.  Half 0 alone counts
+// what bypasses the table.
 __global__ __launch_bounds__(FRISK_PROF_NT) void profile_add_kernel(const uint32_t* __restrict__ codes,
                                                                      const uint32_t* __restrict__ inv,
                                                                      const uint32_t* __restrict__ low, int64_t p0, int64_t p1,
@@ -33,80 +195,15 @@ __global__ __launch_bounds__(FRISK_PROF_NT) void profile_add_kernel(const uint32
                                                                      unsigned long long* __restrict__ raw) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
     const int half = int(blockIdx.x) % halves;
-    const int64_t chunk = int64_t(blockIdx.x) / halves;
-    const uint32_t nbins = (1u << (2 * kmax)) / uint32_t(halves);
-    for (uint32_t b = threadIdx.x; b < nbins / 4; b += blockDim.x) reinterpret_cast<uint4*>(hist)[b] = make_uint4(0, 0, 0, 0);
-    if (nbins < 4) for (uint32_t b = threadIdx.x; b < nbins; b += blockDim.x) hist[b] = 0;
+    const HalfTable table(hist, kmax, halves, half);
+    clear_table(hist, table.nbins);
     __syncthreads();
-    unsigned long long tot = 0, kpos = 0, nn = 0;
-    const int64_t w_first = p0 >> 5, w_end = (p1 + 31) >> 5;               // bitmap words that hold [p0, p1)
-    const int64_t wb = w_first + chunk * chunk_words;
-    int64_t we = wb + chunk_words;
-    if (we > w_end) we = w_end;
-    const int64_t offK = table_offset(kmin, kmax);
-    const int shK = 16 - 2 * kmax;
-    const uint32_t halfbit = (halves == 2) ? nbins : 0u;                    // the leading bit of the code picks the half
-    auto topbits = [](int64_t k) -> uint32_t {                             // the k most significant bits (k clamped to 0..32)
-        k = k < 0 ? 0 : (k > 32 ? 32 : k);
-        return uint32_t(0xFFFFFFFF00000000ull >> k);
-    };
-    for (int64_t wq = wb + threadIdx.x; wq < we; wq += blockDim.x) {
-        const int64_t base = wq << 5;                                       // position of bit 31 of this word
-        const uint32_t i0 = inv[wq], i1 = inv[wq + 1], l0 = low[wq], l1 = low[wq + 1];
-        const uint32_t c0 = codes[2 * wq], c1 = codes[2 * wq + 1], c2 = codes[2 * wq + 2];
-        const uint32_t inr = topbits(p1 - base) & ~topbits(p0 - base);      // positions of the word inside [p0, p1)
-        const uint32_t e0 = i0 | (mask_host ? l0 : 0u), e1 = i1 | (mask_host ? l1 : 0u);
-        const uint64_t V = ~((uint64_t(e0) << 32) | e1);                    // countable bases; position base+j at bit 63-j
-        uint64_t F = V;                                                     // ... that start a run of kmax of them
-        for (int s = 1; s < kmax; ++s) F &= V << s;
-        const uint32_t fullm = uint32_t(F >> 32) & inr;
-        const uint64_t lo64 = (uint64_t(c0) << 32) | c1, hi64 = (uint64_t(c1) << 32) | c2;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            if (fullm & (0x80000000u >> j)) {
-                const uint32_t c16 = uint32_t((j < 16 ? lo64 : hi64) >> (48 - 2 * (j & 15))) & 0xFFFFu;
-                const uint32_t code = c16 >> shK;
-                if ((code & halfbit) == (half ? halfbit : 0u)) atomicAdd(&hist[code & (nbins - 1)], 1u);
-            }
-        }
-        if (half == 0) {
-            // the few countable positions whose run is shorter than kmax: straight to the global tables
-            uint32_t shortm = uint32_t(V >> 32) & ~uint32_t(F >> 32) & inr;
-            while (shortm) {
-                const int j = __clz(int(shortm));
-                shortm &= ~(0x80000000u >> j);
-                const int run = __clzll((long long)(~(V << j)));            // < kmax here
-                if (run >= kmin) {
-                    const uint32_t c16 = uint32_t((j < 16 ? lo64 : hi64) >> (48 - 2 * (j & 15))) & 0xFFFFu;
-                    atomicAdd(&raw[table_offset(kmin, run) + (c16 >> (16 - 2 * run))], 1ull);
-                }
-            }
-            const uint64_t NP = ~((uint64_t(i0 & l0) << 32) | (i1 & l1));   // not a PAD
-            uint64_t G = NP;                                                // a K-mer can start here (L329): no PAD in reach
-            for (int s = 1; s < kmax; ++s) G &= NP << s;
-            const uint32_t real = uint32_t(NP >> 32) & inr;
-            tot += __popc(real);
-            nn += __popc(real & (i0 | l0));                                 // not an uppercase A/T/G/C (countN, L106-118)
-            kpos += __popc(uint32_t(G >> 32) & inr);
-        }
-    }
-    if (half == 0) {                     // wave-level reduction of the three scalars, one atomic per wave
-        for (int o = 32; o > 0; o >>= 1) {
-            tot += __shfl_down(tot, o);
-            kpos += __shfl_down(kpos, o);
-            nn += __shfl_down(nn, o);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            if (tot) atomicAdd(&raw[nprof + 0], tot);
-            if (kpos) atomicAdd(&raw[nprof + 1], kpos);
-            if (nn) atomicAdd(&raw[nprof + 2], nn);
-        }
-    }
+    const ProfRange r{codes, inv, low, p0, p1, mask_host};
+    int64_t wb, we;
+    r.chunk(int64_t(blockIdx.x) / halves, chunk_words, wb, we);
+    walk_words<false>(r, wb, we, kmin, kmax, half == 0, raw, nprof, table);
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < nbins; b += blockDim.x) {
-        const uint32_t v = hist[b];
-        if (v) atomicAdd(&raw[offK + uint32_t(half) * nbins + b], (unsigned long long)v);
-    }
+    flush_table32(hist, table.nbins, raw + table_offset(kmin, kmax) + uint32_t(half) * table.nbins);
 }
 
 // K = 8 in ONE pass (round 4): the order-8 table as 4^8 SIXTEEN-bit counters, two to a word = 128 KiB, so that a workgroup
@@ -126,85 +223,22 @@ __global__ __launch_bounds__(FRISK_PROF_NT) void profile_add16_kernel(const uint
     constexpr uint32_t NW = (1u << (2 * K)) / 2;                            // 32 768 words: two 16-bit counters each, or one half's 32-bit counters
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
     __shared__ unsigned long long red[2];                                   // max-mer positions counted / the table's grand total
-    const int64_t chunk = int64_t(blockIdx.x);
-    auto clear = [&]() {
-        for (uint32_t b = threadIdx.x; b < NW / 4; b += blockDim.x) reinterpret_cast<uint4*>(hist)[b] = make_uint4(0, 0, 0, 0);
-    };
-    clear();
+    clear_table(hist, NW);
     if (threadIdx.x < 2) red[threadIdx.x] = 0ull;
     __syncthreads();
-    const int64_t w_first = p0 >> 5, w_end = (p1 + 31) >> 5;               // bitmap words that hold [p0, p1)
-    const int64_t wb = w_first + chunk * chunk_words;
-    int64_t we = wb + chunk_words;
-    if (we > w_end) we = w_end;
+    const ProfRange r{codes, inv, low, p0, p1, mask_host};
+    int64_t wb, we;
+    r.chunk(int64_t(blockIdx.x), chunk_words, wb, we);
     const int64_t offK = table_offset(kmin, K);
-    auto topbits = [](int64_t k) -> uint32_t {
-        k = k < 0 ? 0 : (k > 32 ? 32 : k);
-        return uint32_t(0xFFFFFFFF00000000ull >> k);
-    };
-    // one walk over the chunk.  MODE 0: every max-mer into its 16-bit field, and everything that bypasses the table; MODE 1 / 2: the
-    // max-mers of half 0 / 1 into 32-bit counters, nothing else
-    auto walk = [&](auto mode_c) {
-        constexpr int MODE = decltype(mode_c)::value;
-        unsigned long long tot = 0, kpos = 0, nn = 0, mine = 0;
-        for (int64_t wq = wb + threadIdx.x; wq < we; wq += blockDim.x) {
-            const int64_t base = wq << 5;
-            const uint32_t i0 = inv[wq], i1 = inv[wq + 1], l0 = low[wq], l1 = low[wq + 1];
-            const uint32_t c0 = codes[2 * wq], c1 = codes[2 * wq + 1], c2 = codes[2 * wq + 2];
-            const uint32_t inr = topbits(p1 - base) & ~topbits(p0 - base);
-            const uint32_t e0 = i0 | (mask_host ? l0 : 0u), e1 = i1 | (mask_host ? l1 : 0u);
-            const uint64_t V = ~((uint64_t(e0) << 32) | e1);
-            uint64_t F = V;
-            F &= F << 1; F &= F << 2; F &= F << 4;                          // eight countable bases in a row
-            const uint32_t fullm = uint32_t(F >> 32) & inr;
-            const uint64_t lo64 = (uint64_t(c0) << 32) | c1, hi64 = (uint64_t(c1) << 32) | c2;
-#pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                if (fullm & (0x80000000u >> j)) {
-                    const uint32_t code = uint32_t((j < 16 ? lo64 : hi64) >> (48 - 2 * (j & 15))) & 0xFFFFu;
-                    if (MODE == 0) atomicAdd(&hist[code >> 1], 1u << ((code & 1u) * 16u));
-                    else if ((code >> 15) == uint32_t(MODE - 1)) atomicAdd(&hist[code & (NW - 1u)], 1u);
-                }
-            }
-            if (MODE == 0) {
-                mine += uint32_t(__popc(fullm));
-                uint32_t shortm = uint32_t(V >> 32) & ~uint32_t(F >> 32) & inr;
-                while (shortm) {
-                    const int j = __clz(int(shortm));
-                    shortm &= ~(0x80000000u >> j);
-                    const int run = __clzll((long long)(~(V << j)));        // < 8 here
-                    if (run >= kmin) {
-                        const uint32_t c16 = uint32_t((j < 16 ? lo64 : hi64) >> (48 - 2 * (j & 15))) & 0xFFFFu;
-                        atomicAdd(&raw[table_offset(kmin, run) + (c16 >> (16 - 2 * run))], 1ull);
-                    }
-                }
-                const uint64_t NP = ~((uint64_t(i0 & l0) << 32) | (i1 & l1));   // not a PAD
-                uint64_t G = NP;
-                G &= G << 1; G &= G << 2; G &= G << 4;                      // a K-mer can start here (L329): no PAD in reach
-                const uint32_t real = uint32_t(NP >> 32) & inr;
-                tot += __popc(real);
-                nn += __popc(real & (i0 | l0));                             // not an uppercase A/T/G/C (countN, L106-118)
-                kpos += __popc(uint32_t(G >> 32) & inr);
-            }
-        }
-        if (MODE == 0) {
-            for (int o = 32; o > 0; o >>= 1) {
-                tot += __shfl_down(tot, o); kpos += __shfl_down(kpos, o); nn += __shfl_down(nn, o); mine += __shfl_down(mine, o);
-            }
-            if ((threadIdx.x & 63) == 0) {
-                if (tot) atomicAdd(&raw[nprof + 0], tot);
-                if (kpos) atomicAdd(&raw[nprof + 1], kpos);
-                if (nn) atomicAdd(&raw[nprof + 2], nn);
-                if (mine) atomicAdd(&red[0], mine);
-            }
-        }
-    };
-    walk(std::integral_constant<int, 0>{});
+    const unsigned long long counted = wave_sum(walk_words<true>(r, wb, we, kmin, K, true, raw, nprof, [&](uint32_t code) {
+        atomicAdd(&hist[code >> 1], 1u << ((code & 1u) * 16u));             // every max-mer into its 16-bit field
+    }));
+    if ((threadIdx.x & 63) == 0 && counted) atomicAdd(&red[0], counted);
     __syncthreads();
     {   // the table's grand total
         unsigned long long sum = 0;
         for (uint32_t b = threadIdx.x; b < NW; b += blockDim.x) { const uint32_t v = hist[b]; sum += (v & 0xFFFFu) + (v >> 16); }
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+        sum = wave_sum(sum);
         if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&red[1], sum);
     }
     __syncthreads();
@@ -216,70 +250,33 @@ __global__ __launch_bounds__(FRISK_PROF_NT) void profile_add16_kernel(const uint
         }
         return;
     }
-    for (int half = 0; half < 2; ++half) {  // a wrapped field: the chunk again, half by half, in 32-bit counters
+    for (int half = 0; half < 2; ++half) {  // a wrapped field: the chunk again, half by half, in 32-bit counters and nothing else
         __syncthreads();
-        clear();
+        clear_table(hist, NW);
         __syncthreads();
-        if (half == 0) walk(std::integral_constant<int, 1>{}); else walk(std::integral_constant<int, 2>{});
+        walk_words<true>(r, wb, we, kmin, K, false, raw, nprof, HalfTable(hist, K, 2, half));
         __syncthreads();
-        for (uint32_t b = threadIdx.x; b < NW; b += blockDim.x) {
-            const uint32_t v = hist[b];
-            if (v) atomicAdd(&raw[offK + uint32_t(half) * NW + b], (unsigned long long)v);
-        }
+        flush_table32(hist, NW, raw + offK + uint32_t(half) * NW);
     }
 }
 
 // The same counting for kmax > 8 (4^K 32-bit counters no longer fit a CU's LDS): every position's ONE update goes straight to
-// the global table of its order.  A lane owns one 32-position word of the bitmaps as above; 24-bit codes (12 bases).
+// the global table of its order.  A lane owns one 32-position word of the bitmaps as above; 24-bit codes (12 bases), and a
+// grid-stride loop in place of chunks.
 // ~20 ms per 400 Mb - the reference's -k is unbounded (L1197-1206) but its own cost grows with 4^K; this path is for
 // completeness, not speed.
 __global__ __launch_bounds__(256) void profile_add_big_kernel(const uint32_t* __restrict__ codes, const uint32_t* __restrict__ inv,
                                                                const uint32_t* __restrict__ low, int64_t p0, int64_t p1, int kmin,
                                                                int kmax, int mask_host, int nprof,
                                                                unsigned long long* __restrict__ raw) {
-    unsigned long long tot = 0, kpos = 0, nn = 0;
-    const int64_t w_first = p0 >> 5, w_end = (p1 + 31) >> 5;
-    auto topbits = [](int64_t k) -> uint32_t {
-        k = k < 0 ? 0 : (k > 32 ? 32 : k);
-        return uint32_t(0xFFFFFFFF00000000ull >> k);
-    };
-    for (int64_t wq = w_first + int64_t(blockIdx.x) * blockDim.x + threadIdx.x; wq < w_end; wq += int64_t(gridDim.x) * blockDim.x) {
-        const int64_t base = wq << 5;
-        const uint32_t i0 = inv[wq], i1 = inv[wq + 1], l0 = low[wq], l1 = low[wq + 1];
-        const uint32_t c0 = codes[2 * wq], c1 = codes[2 * wq + 1], c2 = codes[2 * wq + 2];
-        const uint32_t inr = topbits(p1 - base) & ~topbits(p0 - base);
-        const uint32_t e0 = i0 | (mask_host ? l0 : 0u), e1 = i1 | (mask_host ? l1 : 0u);
-        const uint64_t V = ~((uint64_t(e0) << 32) | e1);                    // countable bases; position base+j at bit 63-j
-        const uint64_t lo64 = (uint64_t(c0) << 32) | c1, hi64 = (uint64_t(c1) << 32) | c2;
-        uint32_t todo = uint32_t(V >> 32) & inr;
-        while (todo) {
-            const int j = __clz(int(todo));
-            todo &= ~(0x80000000u >> j);
-            int run = __clzll((long long)(~(V << j)));                      // countable bases from here on (<= 32 visible)
-            run = run < kmax ? run : kmax;
-            if (run >= kmin) {
-                const uint32_t c24 = uint32_t((j < 16 ? lo64 : hi64) >> (40 - 2 * (j & 15))) & 0xFFFFFFu;
-                atomicAdd(&raw[table_offset(kmin, run) + (c24 >> (24 - 2 * run))], 1ull);
-            }
-        }
-        const uint64_t NP = ~((uint64_t(i0 & l0) << 32) | (i1 & l1));       // not a PAD
-        uint64_t G = NP;                                                    // a K-mer can start here (L329): no PAD in reach
-        for (int s = 1; s < kmax; ++s) G &= NP << s;
-        const uint32_t real = uint32_t(NP >> 32) & inr;
-        tot += __popc(real);
-        nn += __popc(real & (i0 | l0));                                     // not an uppercase A/T/G/C (countN, L106-118)
-        kpos += __popc(uint32_t(G >> 32) & inr);
+    const ProfRange r{codes, inv, low, p0, p1, mask_host};
+    ProfScalars S;
+    for (int64_t wq = r.w_first() + int64_t(blockIdx.x) * blockDim.x + threadIdx.x; wq < r.w_end(); wq += int64_t(gridDim.x) * blockDim.x) {
+        const ProfWord W = load_word(r, wq);
+        add_runs<24>(W, uint32_t(W.V >> 32) & W.inr, kmin, kmax, raw);
+        S.add<false>(W, kmax);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        tot += __shfl_down(tot, o);
-        kpos += __shfl_down(kpos, o);
-        nn += __shfl_down(nn, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (tot) atomicAdd(&raw[nprof + 0], tot);
-        if (kpos) atomicAdd(&raw[nprof + 1], kpos);
-        if (nn) atomicAdd(&raw[nprof + 2], nn);
-    }
+    S.flush(raw + nprof);
 }
 
 // C_x[q] = D_x[q] + sum_b C_{x+1}[4q+b], in place on a copy of the D tables; one launch per order,

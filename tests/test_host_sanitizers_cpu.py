@@ -1,8 +1,9 @@
 """The library's host-only code under AddressSanitizer + UBSan on the CPU (the GPU pool offers no sanitizers): tools/exp/san_host.cpp
 runs the 2-bit packer - the 8-letter form and, where the host has AVX-512BW + BMI2, the 64-letter form - against a letter-by-letter
 restatement, bitmap -> runs, the FASTA reader and the seek index on awkward files, the HMM on series of awkward lengths, the
-scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes and named shapes against hand-derived values, and the
-window-tile planner (scan_tiles.h): the tiles of all ranks of seeded random shapes partition windows and bases."""
+scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes and named shapes against hand-derived values, the
+window-tile planner (scan_tiles.h): the tiles of all ranks of seeded random shapes partition windows and bases, the region scorer's
+plan (range_plan.h), and phase A's launch plan and streamed pieces (profile_plan.h)."""
 import os
 import shutil
 import subprocess

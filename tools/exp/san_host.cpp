@@ -1,8 +1,9 @@
 // (CPU) the library's host-only headers under AddressSanitizer + UBSan (GPU sanitizers are not available on the pool): random batches
 // through the 2-bit packer (against a letter-by-letter restatement), bitmap -> runs, the HMM fit / Viterbi on random series of awkward
 // lengths, the scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes, named shapes against values worked out by
-// hand, the window-tile planner (scan_tiles.h): every rank's tiles of random shapes together, and the region scorer's plan
-// (range_plan.h): invariants over seeded random batches, named cases, the refusals with their rows, and the memory fit.
+// hand, the window-tile planner (scan_tiles.h): every rank's tiles of random shapes together, the region scorer's plan
+// (range_plan.h): invariants over seeded random batches, named cases, the refusals with their rows, and the memory fit, and phase A's
+// plan (profile_plan.h): the launch of every form over a sweep of ranges, two named shapes, and the pieces of a streamed batch.
 // build + run:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifrisk_amd/csrc
 //               tools/exp/san_host.cpp -o build/san/san_host -lpthread -lz && build/san/san_host
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include "scan_schedule.h"
 #include "scan_tiles.h"
 #include "range_plan.h"
+#include "profile_plan.h"
 #include <fstream>
 #include <unistd.h>
 
@@ -387,7 +389,116 @@ static long long check_range_plan() {             // -> plans made
     return plans;
 }
 
+// Phase A's plan (profile_plan.h).  plan_profile_launch over a sweep: the form follows the rule; the chunks of the forms with a table
+// in LDS cover the range's words with no empty workgroup, on no more than one workgroup per CU; the big form's grid-stride loop
+// (no chunks) has no idle workgroup either; the dynamic LDS fits a CU; grid = 0 exactly for an empty range.  Two named shapes against
+// values worked out by hand.  plan_profile_pieces: ascending, disjoint, together [0, padded_len), each launch within what has arrived.
+static long long check_profile_plan() {           // -> plans made
+    long long plans = 0;
+    const int64_t two30 = int64_t(1) << 30;
+    const int64_t ranges[][2] = {
+        {0, 0}, {77, 77},                                       // empty
+        {0, 1}, {95, 96},                                       // one position
+        {33, 60}, {64, 96},                                     // both ends inside one word / exactly one word
+        {5, 100}, {31, 65}, {1000, 70001},                      // unaligned ends
+        {0, 65535}, {0, 65536}, {0, 131072}, {17, 17 + 65535}, {17, 17 + 65536}, {17, 17 + 131072},
+        {0, two30 - 1}, {0, two30}, {3, 3 + two30 - 1}, {3, 3 + two30},
+        {0, 3300000000}, {31, 3300000000 - 7}};
+    int64_t forms[3] = {0, 0, 0};
+    for (int kmax = 1; kmax <= 12; ++kmax) for (int num_cu : {1, 2, 8, 256}) for (int one_pass = 0; one_pass < 2; ++one_pass) for (const auto& r : ranges) {
+        const int64_t p0 = r[0], p1 = r[1], span = p1 - p0;
+        const ProfileLaunch L = plan_profile_launch(kmax, num_cu, p0, p1, one_pass != 0);
+        ++plans;
+        const ProfileForm want = kmax > 8 ? PROFILE_FORM_BIG : (kmax == 8 && (one_pass || span >= two30)) ? PROFILE_FORM_ONE_PASS : PROFILE_FORM_LDS;
+        CHECK(L.form == want);
+        ++forms[L.form];
+        int64_t words = 0;                                      // the words that hold a position of the range, counted one by one at both ends
+        if (span > 0) words = (p1 - 1) / 32 - p0 / 32 + 1;
+        CHECK(L.nwords == words);
+        CHECK((L.grid == 0) == (span == 0) && L.grid >= 0);
+        CHECK(L.halves == (want == PROFILE_FORM_LDS && kmax == 8 ? 2 : 1) && L.grid % L.halves == 0);
+        CHECK(L.lds_bytes <= size_t(160) * 1024);
+        if (want == PROFILE_FORM_BIG) {
+            CHECK(L.threads == 256 && L.lds_bytes == 0 && L.chunk_words == 0 && L.grid <= 8 * num_cu);
+            if (words > 0) CHECK(int64_t(L.grid - 1) * L.threads < words);                 // no workgroup without a word
+            if (L.grid < 8 * num_cu) CHECK(int64_t(L.grid) * L.threads >= words);          // below the cap: one step of the loop
+            continue;
+        }
+        CHECK(L.threads == 1024);
+        CHECK(L.lds_bytes == (want == PROFILE_FORM_ONE_PASS ? size_t(131072) : std::max<size_t>(16, (size_t(1) << (2 * kmax)) * 4 / size_t(L.halves))));
+        const int64_t chunks = L.grid / L.halves;
+        if (words > 0) CHECK((chunks - 1) * L.chunk_words < words && words <= chunks * L.chunk_words);
+        CHECK(chunks <= std::max<int64_t>(1, num_cu / L.halves));
+        if (span > 0) CHECK(chunks <= std::max<int64_t>(1, span / 65536));
+    }
+    CHECK(forms[PROFILE_FORM_BIG] >= 100 && forms[PROFILE_FORM_ONE_PASS] >= 100 && forms[PROFILE_FORM_LDS] >= 100);    // (the sweep reaches each)
+    {   // the bench shard (synth.c5_shard_lens(8, 0): 40 scaffolds, 410 630 532 bases, with their PADs 410 630 592 positions) at 256 CUs:
+        // 12 832 206 words; 6 265 chunks of 65 536 positions would fit, 256 / 2 halves = 128 are allowed; ceil(12 832 206 / 128) = 100 252
+        // words each (127 x 100 252 = 12 732 004 < 12 832 206 <= 128 x 100 252), so 128 chunks x 2 halves; 4^8 / 2 counters of 4 bytes
+        const ProfileLaunch L = plan_profile_launch(8, 256, 0, 410630592, false);
+        CHECK(L.form == PROFILE_FORM_LDS && L.grid == 256 && L.threads == 1024 && L.lds_bytes == 131072 && L.halves == 2);
+        CHECK(L.chunk_words == 100252 && L.nwords == 12832206);
+    }
+    {   // the whole genome of that bench (all eight shards: 424 scaffolds, 3 285 019 936 positions >= 2^30: one pass) at 256 CUs:
+        // 102 656 873 words, 50 125 chunks would fit, 256 are allowed; ceil(102 656 873 / 256) = 401 004 words each
+        // (255 x 401 004 = 102 256 020 < 102 656 873 <= 256 x 401 004); 4^8 fields of 2 bytes
+        const ProfileLaunch L = plan_profile_launch(8, 256, 0, 3285019936, false);
+        CHECK(L.form == PROFILE_FORM_ONE_PASS && L.grid == 256 && L.threads == 1024 && L.lds_bytes == 131072 && L.halves == 1);
+        CHECK(L.chunk_words == 401004 && L.nwords == 102656873);
+    }
+    {   // the corners: one CU at K = 8 (1 / 2 halves = 0 chunks allowed: one results, also of a single word), K = 1 (16 bytes), one position
+        const ProfileLaunch A = plan_profile_launch(8, 1, 0, 1 << 20, false);
+        CHECK(A.grid == 2 && A.halves == 2 && A.chunk_words == 32768);
+        const ProfileLaunch A1 = plan_profile_launch(8, 1, 0, 32, false);
+        CHECK(A1.grid == 2 && A1.halves == 2 && A1.chunk_words == 1);
+        const ProfileLaunch B = plan_profile_launch(1, 256, 40, 41, false);
+        CHECK(B.grid == 1 && B.lds_bytes == 16 && B.chunk_words == 1 && B.nwords == 1);
+    }
+    // the pieces of a streamed batch
+    auto check_pieces = [&](const std::vector<int64_t>& piece_end, int64_t padded_len) {
+        const std::vector<ProfilePiece> P = plan_profile_pieces(piece_end, padded_len);
+        ++plans;
+        CHECK(!P.empty() && P.size() <= piece_end.size());
+        if (P.empty()) return P;
+        int64_t at = 0, firsts = 0, lasts = 0;
+        size_t prev_piece = 0;
+        for (size_t k = 0; k < P.size(); ++k) {
+            const ProfilePiece& L = P[k];
+            CHECK(L.p0 == at && L.p1 >= L.p0);                  // ascending, disjoint, no gap
+            at = L.p1;
+            CHECK(L.piece < piece_end.size() && (k == 0 || L.piece > prev_piece));
+            prev_piece = L.piece;
+            if (L.piece < piece_end.size() && k + 1 < P.size()) CHECK(L.p1 <= (piece_end[L.piece] - 1) * 32);
+            if (k > 0 && k + 1 < P.size()) CHECK(L.p1 > L.p0);  // between the first and the last only what adds positions
+            firsts += L.first; lasts += L.last;
+            CHECK(L.first == (k == 0) && L.last == (k + 1 == P.size()));
+        }
+        CHECK(at == padded_len && firsts == 1 && lasts == 1);
+        CHECK(P.front().piece == 0 && P.back().piece + 1 == piece_end.size());
+        return P;
+    };
+    for (int64_t piece_words : {1, 2, 3, 1000}) for (int64_t total_words : {1, 2, 3, 4, 7, 1000, 1001, 2999, 3000, 3001}) {
+        std::vector<int64_t> piece_end;
+        for (int64_t a = 0; a < total_words; a += piece_words) piece_end.push_back(std::min(total_words, a + piece_words));
+        const std::vector<ProfilePiece> P = check_pieces(piece_end, total_words * 32);
+        // pieces of one word: the first adds nothing (its only word waits for the next piece's) and launches all the same
+        if (piece_words == 1 && total_words > 1 && !P.empty()) CHECK(P[0].p0 == 0 && P[0].p1 == 0 && P.size() == piece_end.size());
+    }
+    {
+        const std::vector<ProfilePiece> one = check_pieces({5}, 160);                      // a single piece: first and last at once
+        CHECK(one.size() == 1 && one[0].p0 == 0 && one[0].p1 == 160 && one[0].first && one[0].last);
+        const std::vector<ProfilePiece> tail = check_pieces({4, 8, 9}, 288);               // a last piece of one word
+        CHECK(tail.size() == 3 && tail[1].p1 == 224 && tail[2].p0 == 224 && tail[2].p1 == 288);
+        const std::vector<ProfilePiece> none = check_pieces({4, 4, 8}, 256);               // a piece that adds nothing is left out
+        CHECK(none.size() == 2 && none[0].p1 == 96 && none[1].piece == 2 && none[1].p0 == 96 && none[1].p1 == 256);
+        const std::vector<ProfilePiece> ends = check_pieces({1, 1}, 32);                   // ... unless it is the first or the last
+        CHECK(ends.size() == 2 && ends[0].p1 == 0 && ends[1].p0 == 0 && ends[1].p1 == 32);
+    }
+    return plans;
+}
+
 int main() {
+    const long long profile_plans = check_profile_plan();
     const long long range_plans = check_range_plan();
     const long long plans = check_scan_schedule();
     const long long tile_shapes = check_scan_tiles();
@@ -532,6 +643,6 @@ int main() {
         }
         ::unlink(path.c_str());
     }
-    std::printf("%s (%d failed checks; %lld scan schedules; %lld tile plans; %lld range plans; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, tile_shapes, range_plans, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
+    std::printf("%s (%d failed checks; %lld scan schedules; %lld tile plans; %lld range plans; %lld profile plans; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, tile_shapes, range_plans, profile_plans, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
     return fails ? 1 : 0;
 }
