@@ -605,14 +605,14 @@ struct ScanRun {
             B.verdict = c->d_verdict.p;
             B.out_list = list1; B.out_count = cnt;
             B.my_form = 1u;
-            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, false));
+            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, false, sched.kmin1_form));
             B.my_form = 2u;
-            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, true));
+            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, true, sched.kmin1_form));
             B.my_form = 3u;
             B.out_list = list2; B.out_count = cnt + 1;
             HIPC(c, launch_narrow(c->kmax, 8, small_w, false, B, c->num_cu, bulk_chunks, st));
         } else
-        HIPC(c, launch_narrow(c->kmax, sched.bulk, small_w, debug, B, c->num_cu, bulk_chunks, st, false, sched.side));
+        HIPC(c, launch_narrow(c->kmax, sched.bulk, small_w, debug, B, c->num_cu, bulk_chunks, st, false, sched.side, sched.kmin1_form));
         if (sched.bulk == 4) {                  // list 1 (4-bit hand-overs) -> 8-bit -> list 2
             ScanParams H = R;
             H.in_list = list1; H.in_count = cnt;
@@ -696,6 +696,7 @@ struct ScanRun {
             if (shape.rip) { std::memcpy(pi, b + blk.pi, N * 8); std::memcpy(si, b + blk.si, N * 8); std::memcpy(cri, b + blk.cri, N * 8); }
             std::memcpy(seq_index, b + blk.seq_index, N * 4); std::memcpy(status, b + blk.status, N * 4);
         }
+        c->scan_stat[5] = sched.kmin1_form && c->scan_stat[0] == 4 ? 1 : 0;
         c->scan_stat[1] = novf[0] + novf[32] + novf_sample[0];
         c->scan_stat[2] = novf[1] + novf[33] + novf_sample[1];
         if (c->b().tiled)               // descriptor index -> index of the scaffold in the FASTA
@@ -734,7 +735,7 @@ int scan_impl(frisk_ctx* c, int32_t w, int32_t inc, uint32_t flags, int64_t c0, 
     const ScanShape shape = scan_shape_of(c, n, w, inc, flags, dbg_counts || dbg_meta);
     const ScanSchedule sched = plan_scan_schedule(shape);
     if (sched.error) return fail(c, sched.error_code, sched.error);
-    c->scan_stat[0] = 16; c->scan_stat[1] = 0; c->scan_stat[2] = 0; c->scan_stat[3] = 1; c->scan_stat[4] = 0;
+    c->scan_stat[0] = 16; c->scan_stat[1] = 0; c->scan_stat[2] = 0; c->scan_stat[3] = 1; c->scan_stat[4] = 0; c->scan_stat[5] = 0;
 
     ScanRun run{c, shape, sched, seq_index, start, stop, status, kld, gc, pi, si, cri, dbg_counts, dbg_meta,
                 ScanParams(), size_t(1) << (2 * c->kmax), {0, 0}};
@@ -817,6 +818,6 @@ char* frisk_format_rows(int64_t n, const char* const* names, const int32_t* seq_
     return frisk_text::format_all(c, out_len);
 }
 void frisk_free(void* p) { std::free(p); }
-int64_t frisk_last_scan_stat(const frisk_ctx* c, int which) { return (c && which >= 0 && which < 5) ? c->scan_stat[which] : -1; }
+int64_t frisk_last_scan_stat(const frisk_ctx* c, int which) { return (c && which >= 0 && which < 6) ? c->scan_stat[which] : -1; }
 
 }  // extern "C"

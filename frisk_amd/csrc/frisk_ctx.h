@@ -114,8 +114,9 @@ struct frisk_ctx {
     DevBuf<double> d_ig_ring;                  // scan8_kernel: per-workgroup ring of genome-side values by position (40 KB each at 20 positions per lane)
     DevBuf<unsigned int> d_verdict;            // the adaptive width's verdict, written on the device by scan8_decide_kernel: {form, handed, would-have, scored}
     DevBuf<unsigned int> d_ovf_count;          // per row segment 32 counters: [0], [1] the lists' lengths, [8..15] the bulk launch's chunk queues, [16] the 8-bit launch's
-    int64_t scan_stat[5] = {0, 0, 0, 0, 0};    // most recent scan: counter width of the bulk launch, windows handed 4->8, ->16, row segments,
-                                               // 1 = the bulk launch had the side table for period-4 max-mers beside its 4-bit counters
+    int64_t scan_stat[6] = {0, 0, 0, 0, 0, 0}; // most recent scan: counter width of the bulk launch, windows handed 4->8, ->16, row segments,
+                                               // 1 = the bulk launch had the side table for period-4 max-mers beside its 4-bit counters,
+                                               // 1 = the 4-bit bulk launch was the kernel compiled for kmin = 1
     DevBuf<uint32_t> d_big;      // 32-bit tables of the long-window path (scan_big_kernel.h), one slice per workgroup
     DevBuf<int64_t> d_meta;          // {totalLen, exMax, nnTotal} of the finalised profile, on the device
     PinBuf<int64_t> h_meta;          // page-locked mirror, valid after the stream has been synchronised

@@ -65,6 +65,9 @@ struct Lds8 {
     static constexpr uint32_t pre = (orphans + FRISK8_ORPH_CAP * 2 + 15) / 16 * 16;
     // SIDE (below): the side table follows the prefix sums (whose weights carry the side count of the (K-3)-mer's 4-mer in their top bits)
     // (LDS is handed out in pieces of 1280 bytes on gfx950: three workgroups per CU get 42 of them each = 53 760 bytes)
+    // (and 16-byte entries {A, W, pad} where three workgroups per CU still fit - the plain 4-bit form at K = 8, 53 376 of 53 760 bytes -
+    //  so that a position computes one address instead of two: the compiler reads such an entry as ds_read_b64 + ds_read_b32 all the same,
+    //  and the C5 shape measured 43.87 .. 43.97 ms against 43.49 .. 43.62 with the two arrays; round 5, NOTES.md)
     static constexpr uint32_t side = pre + NL * 12;                                // u8[256]: counts of the period-4 max-mers (SIDE)
     static constexpr uint32_t logtab = side + (SIDE ? 256 : 0);                    // {1/c_i, -ln(1/c_i)} x LOGN
     // {1/c, c^2 r_K} for c < 16 (second half per window); the 8-bit form has 128 bytes to spare, not 256: 1/c only, the other computed
@@ -133,6 +136,8 @@ __device__ inline uint32_t wave_sum_u32(uint32_t x) {
 
 // ROLE names the launch (bit 0: the sample of the adaptive width, bit 1: no sliding, hence no ring): the code is otherwise the same, but a profiler's
 // per-kernel statistics then keep the 1/16 sample launches apart from the bulk launches.
+// ROLE bit 2 (KMIN1; the K = 8 4-bit bulk forms): the lowest order is the constant 1 - the default, and what nearly every scan runs at - instead of
+// the argument P.kmin, which such a launch never reads: see "KMIN1" in the kernel body.  Which launches take it is plan_scan_schedule's statement.
 // NT threads, windows of at most NT*ITS bases, BITS per order-8 counter, LOGN: bins of the logarithm table, WPS: waves per SIMD the register allocation must allow (= workgroups per
 // CU * NT / 256).
 // SIDE (K = 8, 4-bit counters): the max-mers of period <= 4 - (x0 x1 x2 x3)(x0 x1 x2 x3): poly-A, (CA)n, (AAAT)n ..., the words that
@@ -151,6 +156,8 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     constexpr int SHW = BITS == 8 ? 2 : 3;               // code >> SHW = dword of the table
     constexpr uint32_t PERM = (32 / BITS) - 1;           // code & PERM = field inside the dword
     static_assert(!SIDE || (KMAX == 8 && BITS == 4 && !DEBUG && NT == 256), "the side table exists for the 4-bit form at K = 8");
+    constexpr bool KMIN1 = (ROLE & 4) != 0;
+    static_assert(!KMIN1 || (KMAX == 8 && BITS == 4 && !DEBUG && !(ROLE & 1)), "the kmin = 1 skeleton exists for the 4-bit bulk forms at K = 8");
     using L = Lds8<KMAX, BITS, LOGN, NT, SIDE>;
     // the order-K table is cleared whole when that takes no more stores per thread than a lane has positions (measured: 64 KiB
     // for windows of 2000 bases is the one case where every position clearing its own dword is cheaper)
@@ -391,8 +398,14 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             // The thread index and the lowest order, opaque to the optimiser from here on: otherwise it hoists every
             // per-position constant that depends on them (20 x {tid*20+it, masks, table offsets}: > 100 registers and
             // dozens of spilled scalars) out of the window loop and keeps them alive across all stages.
-            int tid = tid0, kmin = kmin0;
-            asm volatile("" : "+v"(tid), "+s"(kmin));
+            // KMIN1: the lowest order is known where the kernel is compiled.  Every order is then on - the selects of stage 3's rx / ox /
+            // wm, the `kmin <= 4 / 3 / 2 / 1` branches around its DPP sums, the masks of W4 / W5 and short_word's `rs >= kmin` are
+            // gone -, and the small tables' offsets are constants that fold into the ds_ instructions' offset fields.  The thread index
+            // stays opaque: what it keeps out of the window loop is per position, what kmin folds is per window.  Same operations on
+            // the same values in the same order: the same bits as the generic skeleton run at kmin = 1.
+            int tid = tid0, kmin = KMIN1 ? 1 : kmin0;
+            if constexpr (KMIN1) asm volatile("" : "+v"(tid));
+            else asm volatile("" : "+v"(tid), "+s"(kmin));
             asm volatile("" : "+s"(Pk));            // (kernel arguments used once per window: re-read from their segment, see Pk)
             const int lane = tid & 63;
             const WinScaf ws = {d.off, d.size, d.base0, d.cand0, d.ncand, d.j0, d.kind};
@@ -867,6 +880,10 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             };
             // ---- stage 3: window constants r_x = 4^x / D_x, D_x = (S-(x-1))*2 (L401-409), and the shared prefix tables
             uint32_t pend0 = 0xFFFFFFFFu, pend1 = 0xFFFFFFFFu;      // PLACE: (list entry << 16 | fake code) of the orphans this thread folded in
+            // (these depend on S alone, and S is the same from window to window in sequence without N or soft-masking.  Keeping the nine
+            //  quotients in a register pair with the S they belong to, and rstab's second half as it stands, for the windows with that
+            //  S - round 5: 43.47 .. 43.58 ms on the C5 shape against 43.49 .. 43.62, inside the rounds' spread; not taken.  The divisions
+            //  run beside the stage's table reads, and the kept pair was live across the scoring loop.)
             double r_lane = 0.0;
             if (lane <= 8) r_lane = div_exact(double(1u << (2 * lane)), double(int32_t((S - (lane - 1)) * 2)));
             auto r_of = [&](int x) -> double {

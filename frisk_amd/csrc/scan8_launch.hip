@@ -1,12 +1,12 @@
 // scan8_launch.hip - the launches of scan8_kernel.h (narrow order-K counters, several workgroups per CU) and of the adaptive width's
 // verdict: launch_narrow and launch_scan8_decide of scan_launch.h.  The 8-bit forms and K = 6, 7 are instantiated here, the 4-bit
-// forms in scan8_launch4.hip.  gfx950 (MI355X) only.
+// forms in scan8_launch4.hip and scan8_launch41.hip.  gfx950 (MI355X) only.
 #include <hip/hip_runtime.h>
 
 #include "scan8_launch.h"
 #include "scan_schedule.h"          // FRISK_K7_WPS, FRISK_SIDE_SHARE
 
-// (instantiated in scan8_launch4.hip)
+// (instantiated in scan8_launch4.hip and scan8_launch41.hip)
 #define FRISK_SCAN8_4BIT_ELSEWHERE(ITS_, DBG_, ROLE_, SIDE_) extern FRISK_SCAN8_4BIT(ITS_, DBG_, ROLE_, SIDE_)
 FRISK_SCAN8_4BIT_FORMS(FRISK_SCAN8_4BIT_ELSEWHERE)
 #undef FRISK_SCAN8_4BIT_ELSEWHERE
@@ -14,8 +14,17 @@ FRISK_SCAN8_4BIT_FORMS(FRISK_SCAN8_4BIT_ELSEWHERE)
 // one launch of the narrow-counter K = 8 kernel: counter width, window class (<= 2048 / <= 5120 bases), debug dump
 // (side: 4-bit counters with the side table for the period-4 max-mers)
 hipError_t launch_narrow(int kmax, int bits, bool small_w, bool debug, const ScanParams& P, int num_cu, int64_t work_items, hipStream_t st,
-                         bool sample, bool side) {
+                         bool sample, bool side, bool kmin1) {
     const bool slides = P.slide_pp > 0 && P.in_list == nullptr;        // (else: the instantiation without the ring, ROLE bit 1)
+    // the 4-bit bulk forms with the lowest order compiled in (ROLE bit 2): the schedule asks for them, only a launch they exist for takes them
+    if (kmin1 && !sample && bits == 4 && kmax == 8 && !debug && P.in_list == nullptr && P.kmin == 1) {
+#define FRISK_L1(ITS_, SIDE_) return slides ? launch_scan8<8, 256, ITS_, 4, 64, 3, false, 4, SIDE_>(P, num_cu, work_items, st) \
+                                            : launch_scan8<8, 256, ITS_, 4, 64, 3, false, 6, SIDE_>(P, num_cu, work_items, st)
+        if (side) { if (small_w) FRISK_L1(8, true); FRISK_L1(20, true); }
+        if (small_w) FRISK_L1(8, false);
+        FRISK_L1(20, false);
+#undef FRISK_L1
+    }
     if (sample) {           // the sample of the adaptive width: 4-bit counters, its own name in kernel statistics; it runs the
                             // side-table form and counts what the plain form would have handed on as well
         if (small_w) return slides ? launch_scan8<8, 256, 8, 4, 64, 3, false, 1, true>(P, num_cu, work_items, st)

@@ -1,6 +1,6 @@
 // scan_launch.h - the scan kernels as frisk_abi.hip sees them: one plain function per launch.  The kernels themselves are
 // instantiated in scan_launch.hip (16-bit form, two-workgroup form, long-window form, the rows' scalar tail) and in
-// scan8_launch.hip / scan8_launch4.hip (narrow counters), so that the units compile side by side and an experiment on one
+// scan8_launch.hip / scan8_launch4.hip / scan8_launch41.hip (narrow counters), so that the units compile side by side and an experiment on one
 // kernel family rebuilds that family alone.  Every function enqueues on `st` and returns hipGetLastError() of its launch.
 // Internal to the library: hidden, not part of the C ABI of include/frisk_hip.h.
 #pragma once
@@ -21,9 +21,10 @@ FRISK_INTERNAL hipError_t launch_finish_rows(int grid, hipStream_t st, int64_t n
 
 // scan8_launch.hip
 // one launch of the narrow-counter K = 8 kernel: counter width, window class (<= 2048 / <= 5120 bases), debug dump
-// (side: 4-bit counters with the side table for the period-4 max-mers)
+// (side: 4-bit counters with the side table for the period-4 max-mers; kmin1: the 4-bit bulk form compiled for the lowest order 1 -
+//  ScanSchedule::kmin1_form says when)
 FRISK_INTERNAL hipError_t launch_narrow(int kmax, int bits, bool small_w, bool debug, const ScanParams& P, int num_cu, int64_t work_items,
-                                        hipStream_t st, bool sample = false, bool side = false);
+                                        hipStream_t st, bool sample = false, bool side = false, bool kmin1 = false);
 // the adaptive width's verdict (scan8_decide_kernel), one thread behind the sample
 FRISK_INTERNAL hipError_t launch_scan8_decide(const unsigned int* counts, unsigned int n_sampled, int side_ok, unsigned int* verdict,
                                               hipStream_t st);

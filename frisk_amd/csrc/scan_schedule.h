@@ -74,6 +74,7 @@ struct ScanSchedule {
     int32_t orphan_cap;
     // the narrow-counter path
     bool narrow8, small_w, can_slide, short_scan, dealt, sample, side;
+    bool kmin1_form;        // the 4-bit bulk launches take scan8_kernel's instantiations with the lowest order compiled in (ROLE bit 2)
     int64_t chunk8;         // consecutive windows per chunk
     int32_t slide_pp;       // ScanParams::slide_pp
     int64_t ring_slices;    // workgroup slices of the genome-value ring, 0 = no ring
@@ -221,6 +222,11 @@ inline ScanSchedule plan_scan_schedule(const ScanShape& s) {
         S.sel_mode = 2;
     }
     S.bulk = bulk; S.side = side;
+    // The 4-bit bulk forms exist a second time, compiled for the lowest order 1 (scan8_kernel.h, KMIN1): K = 8 and kmin = 1 - the
+    // default, and the reference's - take them, whatever width the bulk turns out to have (a launch of another width follows its own
+    // rule: launch_narrow); the debug instantiations, K = 6 and 7 and every other kmin keep the kernel that reads kmin as an argument,
+    // and so does a scan that asks for it (FRISK_SCAN_GENERIC: the two are compared bit for bit).
+    S.kmin1_form = narrow8 && s.kmin == 1 && !debug && !(s.flags & FRISK_SCAN_GENERIC);
     // The last sixteenth of a long scan goes to a second stream and starts when the kernels of the first fifteen are done:
     // it runs while their rows travel to the host (16 MB per 410 k windows: 0.36 ms that used to follow the scan).  The
     // cut is a multiple of 16 chunks: chunk numbering and the sample's stride stay aligned across it.

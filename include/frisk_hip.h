@@ -51,6 +51,8 @@ enum {
 #define FRISK_SCAN_SIDE4       1024u /* K = 8: as FRISK_SCAN_BITS4, with the side table for the max-mers of period <= 4 (poly-A, (CA)n, (AAAT)n
                                         ...) beside the 4-bit counters - the form a long scan of repeat-rich sequence picks by itself.
                                         Results are the same bits. */
+#define FRISK_SCAN_GENERIC     2048u /* K = 8, lowest order 1: the 4-bit bulk launch keeps the kernel that reads the lowest order as an argument
+                                        instead of the one compiled for 1 (what such a scan otherwise takes).  Results are the same bits. */
 
 /* per-row status bits written to `status` by frisk_scan */
 #define FRISK_ROW_KEPT        1u      /* window passed the < 30 % non-ACGT filter (L237-241)          */
@@ -353,7 +355,8 @@ int frisk_scan_ivom(frisk_ctx* ctx, int32_t w, int32_t inc, uint32_t flags, int6
  * which = 0: counter width of the bulk launch (4 or 8; 16 = the narrow kernel was not used),
  *         1: windows handed from 4-bit to 8-bit counters,   2: windows handed on to 16-bit counters,
  *         3: row segments (2: the last sixteenth of a long scan ran on a second stream while the rows of the rest went to the host),
- *         4: 1 = the 4-bit bulk launch counted the max-mers of period <= 4 in its side table (FRISK_SCAN_SIDE4 / picked by the sample). */
+ *         4: 1 = the 4-bit bulk launch counted the max-mers of period <= 4 in its side table (FRISK_SCAN_SIDE4 / picked by the sample),
+ *         5: 1 = the 4-bit bulk launch ran the kernel compiled for the lowest order 1 (K = 8, kmin = 1, no FRISK_SCAN_GENERIC). */
 int64_t frisk_last_scan_stat(const frisk_ctx* ctx, int which);
 
 /* The rows of the score table as text, exactly as the reference's scan loop writes them (L1487-1494): tab-separated

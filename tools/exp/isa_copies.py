@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""(CPU) device assembly of the unit that holds the 4-bit narrow-counter kernels (scan8_launch4.hip); for the K = 8 / 4-bit bulk kernels (plain and SIDE) the copies of the scoring loop:
+"""(CPU) device assembly of the units that hold the 4-bit narrow-counter kernels (scan8_launch4.hip, scan8_launch41.hip); for the K = 8 / 4-bit bulk kernels (plain and SIDE, each with kmin as an argument and compiled for kmin = 1) the copies of the scoring loop:
 instructions per position and scratch accesses in each.  Usage: python tools/exp/isa_copies.py [extra -D flags]
 (--asm FILE: read that device assembly instead of compiling.)  Behind the runs of positions, the straight-line copies one by one: every
 basic block that scores at least half a lane's positions (the unrolled copies of the K = 8 scoring loop are one block each), with its
@@ -9,17 +9,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from __graft_entry__ import HIPCC, HIP_FLAGS, CSRC
 os.makedirs(os.path.join(ROOT, "build/isa"), exist_ok=True)
-asm = os.path.join(ROOT, "build/isa/scan8_launch4.s")
 flags = sys.argv[1:]
 given = flags.index("--asm") if "--asm" in flags else -1
 if given >= 0:
-    asm, flags = flags[given + 1], flags[:given] + flags[given + 2:]
+    asms, flags = [flags[given + 1]], flags[:given] + flags[given + 2:]
 else:
-    subprocess.run([HIPCC] + HIP_FLAGS + flags + ["--cuda-device-only", "-S", "-o", asm, os.path.join(CSRC, "scan8_launch4.hip")],
-                   check=True, stderr=subprocess.DEVNULL)
-L = open(asm).read().split('\n')
+    asms = [os.path.join(ROOT, "build/isa/%s.s" % u) for u in ("scan8_launch4", "scan8_launch41")]
+    for out in asms:
+        subprocess.run([HIPCC] + HIP_FLAGS + flags + ["--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, os.path.basename(out)[:-2] + ".hip")],
+                       check=True, stderr=subprocess.DEVNULL)
+L = [l for f in asms for l in open(f).read().split('\n')]
 for tag, kern in (('plain', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb0EEv10ScanParams'),
-                  ('side', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb1EEv10ScanParams')):
+                  ('side', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi0ELb1EEv10ScanParams'),
+                  ('plain_kmin1', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi4ELb0EEv10ScanParams'),
+                  ('side_kmin1', '_Z12scan8_kernelILi8ELi256ELi20ELi4ELi64ELi3ELb0ELi4ELb1EEv10ScanParams')):
+    if not any(l.startswith(kern + ':') for l in L): continue        # (--asm: one unit's kernels)
     a = next(i for i, l in enumerate(L) if l.startswith(kern + ':'))
     b = next(i for i in range(a, len(L)) if 's_endpgm' in L[i])
     K = L[a:b]
