@@ -16,6 +16,7 @@ KVEC_MAX_K, KVEC_THREADS, KVEC_GRID_CAP, KVEC_EMPTY_ORDER, KVEC_ORDER_SHIFT = 7,
 RANGES_BIG = 0x10000                                                                                 # frisk_score_ranges
 PANEL_MAX, PANEL_TILE = 64, 8                                                                        # frisk_score_ranges_panel
 EXPLAIN_MAX, EXPLAIN_NONE = 64, 0xFFFFFFFF                                                           # frisk_explain_ranges
+REFINE_MAX_FLANK = 65536                                                                             # frisk_refine_ranges
 
 # every symbol include/frisk_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -64,6 +65,7 @@ SYMBOLS = [
     ("frisk_score_ranges_panel", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     ("frisk_explain_ranges", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint32, C.c_int32, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P, _P, _P, _P, _P]),
+    ("frisk_refine_ranges", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_uint32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("frisk_profile_reset", C.c_int, [_P]),
     ("frisk_profile_add", C.c_int, [_P, C.c_int, C.c_int64, C.c_int64]),
     ("frisk_seq_padded_len", C.c_int64, [_P]),

@@ -154,7 +154,7 @@ void frisk_host_free(frisk_ctx* c, void* ptr) {
 }
 double frisk_last_kernel_ms(const frisk_ctx* cc, int which) {
     frisk_ctx* c = const_cast<frisk_ctx*>(cc);
-    if (!c || which < 0 || which >= 8) return -1.0;
+    if (!c || which < 0 || which >= 9) return -1.0;
     if (which == 1 && c->ms_pending[1]) {           // the profile kernel's events are read on demand: no sync in profile_add
         float ms = 0;
         if (hipEventSynchronize(c->evp1) == hipSuccess && hipEventElapsedTime(&ms, c->evp0, c->evp1) == hipSuccess) c->ms[1] = ms;

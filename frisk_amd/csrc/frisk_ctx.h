@@ -49,7 +49,7 @@ struct frisk_ctx {
     int num_cu = 256;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double ms[8] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // frisk_last_kernel_ms: scan, profile_add, pack / load, window vectors, score ranges, the panel, null sequences, explain
+    double ms[9] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // frisk_last_kernel_ms: scan, profile_add, pack / load, window vectors, score ranges, the panel, null sequences, explain, refine
     std::string err;
 
     // sequence batches: bat[cur] is the resident one; the other slot receives the next batch while the resident one is

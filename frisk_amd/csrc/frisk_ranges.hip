@@ -1,7 +1,8 @@
 // frisk_ranges.hip - the region scorer of the C ABI (include/frisk_hip.h): frisk_score_ranges, frisk_score_ranges_panel and
 // frisk_explain_ranges - the scan loop's columns (KLD, GC, RIP indices) of arbitrary ranges of the resident batch against the
 // context's finalised profile (range_kernels.h), against every profile of its panel in one pass (panel_kernels.h), and with the
-// largest KLD terms of each range (explain_kernels.h) - and the panel's three calls.  What the host decides is range_plan.h's: the
+// largest KLD terms of each range (explain_kernels.h) -, the panel's three calls, and frisk_refine_ranges, which moves a range's
+// boundaries to the base (refine_kernels.h).  What the host decides is range_plan.h's: the
 // row checks, the rows longest first (the workgroups of a launch take its list by grid stride) and their split between the two
 // forms.  An entry point checks its call, plans it, and composes the steps below with its own kernels, buffers and timing slot:
 // upload the plan, reserve the long form's scratch, queue both launches on the context's stream - a range the short form cannot
@@ -14,6 +15,7 @@
 #include "range_kernels.h"
 #include "panel_kernels.h"
 #include "explain_kernels.h"
+#include "refine_kernels.h"
 
 namespace {
 
@@ -36,8 +38,11 @@ struct RangeCall {
     uint32_t* status;
     double *kld, *gc, *pi, *si, *cri;
     int64_t* nn;
+    bool scored = true;         // the call returns kld and gc (frisk_refine_ranges does not)
     bool rip() const { return (flags & FRISK_SCAN_RIP) != 0; }
-    bool arrays_given() const { return seq_index && start && stop && status && kld && gc && nn && (!rip() || (pi && si && cri)); }
+    bool arrays_given() const {
+        return seq_index && start && stop && status && nn && (!scored || (kld && gc && (!rip() || (pi && si && cri))));
+    }
 };
 
 // the device side of a call: the plan's arrays and the score columns (freed on every return)
@@ -276,6 +281,63 @@ extern "C" int frisk_explain_ranges(frisk_ctx* c, const int32_t* seq_index, cons
     HIPC(c, hipMemcpyAsync(pg, E.pg, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(term, E.term, NS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return finish_call(c, 7);
+}
+
+extern "C" int frisk_refine_ranges(frisk_ctx* c, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                                   uint32_t flags, int32_t flank, int32_t order, uint32_t* status, int64_t* nn, int64_t* new_start,
+                                   int64_t* new_stop, int64_t* gain_start, int64_t* gain_stop, int64_t* flank_used) {
+    if (!c) return FRISK_E_ARG;
+    const std::string who = "frisk_refine_ranges";
+    const RangeCall A = {seq_index, start, stop, n, flags & FRISK_RANGES_BIG, status, nullptr, nullptr, nullptr, nullptr, nullptr, nn, false};
+    const char* bad = refine_args_problem(flank, order, c->kmin, c->kmax);
+    const std::string early = bad ? std::string(": ") + bad : std::string();
+    if (int rc = check_call(c, who, A, bad ? early.c_str() : nullptr, c->profile_final, ": no finalised profile",
+                            new_start && new_stop && gain_start && gain_stop && flank_used)) return rc == RANGE_NOTHING_TO_DO ? FRISK_OK : rc;
+    // the rows of the range kernels are the cores (range_plan.h: plan_refine).  Two workgroups of the short form per CU below
+    // kmax = 8: the mode's table takes 8 KB of LDS beside the form's
+    const frisk_ctx::Batch& B = c->b();
+    const bool all_long = (A.flags & FRISK_RANGES_BIG) != 0 || c->kmax > 8;
+    const RefinePlan R = plan_refine(B.n_seq, B.seq_len.data(), B.seq_off.data(), seq_index, start, stop, n, flank, order, c->kmin, c->kmax,
+                                     all_long, c->num_cu, 2);
+    const RangePlan& plan = R.plan;
+    if (plan.error_code) return fail(c, plan.error_code, who + ": " + plan.error);
+    HIPC(c, hipSetDevice(c->device));
+    if (int rc = settle_stream(c)) return rc;
+    RangeBufs D;
+    DevBuf<int64_t> d_geom, d_host, d_out;
+    RefineParams E = RefineParams();
+    int64_t wgs = 0, stride = 0;
+    if (int rc = upload_plan(c, A, plan, 1, D, E.R)) return rc;         // (kld and gc of the cores: written, not returned)
+    const RangeParams P = E.R;
+    const size_t N = size_t(n), n_words = size_t(1) << (2 * (order + 1));
+    HIPC(c, d_geom.reserve(R.geom.size(), R.geom.size()));
+    HIPC(c, d_host.reserve(n_words, n_words));
+    HIPC(c, d_out.reserve(5 * N, 5 * N));
+    HIPC(c, hipMemcpyAsync(d_geom.p, R.geom.data(), R.geom.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    E.geom = d_geom.p; E.host_lp = d_host.p; E.order = order;
+    E.new_start = d_out.p; E.new_stop = d_out.p + N; E.gain_start = d_out.p + 2 * N; E.gain_stop = d_out.p + 3 * N;
+    E.flank_used = d_out.p + 4 * N;
+    if (int rc = reserve_long_scratch(c, plan, 0, wgs, stride)) return rc;
+    HIPC(c, hipEventRecord(c->ev0, c->stream));
+    refine_host_kernel<<<grid_for(int64_t(n_words), 256, c->num_cu * 8), 256, 0, c->stream>>>(c->d_sym.p + table_offset(c->kmin, order + 1),
+                                                                                           int64_t(n_words), d_host.p);
+    HIPC(c, hipGetLastError());
+    if (plan.n_short()) {
+        const size_t lds = range_lds(c->kmin, c->kmax).total;
+        E.R = short_list(P, plan, D);
+        HIPC(c, launch_with_lds(c, refine_short_kernel<true>, refine_short_kernel<false>, E, plan.grid_short, lds));
+    }
+    if (plan.long_cap) {
+        E.R = long_list(P, plan, D);
+        refine_long_kernel<<<int(wgs), FRISK_RANGE_BIG_NT, 0, c->stream>>>(E, c->d_big.p, stride);
+        HIPC(c, hipGetLastError());
+    }
+    HIPC(c, hipEventRecord(c->ev1, c->stream));
+    HIPC(c, hipMemcpyAsync(status, P.status, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(nn, P.nn, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    int64_t* const out[5] = {new_start, new_stop, gain_start, gain_stop, flank_used};
+    for (size_t k = 0; k < 5; ++k) HIPC(c, hipMemcpyAsync(out[k], d_out.p + k * N, N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    return finish_call(c, 8);
 }
 
 extern "C" int32_t frisk_panel_size(const frisk_ctx* c) { return c ? c->panel_n : 0; }

@@ -20,7 +20,7 @@
 //
 // A FORM hides the table format (ShortForm<K8>, LongForm: NT, tables, count, walk, release).  A MODE is what is done with a row
 // whose tables are ready: PlainMode here scores inside the walk (at K = 8 in a loop of its own, see there); panel_kernels.h and
-// explain_kernels.h bring theirs.  The row loop (range_row_loop) is written once for every form and mode; a __global__ entry
+// explain_kernels.h bring theirs, refine_kernels.h one that does not score at all.  The row loop (range_row_loop) is written once for every form and mode; a __global__ entry
 // point declares its LDS, makes a form and a mode and runs the loop.
 //
 // FP64 throughout, no MFMA, no floating-point atomics.

@@ -73,6 +73,57 @@ inline RangePlan plan_ranges(int32_t n_seq, const int64_t* seq_len, const int64_
     return R;
 }
 
+// ---- frisk_refine_ranges ----------------------------------------------------------------------------------------------------
+#define FRISK_REFINE_MAX_FLANK 65536
+#define FRISK_REFINE_GEOM 6         // entries of a row's geometry
+
+// why a call's flank or order is refused (nullptr: they are fine); the chain of order r reads the counts of order r + 1
+inline const char* refine_args_problem(int32_t flank, int32_t order, int kmin, int kmax) {
+    if (flank < 1 || flank > FRISK_REFINE_MAX_FLANK) return "flank outside 1 .. 65536";
+    if (order < 0 || order + 1 < kmin || order + 1 > kmax) return "the chain of order r reads the counts of order r + 1, which must lie in kmin .. kmax";
+    return nullptr;
+}
+
+// The plan of the CORES [a + Fe, b - Fe), Fe = min(flank, (b - a) / 4), as plan_ranges plans any rows, and per caller's row the
+// geometry of the search: resident position of the scaffold's first base, a, b, Fe, the bases searched left of a (the flank
+// clipped at the scaffold's first base) and right of b (clipped at its last).  A region of fewer than four bases has Fe = 0: its
+// core is the region itself - it takes a workgroup for its status and nn, which only the device can tell - and nothing is searched.
+struct RefinePlan {
+    RangePlan plan;                 // error_code / error: a refused call, nothing else is set
+    std::vector<int64_t> geom;      // FRISK_REFINE_GEOM per caller's row
+};
+inline RefinePlan plan_refine(int32_t n_seq, const int64_t* seq_len, const int64_t* seq_off, const int32_t* seq_index, const int64_t* start,
+                              const int64_t* stop, int64_t n, int32_t flank, int32_t order, int kmin, int kmax, bool all_long, int num_cu,
+                              int per_cu_short) {
+    RefinePlan R;
+    auto refuse = [&](const std::string& what) {
+        R = RefinePlan();
+        R.plan.error_code = FRISK_E_ARG;
+        R.plan.error = what;
+        return R;
+    };
+    if (const char* bad = refine_args_problem(flank, order, kmin, kmax)) return refuse(bad);
+    std::vector<int64_t> core_start(static_cast<size_t>(n)), core_stop(static_cast<size_t>(n));
+    R.geom.resize(size_t(n) * FRISK_REFINE_GEOM);
+    for (int64_t r = 0; r < n; ++r) {
+        const int32_t s = seq_index[r];
+        if (s < 0 || s >= n_seq) return refuse("sequence index out of range in row " + std::to_string(r));
+        const int64_t a = start[r], b = stop[r], L = seq_len[size_t(s)];
+        if (a < 0 || b <= a || b > L || b - a > int64_t(0x7FFFFFFF))
+            return refuse("range outside the scaffold (or empty, or of 2^31 bases or more) in row " + std::to_string(r));
+        const int64_t fe = std::min<int64_t>(flank, (b - a) / 4);
+        core_start[size_t(r)] = a + fe;
+        core_stop[size_t(r)] = b - fe;
+        int64_t* g = R.geom.data() + size_t(r) * FRISK_REFINE_GEOM;
+        g[0] = seq_off[size_t(s)]; g[1] = a; g[2] = b; g[3] = fe;
+        g[4] = std::min(fe, a);
+        g[5] = std::min(fe, L - b);
+    }
+    R.plan = plan_ranges(n_seq, seq_len, seq_off, seq_index, core_start.data(), core_stop.data(), n, kmax, all_long, num_cu, per_cu_short, 0);
+    if (R.plan.error_code) R.geom.clear();
+    return R;
+}
+
 // The long form's workgroups that fit: each takes `stride` 32-bit words of tables and slice_bytes more (explain); half of the
 // free memory may go to them, beside what the table buffer (have_words) holds already.  The device is asked for free_bytes only
 // when the buffer is too small for `want` or a slice is needed; this is what is made of the answer.

@@ -632,6 +632,22 @@ class Engine:
                                                    _ptr(r.n_present), _ptr(r.code), _ptr(r.count), _ptr(r.pw), _ptr(r.pg), _ptr(r.term)))
         return r
 
+    def refine_ranges(self, seq_index, start, stop, flank, order, big=False):
+        """frisk_refine_ranges: the boundaries of the ranges [start[r], stop[r]) moved within +- flank bases to the change point of
+        a likelihood ratio between an order-`order` chain trained on the range's core and the host's (csrc/refine_kernels.h; the
+        definition is refine.py's).  Returns a refine.RefineResult with seq_index, start, stop (as given), status and nn (the
+        core's), new_start, new_stop (0-based, half-open), gain_start, gain_stop (int64, units of 2^-32 bit) and flank_used."""
+        from .refine import RefineResult
+        seq_index, start, stop = self._range_rows(seq_index, start, stop)
+        n = int(seq_index.size)
+        new = lambda: np.zeros(n, np.int64)                                # noqa: E731
+        r = RefineResult(seq_index=seq_index, start=start, stop=stop, status=np.zeros(n, np.uint32), nn=new(), new_start=new(),
+                         new_stop=new(), gain_start=new(), gain_stop=new(), flank_used=new())
+        self._check(self._lib.frisk_refine_ranges(self._ctx, _ptr(seq_index), _ptr(start), _ptr(stop), n, _ffi.RANGES_BIG if big else 0,
+                                                  int(flank), int(order), _ptr(r.status), _ptr(r.nn), _ptr(r.new_start), _ptr(r.new_stop),
+                                                  _ptr(r.gain_start), _ptr(r.gain_stop), _ptr(r.flank_used)))
+        return r
+
     def scan_stat(self):
         """(counter width of the bulk launch, windows handed 4->8 bit, windows handed on to 16 bit, row segments) of the last scan."""
         return tuple(int(self._lib.frisk_last_scan_stat(self._ctx, i)) for i in range(4))

@@ -312,6 +312,19 @@ class HotPath:
         seq, start, stop, rip = self._regionArrays(args, querySeq, regions)
         return self.engine.explain_ranges(seq, start, stop, top_n, rip=rip)
 
+    def refineRegions(self, args, querySeq, regions, flank, order, genomeKmers=None):
+        """The regions' boundaries moved to the base (Engine.refine_ranges: a likelihood-ratio change point within +- flank bases
+        of each boundary, refine.py).  The profile and `querySeq` as in scoreRegions, the same checks of the records.  Returns the
+        RefineResult, rows in the order of `regions`; `querySeq` stays resident for a later scoreResident()."""
+        self._installProfile(args, genomeKmers)
+        seq, start, stop, _ = self._regionArrays(args, querySeq, regions)
+        return self.engine.refine_ranges(seq, start, stop, flank, order)
+
+    def scoreResident(self, args, seq_index, start, stop):
+        """Engine.score_ranges on the batch and profile a region call left in place: rows (seq_index, start, stop) of it."""
+        rip = bool(getattr(args, "RIP", False)) and args.minWordSize <= 2
+        return self.engine.score_ranges(seq_index, start, stop, rip=rip)
+
     def _regionArrays(self, args, querySeq, regions):
         """scoreRegions / scoreRegionsPanel: make `querySeq` resident and turn the records into (seq_index, start, stop, rip)."""
         self._load(querySeq)

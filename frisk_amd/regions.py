@@ -61,6 +61,23 @@ region upper-cased), share = term / windowKLD (`.` when the KLD is 0), floats as
 positive, that of a present but under-represented word negative - a KLD is what is left after they cancel, so shares can exceed 1
 and the tail of a short region's list, which holds every word it has, is negative.  --topKmers goes with --null (the terms are
 taken before the null batch replaces the resident one) and not with --donors.
+
+    python -m frisk_amd.regions -H host.fa --bed anomalies.bed --refine 2000                   where does each region start and end?
+
+Every region the scanner yields has boundaries on a window grid.  --refine F moves each boundary, within F bases on either side, to a
+likelihood-ratio change point (HotPath.refineRegions -> frisk_refine_ranges, csrc/refine_kernels.h; refine.py is the definition): a
+Markov chain of order --refineOrder r is trained on the region's core - the region without min(F, length / 4) bases at each end,
+where it is certainly the island - and compared base by base with the host's chain over both flanks; each boundary goes where the
+cumulative log-likelihood ratio is extreme, and on a tie the shorter region wins.  The default order is min(max(2, kmin - 1), kmax -
+1): LOW on purpose - a core of a few kilobases cannot train a long context, and at order 5 the cut is off by kilobases (DESIGN.md
+section 17).  -O is byte for byte the file of the same run without --refine; the refined regions are scored by a second call on the
+still-resident query.  --refineOutfile (in --tempDir, default region_refined.tsv): header `name start stop length id newStart newStop
+newLength shiftStart shiftStop llrStart llrStop flank windowKLD newKLD note`, one row per input record in input order; coordinates
+1-based inclusive as in -O; shift = new minus old; llr = what the move gains in log-likelihood ratio, in bits; flank = the bases
+searched on either side of a boundary; windowKLD / newKLD = the region's and the refined region's KLD as -O prints one.  note: `.`,
+`unresolved` (30 % or more of the core is not uppercase A/C/G/T: left as it was) or `short` (fewer than 4 bases: left as it was).
+--refinedBed (in --tempDir, default regions_refined.bed): name, newStart, newStop (0-based half-open), id - ready to be fed back
+through --bed.  --refine does not go with --donors, --null or --topKmers: a second run on the refined BED gives those.
 """
 import argparse
 import gzip
@@ -104,6 +121,14 @@ def build_parser():
     p.add_argument("--topKmers", type=int, default=None, help="list the N (1..64) k-mers of --maxWordSize letters with the largest "
                    "terms of each region's KLD")
     p.add_argument("--kmerOutfile", type=str, default="region_kmers.tsv", help="with --topKmers: the per-region k-mer table, written "
+                   "in --tempDir")
+    p.add_argument("--refine", type=int, default=None, metavar="F", help="move each region's boundaries, within F bases (1..65536) on "
+                   "either side, to a likelihood-ratio change point")
+    p.add_argument("--refineOrder", type=int, default=None, help="with --refine: order r of the two Markov chains (default: "
+                   "min(max(2, kmin - 1), kmax - 1); keep it low)")
+    p.add_argument("--refineOutfile", type=str, default="region_refined.tsv", help="with --refine: the table of refined boundaries, "
+                   "written in --tempDir")
+    p.add_argument("--refinedBed", type=str, default="regions_refined.bed", help="with --refine: the refined regions as BED, written "
                    "in --tempDir")
     return p
 
@@ -266,6 +291,50 @@ def kmer_rows(regions, res, k, fmt):
                              fmt(int(res.count[r][j])), fmt(float(res.pw[r][j])), fmt(float(res.pg[r][j])), fmt(term), share]) + "\n"
 
 
+REFINE_COLUMNS = ["name", "start", "stop", "length", "id", "newStart", "newStop", "newLength", "shiftStart", "shiftStop", "llrStart",
+                  "llrStop", "flank", "windowKLD", "newKLD", "note"]
+
+
+def refine_order(args):
+    """The order of --refine's chains: --refineOrder, else low (refine.default_order)."""
+    from . import refine
+    return refine.default_order(args.minWordSize, args.maxWordSize) if args.refineOrder is None else args.refineOrder
+
+
+def refine_problem(args):
+    """Why this command line cannot have its --refine (a message), or None: checked before any device work."""
+    for other, given in (("--donors", args.donors), ("--null", args.null), ("--topKmers", args.topKmers is not None)):
+        if given:
+            return "--refine does not go with %s: run again on the refined BED for that" % other
+    if not 1 <= args.refine <= _ffi.REFINE_MAX_FLANK:
+        return "--refine takes 1..%d bases" % _ffi.REFINE_MAX_FLANK
+    r = refine_order(args)
+    if r < 0 or not args.minWordSize <= r + 1 <= args.maxWordSize:
+        return "--refineOrder r needs the k-mers of length r + 1: %d <= r + 1 <= %d" % (args.minWordSize, args.maxWordSize)
+    return None
+
+
+def refine_note(status, flank_used):
+    st = int(status)
+    return "short" if int(flank_used) == 0 else ("." if st & _ffi.ROW_KEPT else "unresolved")
+
+
+def refine_rows(regions, res, rf, res_new, fmt):
+    """One line per region of the --refine table.  res, res_new: the score columns of the regions and of the refined regions."""
+    for r, (name, a, b, ident) in enumerate(regions):
+        ns, ne = int(rf.new_start[r]), int(rf.new_stop[r])
+        llr = [float(int(g)) / 4294967296.0 for g in (rf.gain_start[r], rf.gain_stop[r])]
+        yield "\t".join([fmt(v) for v in [name, a + 1, b, b - a]] + [ident] +
+                        [fmt(v) for v in [ns + 1, ne, ne - ns, ns - a, ne - b, llr[0], llr[1], int(rf.flank_used[r]),
+                                          region_cell(res.status[r], res.kld[r])[1], region_cell(res_new.status[r], res_new.kld[r])[1]]] +
+                        [refine_note(rf.status[r], rf.flank_used[r])]) + "\n"
+
+
+def refined_bed_rows(regions, rf):
+    for r, (name, _, _, ident) in enumerate(regions):
+        yield "%s\t%d\t%d\t%s\n" % (name, int(rf.new_start[r]), int(rf.new_stop[r]), ident)
+
+
 def write_table(path, columns, rows=()):
     """A table of the command line: the header, then the rows' lines."""
     with open(path, "w") as fh:
@@ -323,6 +392,10 @@ def main(argv=None):
     if problem:
         logging.error("[ERROR] %s\n", problem)
         return 1
+    problem = refine_problem(args) if args.refine is not None else None
+    if problem:
+        logging.error("[ERROR] %s\n", problem)
+        return 1
     labels = [os.path.basename(p) for p in [args.hostSeq] + list(args.donors or [])]
     if len(set(labels)) != len(labels):
         logging.error("[ERROR] the host and the donors (--donors) must differ in their file names, which label the columns: %s\n",
@@ -342,6 +415,7 @@ def main(argv=None):
         os.makedirs(os.path.abspath(args.tempDir))
     out_path, kmer_path, null_path, donor_path = (os.path.join(args.tempDir, f) for f in (args.outfile, args.kmerOutfile, args.nullOutfile,
                                                                                          args.donorOutfile))
+    refine_path, bed_path = os.path.join(args.tempDir, args.refineOutfile), os.path.join(args.tempDir, args.refinedBed)
     if not regions:
         write_table(out_path, columns(rip))
         if args.donors:
@@ -350,6 +424,9 @@ def main(argv=None):
             write_table(null_path, NULL_COLUMNS)
         if args.topKmers is not None:
             write_table(kmer_path, KMER_COLUMNS)
+        if args.refine is not None:
+            write_table(refine_path, REFINE_COLUMNS)
+            open(bed_path, "w").close()
         log.info("No regions in %s: wrote the header to %s", args.bed or args.gff, out_path)
         return 0
 
@@ -369,6 +446,11 @@ def main(argv=None):
             if args.donors:
                 panel, planes = score_with_donors(args, hp, regions, log)
                 res = panel.plane(planes[0])
+            elif args.refine is not None:       # the boundaries first; both scorings on the query it leaves resident
+                rf = hp.refineRegions(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], args.refine, refine_order(args),
+                                      genomeKmers=genomeKmers)
+                res = hp.scoreResident(args, rf.seq_index, rf.start, rf.stop)
+                res_new = hp.scoreResident(args, rf.seq_index, rf.new_start, rf.new_stop)
             elif args.topKmers is not None:
                 res = hp.explainRegions(args, args.querySeq or args.hostSeq, [r[:3] for r in regions], args.topKmers,
                                         genomeKmers=genomeKmers)
@@ -386,6 +468,11 @@ def main(argv=None):
         hp.close()
     write_table(out_path, columns(rip), region_rows(regions, res, rip, cli._fmt()))
     log.info("Scored %d regions: %s", len(regions), out_path)
+    if args.refine is not None:
+        write_table(refine_path, REFINE_COLUMNS, refine_rows(regions, res, rf, res_new, cli._fmt()))
+        with open(bed_path, "w") as fh:
+            fh.writelines(refined_bed_rows(regions, rf))
+        log.info("Refined their boundaries within %d bases (order %d): %s, %s", args.refine, refine_order(args), refine_path, bed_path)
     if args.topKmers is not None:
         write_table(kmer_path, KMER_COLUMNS, kmer_rows(regions, res, args.maxWordSize, cli._fmt()))
         log.info("Listed the %d largest KLD terms of each: %s", args.topKmers, kmer_path)

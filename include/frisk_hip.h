@@ -344,6 +344,43 @@ int frisk_explain_ranges(frisk_ctx* ctx, const int32_t* seq_index, const int64_t
                          uint32_t* status, double* kld, double* gc, double* pi, double* si, double* cri, int64_t* nn,
                          int32_t* n_present, uint32_t* code, uint32_t* count, double* pw, double* pg, double* term);
 
+/* ---- a region's boundaries, to the base -----------------------------------------------------
+ * "Where does this region start and end?"  Every region the scanner yields has boundaries on a window grid; frisk_refine_ranges
+ * moves each boundary within +- flank bases to a likelihood-ratio change point (csrc/refine_kernels.h; frisk_amd/refine.py restates
+ * it in numpy with the same integers).  Integer arithmetic only: a row's outputs are exactly reproducible.
+ * Row r is (seq_index[r], a = start[r], b = stop[r]), 0-based half-open; F = flank, 1 <= F <= 65 536; the chain's order r = order
+ * with kmin <= r + 1 <= kmax (the rule of frisk_seq_null); L = the scaffold's length.  Fe = min(F, (b - a) / 4) = flank_used[r].
+ *   core    [a + Fe, b - Fe), counted as frisk_score_ranges counts a slice (no word past its ends, lowercase counts in words).
+ *           status[r], nn[r] are the core's: nn as in frisk_score_ranges; FRISK_ROW_KEPT, FRISK_ROW_NO_MAXMER as there;
+ *           FRISK_ROW_ZERO_WEIGHT for a max-mer present and kmin-1 <= S <= kmax-1 only (the genome's weights are not looked at).
+ *           Fe = 0 (fewer than 4 bases: the core is the region) or a core the N rule drops (status 0): new_start = a, new_stop = b,
+ *           both gains 0.
+ *   models  one table of order r + 1 each; digits A, T, G, C = 0..3, first base most significant, word c has the context c >> 2.
+ *           island: n_i(c) = the core's count of c; host: n_h(c) = the finalised profile's symmetric count of c; T(ctx) = the sum
+ *           over the context's four words.  lp(n, T) = flog2(n + 1) - flog2(T + 4) (Laplace), qtab(c) = lp(n_i(c), T_i(c >> 2)) -
+ *           lp(n_h(c), T_h(c >> 2)): int64 in units of 2^-32 bit.
+ *   flog2   for an integer 1 <= x < 2^63: e = the index of its top bit, m = x << (63 - e) (Q1.63), f = 0; 32 times: p = m * m
+ *           (128 bits), hi = p >> 64, f <<= 1; if hi >= 2^63: f |= 1, m = hi; else m = (hi << 1) | (low64(p) >> 63).  flog2(x) =
+ *           (e << 32) + f, and 0 <= 2^32 log2 x - flog2(x) < 1 + 2^-20.
+ *   q_j     at position j of the scaffold: qtab(the word of bases [j - r, j], upper-cased) when j - r >= 0 and none of its r + 1
+ *           bases is invalid, else 0.  A word never crosses a scaffold's edge.
+ *   start   G_s(t) = sum_{j = t}^{a + Fe - 1} q_j for t in [max(0, a - Fe), a + Fe]; new_start[r] = the LARGEST t that maximises it;
+ *           gain_start[r] = G_s(new_start) - G_s(a) >= 0.
+ *   stop    G_e(u) = sum_{j = b - Fe}^{u - 1} q_j for u in [b - Fe, min(L, b + Fe)]; new_stop[r] = the SMALLEST u that maximises it;
+ *           gain_stop[r] = G_e(new_stop) - G_e(b) >= 0.
+ * On a tie the shorter region wins (an N run across a boundary is left outside); new_start <= a + Fe < b - Fe <= new_stop.  Gains
+ * are in units of 2^-32 bit.  A row's outputs depend on the row, the batch, the profile, F and r alone - not on the other rows,
+ * their order, the form or the grid.
+ * flags: FRISK_RANGES_BIG as in frisk_score_ranges; other bits are ignored.  The row and batch checks of frisk_score_ranges, with
+ * the same FRISK_E_ARG and nothing launched; FRISK_E_ARG too for a flank or an order outside the above and for a null array.
+ * FRISK_E_STATE: no finalised profile.  n = 0 is FRISK_OK and touches no output.  A streamed batch is waited for.  The scan's plan
+ * and rows, the panel, frisk_score_ranges and frisk_explain_ranges are left alone.
+ * frisk_last_kernel_ms(ctx, 8) = the refine kernels' time of the last call. */
+int frisk_refine_ranges(frisk_ctx* ctx, const int32_t* seq_index, const int64_t* start, const int64_t* stop, int64_t n,
+                        uint32_t flags, int32_t flank, int32_t order,
+                        uint32_t* status, int64_t* nn, int64_t* new_start, int64_t* new_stop,
+                        int64_t* gain_start, int64_t* gain_stop, int64_t* flank_used);
+
 /* Test utility (kmax <= 6): the two distributions IvomBuild returns for each candidate window of [c0,c1) (L1481-1482, L369-457) -
  * window-side and genome-side interpolated probabilities of the window's present max-mers, each normalised to sum 1 -
  * as dense vectors of 4^kmax doubles per candidate (0 for absent max-mers; all 0 for windows the reference drops). */
@@ -609,8 +646,8 @@ void  frisk_host_free(frisk_ctx* ctx, void* ptr);
 
 /* Timing of the most recent launches on the context's stream, measured with HIP events:
  * which = 0 scan kernel, 1 profile_add kernel, 2 pack kernel, 3 frisk_window_vectors' kernels, 4 frisk_score_ranges' kernels,
- * 5 frisk_score_ranges_panel's kernels, 6 frisk_seq_null's generator kernels, 7 frisk_explain_ranges' kernels.  Returns
- * milliseconds, <0 if none. */
+ * 5 frisk_score_ranges_panel's kernels, 6 frisk_seq_null's generator kernels, 7 frisk_explain_ranges' kernels,
+ * 8 frisk_refine_ranges' kernels (the host table, both forms).  Returns milliseconds, <0 if none. */
 double frisk_last_kernel_ms(const frisk_ctx* ctx, int which);
 
 #ifdef __cplusplus

@@ -2,7 +2,9 @@
 // through the 2-bit packer (against a letter-by-letter restatement), bitmap -> runs, the HMM fit / Viterbi on random series of awkward
 // lengths, the scan's launch schedule (scan_schedule.h): invariants over a sweep of shapes, named shapes against values worked out by
 // hand, the window-tile planner (scan_tiles.h): every rank's tiles of random shapes together, the region scorer's plan
-// (range_plan.h): invariants over seeded random batches, named cases, the refusals with their rows, and the memory fit, and phase A's
+// (range_plan.h): invariants over seeded random batches, named cases, the refusals with their rows, and the memory fit, the boundary
+// refinement's plan (plan_refine: the cores and the search geometry over seeded random batches, named cases, every refusal) and its
+// integer arithmetic (refine_math.h: flog2 against long double, the workgroup's change-point search against a scan), and phase A's
 // plan (profile_plan.h): the launch of every form over a sweep of ranges, two named shapes, and the pieces of a streamed batch.
 // build + run:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ifrisk_amd/csrc
 //               tools/exp/san_host.cpp -o build/san/san_host -lpthread -lz && build/san/san_host
@@ -17,6 +19,7 @@
 #include "scan_schedule.h"
 #include "scan_tiles.h"
 #include "range_plan.h"
+#include "refine_math.h"
 #include "profile_plan.h"
 #include <fstream>
 #include <unistd.h>
@@ -389,6 +392,149 @@ static long long check_range_plan() {             // -> plans made
     return plans;
 }
 
+// frisk_refine_ranges' plan (range_plan.h: plan_refine).  Of an accepted plan: the rows of its RangePlan are the cores [a + Fe, b - Fe),
+// Fe = min(flank, (b - a) / 4), and pass every check of plan_ranges; a row's geometry names its scaffold, a, b, Fe and the two
+// clipped flanks, so that both search intervals lie inside the scaffold and new_start <= a + Fe < b - Fe <= new_stop can hold.
+static long long check_refine_plan() {
+    long long plans = 0;
+    std::mt19937_64 rng(20241021);
+    int64_t clipped_left = 0, clipped_right = 0, tiny = 0, capped = 0;
+    for (int round = 0; round < 3000; ++round) {
+        const int n_seq = 1 + int(rng() % 5);
+        std::vector<int64_t> seq_len(static_cast<size_t>(n_seq)), seq_off(static_cast<size_t>(n_seq));
+        int64_t off = 0;
+        for (int s = 0; s < n_seq; ++s) {
+            seq_len[size_t(s)] = 1 + int64_t(rng() % 300000);
+            seq_off[size_t(s)] = off;
+            off += seq_len[size_t(s)] + 1;
+        }
+        const int64_t n = int64_t(rng() % 40);
+        std::vector<int32_t> si(static_cast<size_t>(n));
+        std::vector<int64_t> a(static_cast<size_t>(n)), b(static_cast<size_t>(n));
+        for (int64_t r = 0; r < n; ++r) {
+            const int32_t s = int32_t(rng() % uint64_t(n_seq));
+            const int64_t size = seq_len[size_t(s)];
+            int64_t len = 1 + int64_t(rng() % uint64_t(size));
+            if (rng() % 4 == 0) len = std::min<int64_t>(size, 1 + int64_t(rng() % 9));
+            si[size_t(r)] = s;
+            a[size_t(r)] = rng() % 5 == 0 ? 0 : (rng() % 5 == 0 ? size - len : int64_t(rng() % uint64_t(size - len + 1)));
+            b[size_t(r)] = a[size_t(r)] + len;
+        }
+        const int kmin = 1 + int(rng() % 4), kmax = kmin + int(rng() % (13 - kmin)), num_cu = 1 + int(rng() % 300);
+        const int32_t order = int32_t(kmin - 1 + int(rng() % (kmax - kmin + 1)));
+        const int32_t flank = (rng() & 1) ? 1 + int32_t(rng() % 65536) : 1 + int32_t(rng() % 600);
+        const bool all_long = kmax > 8 || rng() % 4 == 0;
+        const RefinePlan R = plan_refine(n_seq, seq_len.data(), seq_off.data(), si.data(), a.data(), b.data(), n, flank, order, kmin, kmax, all_long, num_cu, 2);
+        ++plans;
+        CHECK(R.plan.error_code == FRISK_OK && int64_t(R.geom.size()) == n * FRISK_REFINE_GEOM);
+        if (R.plan.error_code != FRISK_OK || int64_t(R.geom.size()) != n * FRISK_REFINE_GEOM) continue;
+        std::vector<int64_t> ca(static_cast<size_t>(n)), cb(static_cast<size_t>(n));
+        for (int64_t r = 0; r < n; ++r) {
+            const int64_t* g = R.geom.data() + size_t(r) * FRISK_REFINE_GEOM;
+            const int64_t L = seq_len[size_t(si[size_t(r)])], A = a[size_t(r)], B = b[size_t(r)], fe = g[3];
+            CHECK(g[0] == seq_off[size_t(si[size_t(r)])] && g[1] == A && g[2] == B);
+            CHECK(fe == std::min<int64_t>(flank, (B - A) / 4) && 0 <= fe && fe <= FRISK_REFINE_MAX_FLANK);
+            CHECK(g[4] == std::min(fe, A) && g[5] == std::min(fe, L - B));
+            CHECK(A - g[4] >= 0 && B + g[5] <= L && A + fe < B - fe + (fe == 0 ? 1 : 0) && A + fe < B - fe + 1);
+            CHECK((fe == 0) == (B - A < 4));
+            ca[size_t(r)] = A + fe; cb[size_t(r)] = B - fe;
+            CHECK(ca[size_t(r)] < cb[size_t(r)]);
+            clipped_left += g[4] < fe; clipped_right += g[5] < fe; tiny += fe == 0; capped += fe == flank;
+        }
+        check_one_plan(R.plan, seq_off, si, ca, cb, kmax, all_long, num_cu, 2, 0);
+    }
+    CHECK(clipped_left > 300 && clipped_right > 300 && tiny > 300 && capped > 300);      // (the sweep reaches them)
+    // named cases on one batch
+    const std::vector<int64_t> seq_len = {100000, 11}, seq_off = {0, 100001};
+    auto plan = [&](const std::vector<int32_t>& si, const std::vector<int64_t>& a, const std::vector<int64_t>& b, int32_t flank, int32_t order,
+                    int kmin = 1, int kmax = 8) {
+        ++plans;
+        return plan_refine(2, seq_len.data(), seq_off.data(), si.data(), a.data(), b.data(), int64_t(si.size()), flank, order, kmin, kmax, kmax > 8, 256, 2);
+    };
+    {   // n = 0; lengths 3, 4, 7, 8; a region at the first base, one at the last; 4F - 1, 4F, 4F + 1
+        CHECK(plan({}, {}, {}, 500, 2).plan.error_code == FRISK_OK && plan({}, {}, {}, 500, 2).geom.empty());
+        const RefinePlan R = plan({0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, {10, 10, 10, 10, 0, 99000, 5000, 5000, 5000, 0}, {13, 14, 17, 18, 3000, 100000, 6999, 7000, 7001, 11}, 500, 2);
+        CHECK(R.plan.error_code == FRISK_OK);
+        auto g = [&](int r, int k) { return R.geom[size_t(r * FRISK_REFINE_GEOM + k)]; };
+        CHECK(g(0, 3) == 0 && g(1, 3) == 1 && g(2, 3) == 1 && g(3, 3) == 2);
+        CHECK(R.plan.ranges[0] == 10 && R.plan.ranges[1] == 3 && R.plan.ranges[2] == 11 && R.plan.ranges[3] == 2 && R.plan.ranges[7] == 4);
+        CHECK(g(4, 3) == 500 && g(4, 4) == 0 && g(4, 5) == 500 && g(5, 3) == 250 && g(5, 4) == 250 && g(5, 5) == 0);
+        CHECK(g(6, 3) == 499 && g(7, 3) == 500 && g(8, 3) == 500 && R.plan.ranges[2 * 8 + 1] == 1001 && R.plan.ranges[2 * 6 + 1] == 1001);
+        CHECK(g(9, 0) == 100001 && g(9, 3) == 2 && g(9, 4) == 0 && g(9, 5) == 0 && R.plan.ranges[18] == 100003 && R.plan.ranges[19] == 7);
+    }
+    {   // a core on either side of the short form's limit: 65 535 + 2 * 500 bases and one more
+        const RefinePlan R = plan({0, 0}, {0, 0}, {66535, 66536}, 500, 2);
+        CHECK(R.plan.short_rows == std::vector<int64_t>{0} && R.plan.long_rows == std::vector<int64_t>{1});
+    }
+    {   // the refusals: flank, order, then the rows as plan_ranges refuses them
+        const char* chain = "the chain of order r reads the counts of order r + 1, which must lie in kmin .. kmax";
+        for (int32_t f : {0, -1, 65537}) CHECK(plan({0}, {0}, {100}, f, 2).plan.error == "flank outside 1 .. 65536");
+        CHECK(plan({0}, {0}, {100}, 65536, 2).plan.error_code == FRISK_OK && plan({0}, {0}, {100}, 1, 7).plan.error_code == FRISK_OK);
+        CHECK(plan({0}, {0}, {100}, 500, 8).plan.error == chain && plan({0}, {0}, {100}, 500, -1).plan.error == chain);
+        CHECK(plan({0}, {0}, {100}, 500, 1, 3, 5).plan.error == chain && plan({0}, {0}, {100}, 500, 5, 3, 5).plan.error == chain);
+        CHECK(plan({0}, {0}, {100}, 500, 2, 3, 5).plan.error_code == FRISK_OK && plan({0}, {0}, {100}, 500, 11, 2, 12).plan.error_code == FRISK_OK);
+        CHECK(plan({0, 2}, {0, 0}, {10, 10}, 500, 2).plan.error == "sequence index out of range in row 1");
+        const std::string rng_ = "range outside the scaffold (or empty, or of 2^31 bases or more) in row ";
+        CHECK(plan({0, 0}, {0, 10}, {10, 10}, 500, 2).plan.error == rng_ + "1" && plan({0}, {-1}, {9}, 500, 2).plan.error == rng_ + "0");
+        CHECK(plan({1}, {0}, {12}, 500, 2).plan.error == rng_ + "0" && plan({1}, {0}, {12}, 500, 2).geom.empty());
+        CHECK(plan({0}, {0}, {100}, 0, 99).plan.error_code == FRISK_E_ARG);
+    }
+    return plans;
+}
+
+// refine_math.h.  flog2 from below within 1 + 2^-20 units of 2^-32 bit of the long double logarithm (64-bit mantissa: 2^-20 of slack
+// for its own rounding at 63 * 2^32), exact at the powers of two.  The change-point search as a workgroup runs it - nt threads' runs
+// (refine_run), joined over each wave by the butterfly of refine_kernels.h and over the waves in order (refine_join), against the
+// empty prefix (refine_pick) - against one plain scan that keeps the first maximum, over sequences full of ties.
+static long long check_refine_math() {
+    long long cuts = 0;
+    std::mt19937_64 rng(77);
+    auto check_log = [&](uint64_t x) {
+        const long double d = std::log2(static_cast<long double>(x)) * 4294967296.0L - static_cast<long double>(refine_flog2(x));
+        CHECK(d >= -1.0L / 1048576.0L && d < 1.0L + 1.0L / 1048576.0L);
+    };
+    for (uint64_t x = 1; x < 3000; ++x) check_log(x);
+    for (int k = 1; k < 63; ++k) {
+        CHECK(refine_flog2(uint64_t(1) << k) == int64_t(k) << 32);
+        check_log((uint64_t(1) << k) - 1); check_log((uint64_t(1) << k) + 1);
+    }
+    for (int i = 0; i < 3000; ++i) check_log(1 + (rng() >> 2) % ((uint64_t(1) << 62) - 1));
+    CHECK(refine_lp(0, 0) == -(int64_t(2) << 32) && refine_lp(3, 4) == (int64_t(2) << 32) - (int64_t(3) << 32));
+    for (int round = 0; round < 4000; ++round) {
+        const int nt = (round & 1) ? 1024 : 512;
+        const int32_t n = round % 7 == 0 ? int32_t(rng() % 4) : (round % 5 == 0 ? int32_t(nt - 2 + rng() % 5) : int32_t(rng() % 5000));
+        const int32_t Fe = int32_t(rng() % uint64_t(n + 2));
+        const int span = 1 + int(rng() % 3);                    // small values: plateaus and ties everywhere
+        std::vector<int64_t> x(static_cast<size_t>(n));
+        for (auto& v : x) v = (rng() % 3 == 0) ? 0 : int64_t(rng() % uint64_t(2 * span + 1)) - span;
+        if (round % 11 == 0) for (auto& v : x) v *= int64_t(1) << 38;
+        std::vector<RefineCut> lane(static_cast<size_t>(nt));
+        for (int t = 0; t < nt; ++t) lane[size_t(t)] = refine_run(n, t, nt, Fe, [&](int32_t i) { return x[size_t(i)]; });
+        RefineCut total = {0, 0, 0, -1};
+        for (int w = 0; w < nt / 64; ++w) {
+            RefineCut* v = lane.data() + size_t(w) * 64;
+            for (int d = 1; d < 64; d <<= 1) {
+                RefineCut y[64];
+                for (int l = 0; l < 64; ++l) y[l] = v[l ^ d];
+                for (int l = 0; l < 64; ++l) v[l] = (l & d) ? refine_join(y[l], v[l]) : refine_join(v[l], y[l]);
+            }
+            for (int l = 1; l < 64; ++l) CHECK(v[l].sum == v[0].sum && v[l].best == v[0].best && v[l].arg == v[0].arg && v[l].ref == v[0].ref);
+            total = w == 0 ? v[0] : refine_join(total, v[0]);
+        }
+        int64_t best, want_best = 0, run = 0, want_ref = 0;
+        int32_t arg, want_arg = 0;
+        refine_pick(total, best, arg);
+        for (int32_t i = 0; i < n; ++i) {
+            run += x[size_t(i)];
+            if (i < Fe) want_ref += x[size_t(i)];
+            if (run > want_best) { want_best = run; want_arg = i + 1; }
+        }
+        CHECK(best == want_best && arg == want_arg && total.ref == want_ref && total.sum == run);
+        ++cuts;
+    }
+    return cuts;
+}
+
 // Phase A's plan (profile_plan.h).  plan_profile_launch over a sweep: the form follows the rule; the chunks of the forms with a table
 // in LDS cover the range's words with no empty workgroup, on no more than one workgroup per CU; the big form's grid-stride loop
 // (no chunks) has no idle workgroup either; the dynamic LDS fits a CU; grid = 0 exactly for an empty range.  Two named shapes against
@@ -500,6 +646,8 @@ static long long check_profile_plan() {           // -> plans made
 int main() {
     const long long profile_plans = check_profile_plan();
     const long long range_plans = check_range_plan();
+    const long long refine_plans = check_refine_plan();
+    const long long refine_cuts = check_refine_math();
     const long long plans = check_scan_schedule();
     const long long tile_shapes = check_scan_tiles();
     std::mt19937_64 rng(12345);
@@ -643,6 +791,6 @@ int main() {
         }
         ::unlink(path.c_str());
     }
-    std::printf("%s (%d failed checks; %lld scan schedules; %lld tile plans; %lld range plans; %lld profile plans; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, tile_shapes, range_plans, profile_plans, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
+    std::printf("%s (%d failed checks; %lld scan schedules; %lld tile plans; %lld range plans; %lld refine plans; %lld refine cuts; %lld profile plans; AVX-512 packer %s)\n", fails ? "FAILED" : "ok", fails, plans, tile_shapes, range_plans, refine_plans, refine_cuts, profile_plans, frisk_pack2::have_avx512() ? "exercised" : "not available on this host");
     return fails ? 1 : 0;
 }
