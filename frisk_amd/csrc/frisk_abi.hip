@@ -1,6 +1,6 @@
 // frisk_abi.hip - host side of libfrisk_hip.so: the context's creation and destruction, its small getters, the profile (phase A: its
 // launches are planned in profile_plan.h) and the scan of the C ABI declared in include/frisk_hip.h.  The context itself is
-// frisk_ctx.h's; the sequence and FASTA entry points are in frisk_seq.hip.  The scan kernels are launched through scan_launch.h (scan_launch.hip, scan8_launch.hip, scan8_launch4.hip); the
+// frisk_ctx.h's; the sequence and FASTA entry points are in frisk_seq.hip.  The scan kernels are launched through scan_launch.h (scan_launch.hip, scan8_launch*.hip), each by the form that the schedule names; the
 // entry points that take no context (HMM, projection, clustering) are in frisk_analysis.hip.  gfx950 (MI355X) only.  Build: see
 // __graft_entry__.build_hip().
 #include <hip/hip_runtime.h>
@@ -116,7 +116,7 @@ int frisk_create(int device, int kmin, int kmax, frisk_ctx** out) {
         for (int i = 1; i < 256; ++i) rc[i] = 1.0 / double(i);
         HIPC(c, c->d_rctab.reserve(256));
         HIPC(c, hipMemcpyAsync(c->d_rctab.p, rc, sizeof(rc), hipMemcpyHostToDevice, c->stream));
-        HIPC(c, c->d_ovf_count.reserve(64));
+        HIPC(c, c->d_ovf_count.reserve(SCAN_CNT_TOTAL));
         HIPC(c, c->d_verdict.reserve(8));
         HIPC(c, hipStreamSynchronize(c->stream));
     }
@@ -495,9 +495,9 @@ struct ScanRun {
         return FRISK_OK;
     }
 
-    // the 16-bit form (scan_kernel.h) over the candidates that PP names, by window class
+    // the 16-bit form (scan_kernel.h) over the candidates that PP names
     hipError_t launch16(const ScanParams& PP, int g, hipStream_t st) const {
-        return launch_scan16(PP, c->kmax, sched.its, shape.debug, sched.lds_total, g, st);
+        return launch_scan16_form(sched.form16, PP, sched.lds_total, g, st);
     }
 
     // rows [r0, r1) to the caller's buffers
@@ -530,9 +530,7 @@ struct ScanRun {
             HIPC(c, c->d_big.reserve(size_t(sched.big_grid) * size_t(stride)));
             HIPC(c, hipMemsetAsync(c->d_big.p, 0, size_t(sched.big_grid) * size_t(stride) * 4, c->stream));
             e = launch_scan_big(P, shape.debug, sched.big_grid, c->d_big.p, stride, c->stream);
-        } else if (sched.path == SCAN_PATH_TWO_WG) {
-            e = launch_scan_two_wg(P, sched.its, sched.lds_total, sched.grid, c->stream);
-        } else {
+        } else {        // (one or two workgroups per CU: the form says)
             e = launch16(P, sched.grid, c->stream);
         }
         HIPC(c, e);
@@ -549,9 +547,10 @@ struct ScanRun {
         const int64_t n = shape.n, nsample = sched.nsample, chunk8 = sched.chunk8;
         ScanParams S = P;
         S.chunk = int32_t(chunk8);
-        S.sel_mode = 1; S.out_list = c->d_ovf_list.p; S.out_count = c->d_ovf_count.p;
-        if (sched.dealt) { S.queue = c->d_ovf_count.p + 8; S.queue_n = 8; }
-        HIPC(c, launch_narrow(c->kmax, 4, sched.small_w, false, S, c->num_cu, nsample, c->stream, true));
+        unsigned int* cnt = c->d_ovf_count.p;       // (the sample counts where segment 0 will)
+        S.sel_mode = 1; S.out_list = c->d_ovf_list.p; S.out_count = cnt + SCAN_CNT_LIST1;
+        if (sched.dealt) { S.queue = cnt + SCAN_CNT_BULK_QUEUES; S.queue_n = SCAN_CNT_BULK_QUEUE_N; }
+        HIPC(c, launch_scan8_form(sched.form_sample, S, c->num_cu, nsample, c->stream));
         // The verdict is taken ON THE DEVICE (scan8_decide_kernel, one thread behind the sample): the host queues all three bulk forms
         // behind it, each with the verdict's address and its own number, and two of them return at once - no host synchronisation
         // in the first scan of a batch (round 3: sample -> copy -> hipStreamSynchronize -> decide -> launch).  The rule:
@@ -560,29 +559,29 @@ struct ScanRun {
         // 9.98 ms, 8-bit bulk 8.51 / 8.57 / 8.71 / 8.78 ms - tools/exp/width_sweep.sh); the side table pays when the plain form
         // would hand on more than FRISK_SIDE_SHARE of the windows that are scored (it costs a scored window 1.0 ns - ten
         // instructions per position: 6.97 against 6.59 ms per scan -, a window handed on 18 ns: tools/exp/side_rate.py)
-        HIPC(c, launch_scan8_decide(c->d_ovf_count.p, static_cast<unsigned int>(nsample * chunk8), sched.narrow8 && !shape.debug ? 1 : 0,
+        HIPC(c, launch_scan8_decide(cnt, static_cast<unsigned int>(nsample * chunk8), sched.narrow8 && !shape.debug ? 1 : 0,
                                     c->d_verdict.p, c->stream));
         ScanParams H = P;
-        H.in_list = c->d_ovf_list.p; H.in_count = c->d_ovf_count.p;
-        H.out_list = c->d_ovf_list2.p; H.out_count = c->d_ovf_count.p + 1;
-        if (sched.dealt) H.queue = c->d_ovf_count.p + 16;
-        HIPC(c, launch_narrow(c->kmax, 8, sched.small_w, false, H, c->num_cu, nsample * chunk8, c->stream));
+        H.in_list = c->d_ovf_list.p; H.in_count = cnt + SCAN_CNT_LIST1;
+        H.out_list = c->d_ovf_list2.p; H.out_count = cnt + SCAN_CNT_LIST2;
+        if (sched.dealt) H.queue = cnt + SCAN_CNT_QUEUE8;
+        HIPC(c, launch_scan8_form(sched.form_handover, H, c->num_cu, nsample * chunk8, c->stream));
         ScanParams H2 = P;
-        H2.in_list = c->d_ovf_list2.p; H2.in_count = c->d_ovf_count.p + 1;
+        H2.in_list = c->d_ovf_list2.p; H2.in_count = cnt + SCAN_CNT_LIST2;
         int g16 = int(std::min<int64_t>(n, int64_t(c->num_cu)));
         if (g16 >= 8) g16 &= ~7;
         HIPC(c, launch16(H2, g16, c->stream));
-        HIPC(c, hipMemcpyAsync(novf_sample, c->d_ovf_count.p, sizeof(novf_sample), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemsetAsync(c->d_ovf_count.p, 0, 64 * sizeof(unsigned int), c->stream));
+        static_assert(SCAN_CNT_LIST1 == 0 && SCAN_CNT_LIST2 == 1, "the two list lengths lead the block: one copy brings both");
+        HIPC(c, hipMemcpyAsync(novf_sample, cnt, sizeof(novf_sample), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemsetAsync(cnt, 0, SCAN_CNT_TOTAL * sizeof(unsigned int), c->stream));
         return FRISK_OK;
     }
 
     // Rows [r0, r1) of this scan on stream `st`: bulk launch, the two hand-over launches and the rows' scalar tail.  Segment `seg`
-    // has its own slice of the two lists (from entry r0) and its own 32 counters: [0], [1] the lists' lengths, [8..15] the bulk
-    // launch's chunk queues (one per XCD), [16] the 8-bit launch's.
+    // has its own slice of the two lists (from entry r0) and its own counters (ScanCounter, scan_params.h).  Which kernel a launch
+    // runs is the schedule's statement (sched.form_*).
     int run_rows(int seg, int64_t r0, int64_t r1, hipStream_t st, bool fork_tail) {
         const int64_t m = r1 - r0, chunk8 = sched.chunk8;
-        const bool small_w = sched.small_w, debug = shape.debug;
         ScanParams R = P;
         R.c0 = P.c0 + r0; R.c1 = P.c0 + r1;
         R.seq_index += r0; R.start += r0; R.stop += r0; R.status += r0; R.kld += r0; R.gc += r0; R.sw += r0; R.sg += r0;
@@ -590,38 +589,38 @@ struct ScanRun {
         if (R.dbg_counts) R.dbg_counts += r0 * int64_t(c->nprof);
         if (R.dbg_meta) R.dbg_meta += r0 * 3;
         if (R.dbg_ivom) R.dbg_ivom += r0 * 2 * int64_t(nk);
-        unsigned int* cnt = c->d_ovf_count.p + 32 * seg;
+        unsigned int* cnt = c->d_ovf_count.p + SCAN_CNT_SEGMENT * seg;
         int64_t* list1 = c->d_ovf_list.p + r0;
         int64_t* list2 = c->d_ovf_list2.p + r0;
         ScanParams B = R;                       // the bulk launch
         B.chunk = int32_t(chunk8);
         B.sel_mode = sched.sel_mode;
-        if (sched.bulk == 4) { B.out_list = list1; B.out_count = cnt; }
-        else { B.out_list = list2; B.out_count = cnt + 1; }
-        if (sched.dealt) { B.queue = cnt + 8; B.queue_n = 8; }
+        if (sched.bulk == 4) { B.out_list = list1; B.out_count = cnt + SCAN_CNT_LIST1; }
+        else { B.out_list = list2; B.out_count = cnt + SCAN_CNT_LIST2; }
+        if (sched.dealt) { B.queue = cnt + SCAN_CNT_BULK_QUEUES; B.queue_n = SCAN_CNT_BULK_QUEUE_N; }
         const int64_t mchunks = (m + chunk8 - 1) / chunk8;
         const int64_t bulk_chunks = sched.sel_mode == 2 ? mchunks - (mchunks + B.sel_mod - 1) / B.sel_mod : mchunks;
         if (sched.sample) {                     // plain 4-bit / 4-bit + side table / 8-bit: the device's verdict lets one of them run
             B.verdict = c->d_verdict.p;
-            B.out_list = list1; B.out_count = cnt;
+            B.out_list = list1; B.out_count = cnt + SCAN_CNT_LIST1;
             B.my_form = 1u;
-            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, false, sched.kmin1_form));
+            HIPC(c, launch_scan8_form(sched.form_verdict[0], B, c->num_cu, bulk_chunks, st));
             B.my_form = 2u;
-            HIPC(c, launch_narrow(c->kmax, 4, small_w, false, B, c->num_cu, bulk_chunks, st, false, true, sched.kmin1_form));
+            HIPC(c, launch_scan8_form(sched.form_verdict[1], B, c->num_cu, bulk_chunks, st));
             B.my_form = 3u;
-            B.out_list = list2; B.out_count = cnt + 1;
-            HIPC(c, launch_narrow(c->kmax, 8, small_w, false, B, c->num_cu, bulk_chunks, st));
+            B.out_list = list2; B.out_count = cnt + SCAN_CNT_LIST2;
+            HIPC(c, launch_scan8_form(sched.form_verdict[2], B, c->num_cu, bulk_chunks, st));
         } else
-        HIPC(c, launch_narrow(c->kmax, sched.bulk, small_w, debug, B, c->num_cu, bulk_chunks, st, false, sched.side, sched.kmin1_form));
+        HIPC(c, launch_scan8_form(sched.form_bulk, B, c->num_cu, bulk_chunks, st));
         if (sched.bulk == 4) {                  // list 1 (4-bit hand-overs) -> 8-bit -> list 2
             ScanParams H = R;
-            H.in_list = list1; H.in_count = cnt;
-            H.out_list = list2; H.out_count = cnt + 1;
-            if (sched.dealt) H.queue = cnt + 16;
-            HIPC(c, launch_narrow(c->kmax, 8, small_w, debug, H, c->num_cu, m, st));
+            H.in_list = list1; H.in_count = cnt + SCAN_CNT_LIST1;
+            H.out_list = list2; H.out_count = cnt + SCAN_CNT_LIST2;
+            if (sched.dealt) H.queue = cnt + SCAN_CNT_QUEUE8;
+            HIPC(c, launch_scan8_form(sched.form_handover, H, c->num_cu, m, st));
         }
         // list 2 -> 16-bit counters, one window per workgroup at a time (a no-op when the list is empty)
-        R.in_list = list2; R.in_count = cnt + 1;
+        R.in_list = list2; R.in_count = cnt + SCAN_CNT_LIST2;
         int g16 = int(std::min<int64_t>(m, int64_t(c->num_cu)));
         if (g16 >= 8) g16 &= ~7;
         HIPC(c, launch16(R, g16, st));
@@ -638,7 +637,7 @@ struct ScanRun {
         const int64_t n = shape.n, cut = sched.cut;
         HIPC(c, c->d_ovf_list.reserve(size_t(n)));
         HIPC(c, c->d_ovf_list2.reserve(size_t(n)));
-        HIPC(c, hipMemsetAsync(c->d_ovf_count.p, 0, 64 * sizeof(unsigned int), c->stream));
+        HIPC(c, hipMemsetAsync(c->d_ovf_count.p, 0, SCAN_CNT_TOTAL * sizeof(unsigned int), c->stream));
         if (sched.ring_slices > 0) {    // a copy of the genome table (one base address for both), then one slice per workgroup launched
             const double* had = c->d_ig_ring.p;
             HIPC(c, c->d_ig_ring.reserve(nk + size_t(sched.ring_slices) * (20 * FRISK8_RING_COLS + FRISK8_RING_PAD)));
@@ -673,7 +672,7 @@ struct ScanRun {
     // debug dumps and counters to the host, the one wait of the call, then what the host does with the rows
     int collect() {
         const size_t N = size_t(shape.n);
-        unsigned int novf[34] = {0}, verdict_host[4] = {0, 0, 0, 0};
+        unsigned int novf[SCAN_CNT_SEGMENT + SCAN_CNT_LIST2 + 1] = {0}, verdict_host[4] = {0, 0, 0, 0};
         if (dbg_counts)
             HIPC(c, hipMemcpyAsync(dbg_counts, c->o_counts.p, N * size_t(c->nprof) * 4, hipMemcpyDeviceToHost, c->stream));
         if (dbg_meta) HIPC(c, hipMemcpyAsync(dbg_meta, c->o_meta.p, N * 3 * 8, hipMemcpyDeviceToHost, c->stream));
@@ -697,8 +696,8 @@ struct ScanRun {
             std::memcpy(seq_index, b + blk.seq_index, N * 4); std::memcpy(status, b + blk.status, N * 4);
         }
         c->scan_stat[5] = sched.kmin1_form && c->scan_stat[0] == 4 ? 1 : 0;
-        c->scan_stat[1] = novf[0] + novf[32] + novf_sample[0];
-        c->scan_stat[2] = novf[1] + novf[33] + novf_sample[1];
+        c->scan_stat[1] = novf[SCAN_CNT_LIST1] + novf[SCAN_CNT_SEGMENT + SCAN_CNT_LIST1] + novf_sample[0];
+        c->scan_stat[2] = novf[SCAN_CNT_LIST2] + novf[SCAN_CNT_SEGMENT + SCAN_CNT_LIST2] + novf_sample[1];
         if (c->b().tiled)               // descriptor index -> index of the scaffold in the FASTA
             for (size_t r = 0; r < N; ++r) seq_index[r] = c->b().tiles[size_t(seq_index[r])].scaf;
         float ms = 0;

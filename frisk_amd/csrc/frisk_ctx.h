@@ -113,7 +113,7 @@ struct frisk_ctx {
     uint64_t ig_gen = 1, ring_gen = 0;         // the genome table's generation, and the one whose copy heads d_ig_ring
     DevBuf<double> d_ig_ring;                  // scan8_kernel: per-workgroup ring of genome-side values by position (40 KB each at 20 positions per lane)
     DevBuf<unsigned int> d_verdict;            // the adaptive width's verdict, written on the device by scan8_decide_kernel: {form, handed, would-have, scored}
-    DevBuf<unsigned int> d_ovf_count;          // per row segment 32 counters: [0], [1] the lists' lengths, [8..15] the bulk launch's chunk queues, [16] the 8-bit launch's
+    DevBuf<unsigned int> d_ovf_count;          // SCAN_CNT_TOTAL counters, SCAN_CNT_SEGMENT per row segment (ScanCounter, scan_params.h): the lists' lengths, the sample's counts, the launches' chunk queues
     int64_t scan_stat[6] = {0, 0, 0, 0, 0, 0}; // most recent scan: counter width of the bulk launch, windows handed 4->8, ->16, row segments,
                                                // 1 = the bulk launch had the side table for period-4 max-mers beside its 4-bit counters,
                                                // 1 = the 4-bit bulk launch was the kernel compiled for kmin = 1

@@ -37,6 +37,7 @@
 // Measurements, the adaptive choice between 4 and 8 bits, and what was tried and dropped: DESIGN.md section 3.3.
 #pragma once
 #include "scan_kernel.h"
+#include "scan_forms.h"             // SCAN8_ROLE_*: the bits of ROLE, as the schedule and the launcher name them (no HIP there)
 #include "ring_rows.h"              // FRISK8_RING_COLS and the ring's address arithmetic (no HIP there: checked on a CPU as well)
 #include "win_step.h"               // a window's geometry, afresh and from its predecessor; stage 1's sequence addressing (no HIP either)
 
@@ -134,10 +135,10 @@ __device__ inline uint32_t wave_sum_u32(uint32_t x) {
            __builtin_amdgcn_readlane(int(x), 32) + __builtin_amdgcn_readlane(int(x), 48);
 }
 
-// ROLE names the launch (bit 0: the sample of the adaptive width, bit 1: no sliding, hence no ring): the code is otherwise the same, but a profiler's
-// per-kernel statistics then keep the 1/16 sample launches apart from the bulk launches.
-// ROLE bit 2 (KMIN1; the K = 8 4-bit bulk forms): the lowest order is the constant 1 - the default, and what nearly every scan runs at - instead of
-// the argument P.kmin, which such a launch never reads: see "KMIN1" in the kernel body.  Which launches take it is plan_scan_schedule's statement.
+// ROLE names the launch, as a set of the bits of scan_forms.h (SCAN8_ROLE_SAMPLE: the sample of the adaptive width, SCAN8_ROLE_NO_SLIDE: no sliding,
+// hence no ring): the code is otherwise the same, but a profiler's per-kernel statistics then keep the 1/16 sample launches apart from the bulk launches.
+// SCAN8_ROLE_KMIN1 (the K = 8 4-bit bulk forms): the lowest order is the constant 1 - the default, and what nearly every scan runs at - instead of
+// the argument P.kmin, which such a launch never reads: see "KMIN1" in the kernel body.  Which launches take it is plan_scan_schedule's statement; every (ROLE, SIDE, ...) that exists is a row of FRISK_SCAN8_FORMS.
 // NT threads, windows of at most NT*ITS bases, BITS per order-8 counter, LOGN: bins of the logarithm table, WPS: waves per SIMD the register allocation must allow (= workgroups per
 // CU * NT / 256).
 // SIDE (K = 8, 4-bit counters): the max-mers of period <= 4 - (x0 x1 x2 x3)(x0 x1 x2 x3): poly-A, (CA)n, (AAAT)n ..., the words that
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     constexpr int SHW = BITS == 8 ? 2 : 3;               // code >> SHW = dword of the table
     constexpr uint32_t PERM = (32 / BITS) - 1;           // code & PERM = field inside the dword
     static_assert(!SIDE || (KMAX == 8 && BITS == 4 && !DEBUG && NT == 256), "the side table exists for the 4-bit form at K = 8");
-    constexpr bool KMIN1 = (ROLE & 4) != 0;
-    static_assert(!KMIN1 || (KMAX == 8 && BITS == 4 && !DEBUG && !(ROLE & 1)), "the kmin = 1 skeleton exists for the 4-bit bulk forms at K = 8");
+    constexpr bool KMIN1 = (ROLE & SCAN8_ROLE_KMIN1) != 0;
+    static_assert(!KMIN1 || (KMAX == 8 && BITS == 4 && !DEBUG && !(ROLE & SCAN8_ROLE_SAMPLE)), "the kmin = 1 skeleton exists for the 4-bit bulk forms at K = 8");
     using L = Lds8<KMAX, BITS, LOGN, NT, SIDE>;
     // the order-K table is cleared whole when that takes no more stores per thread than a lane has positions (measured: 64 KiB
     // for windows of 2000 bases is the one case where every position clearing its own dword is cheaper)
@@ -308,9 +309,9 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
     // summation: same bits.  (The ring lives in the Infinity Cache: 80 KB per workgroup, more in all than L2 holds.)
     // (K = 8 with 4-bit counters only: the 8-bit form - two workgroups per CU - is bound by instruction issue at its occupancy,
     //  not by the gather: measured 8.80 ms without the ring, 9.06 with it, on the repeat-rich shape; at K = 6, 7 the table is 32 / 128 KB)
-    //  ROLE & 2: a launch whose windows do not slide (increment above half a window, or too few windows for chunks): every window
+    //  SCAN8_ROLE_NO_SLIDE: a launch whose windows do not slide (increment above half a window, or too few windows for chunks): every window
     //  would gather everything and park it for nobody - such launches take the instantiation without the ring.)
-    constexpr bool RING = KMAX == 8 && BITS == 4 && !(ROLE & 2);
+    constexpr bool RING = KMAX == 8 && BITS == 4 && !(ROLE & SCAN8_ROLE_NO_SLIDE);
     // (one buffer: a copy of the genome table first, the workgroups' slices behind it - so that "from the table" and "from the
     //  ring" are two 32-bit offsets from one base, and the scoring loop's load is one instruction either way)
     char* const ring = RING ? reinterpret_cast<char*>(P.ig_ring) : nullptr;
@@ -1080,7 +1081,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
 #pragma unroll
                             for (int m = 0; m < 4; ++m) put_pre(4 * q4 + j5[m], A5[m], W5[m], side_mine);
                             // (the sample of the adaptive width counts the windows that would have wrapped a 4-bit counter without the side table)
-                            if (SIDE && (ROLE & 1) && side_mine >= 16u) atomicOr(&misc[M8_PMASK], 0x80000000u);
+                            if (SIDE && (ROLE & SCAN8_ROLE_SAMPLE) && side_mine >= 16u) atomicOr(&misc[M8_PMASK], 0x80000000u);
                         } else {
                             auto lo = [](double x) -> uint32_t { return uint32_t(__double2loint(x)); };
                             auto hi = [](double x) -> uint32_t { return uint32_t(__double2hiint(x)); };
@@ -1133,7 +1134,7 @@ __global__ __launch_bounds__(NT, WPS) void scan8_kernel(const ScanParams P) {
             }
             // (the sample of the adaptive width: windows that reach the scoring loop, and those among them that a plain 4-bit table would
             //  have handed on - a side count of 16+)
-            if (SIDE && (ROLE & 1) && tid == 0) { atomicAdd(Pk->out_count + 3, 1u); if (pmask_raw >> 31) atomicAdd(Pk->out_count + 2, 1u); }
+            if (SIDE && (ROLE & SCAN8_ROLE_SAMPLE) && tid == 0) { atomicAdd(Pk->out_count + SCAN_CNT_SAMPLE_SCORED, 1u); if (pmask_raw >> 31) atomicAdd(Pk->out_count + SCAN_CNT_SAMPLE_WOULD, 1u); }
             load_orphans(placed);
 
             if (DEBUG && P.dbg_counts) {

@@ -1,6 +1,7 @@
-// scan8_launch.h - what the two units of the narrow-counter kernels share: the launch of one scan8_kernel instantiation, and the list of
-// the 4-bit forms, which scan8_launch4.hip and scan8_launch41.hip instantiate and scan8_launch.hip (launch_narrow, the 8-bit forms, K = 6 and 7) only calls.
-// The cut is by counter width and exists for build time alone: the two halves compile side by side.
+// scan8_launch.h - what the units of the narrow-counter kernels share: the launch of one scan8_kernel instantiation, and how a row of
+// the form table (FRISK_SCAN8_FORMS, scan_forms.h) is instantiated.  scan8_launch4.hip and scan8_launch41.hip instantiate the two
+// 4-bit sub-lists, scan8_launch.hip the 8-bit one; launch_scan8_form there calls them all.  The cut exists for build time alone: the
+// units compile side by side.
 #pragma once
 #include <algorithm>
 
@@ -17,16 +18,7 @@ FRISK_INTERNAL hipError_t launch_scan8(const ScanParams& P, int num_cu, int64_t 
     return hipGetLastError();
 }
 
-// K = 8 with 4-bit counters, as X(ITS, DEBUG, ROLE, SIDE): the sample (ROLE bit 0) and the side-table form, each sliding or not (ROLE
-// bit 1), then the plain form - debug, not sliding, sliding; FRISK_SCAN8_4BIT_KMIN1_FORMS: the bulk forms again with the lowest order
-// fixed at 1 (ROLE bit 2; scan8_launch41.hip)
-#define FRISK_SCAN8_4BIT_GENERIC_FORMS(X)                                                                                   \
-    X(8, false, 1, true) X(8, false, 3, true) X(20, false, 1, true) X(20, false, 3, true)                                  \
-    X(8, false, 0, true) X(8, false, 2, true) X(20, false, 0, true) X(20, false, 2, true)                                  \
-    X(8, true, 0, false) X(20, true, 0, false) X(8, false, 2, false) X(20, false, 2, false) X(8, false, 0, false) X(20, false, 0, false)
-#define FRISK_SCAN8_4BIT_KMIN1_FORMS(X)                                                                                     \
-    X(8, false, 4, true) X(8, false, 6, true) X(20, false, 4, true) X(20, false, 6, true)                                  \
-    X(8, false, 6, false) X(20, false, 6, false) X(8, false, 4, false) X(20, false, 4, false)
-#define FRISK_SCAN8_4BIT_FORMS(X) FRISK_SCAN8_4BIT_GENERIC_FORMS(X) FRISK_SCAN8_4BIT_KMIN1_FORMS(X)
-#define FRISK_SCAN8_4BIT(ITS_, DBG_, ROLE_, SIDE_) \
-    template hipError_t launch_scan8<8, 256, ITS_, 4, 64, 3, DBG_, ROLE_, SIDE_>(const ScanParams&, int, int64_t, hipStream_t);
+// a row of the table as an instantiation of its launch: 256 threads, the logarithm table of 64 bins
+#define FRISK_SCAN8_LAUNCH_OF(KMAX_, ITS_, BITS_, WPS_, DBG_, ROLE_, SIDE_) launch_scan8<KMAX_, 256, ITS_, BITS_, 64, WPS_, DBG_, ROLE_, SIDE_>
+#define FRISK_SCAN8_INSTANTIATE(KMAX_, ITS_, BITS_, WPS_, DBG_, ROLE_, SIDE_) \
+    template hipError_t FRISK_SCAN8_LAUNCH_OF(KMAX_, ITS_, BITS_, WPS_, DBG_, ROLE_, SIDE_)(const ScanParams&, int, int64_t, hipStream_t);

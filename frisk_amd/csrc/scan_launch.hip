@@ -1,4 +1,4 @@
-// scan_launch.hip - the launches of scan_kernel.h (16-bit counters, one or two workgroups per CU), of scan_big_kernel.h (long windows
+// scan_launch.hip - the launches of scan_kernel.h (16-bit counters, one or two workgroups per CU: launch_scan16_form), of scan_big_kernel.h (long windows
 // and orders above 8) and of the rows' scalar tail: the functions of scan_launch.h that frisk_abi.hip calls.  gfx950 (MI355X) only.
 #include <hip/hip_runtime.h>
 
@@ -39,29 +39,13 @@ hipError_t launch_scan(const ScanParams& P, int grid, size_t lds, hipStream_t st
 
 }  // namespace
 
-hipError_t launch_scan16(const ScanParams& PP, int kmax, int its, bool debug, size_t lds, int g, hipStream_t st) {
-    hipError_t le;
-#define FRISK_LAUNCH16(NT_, K8_, ITS_, DBG_) le = launch_scan<NT_, K8_, ITS_, DBG_>(PP, g, lds, st)
-    if (kmax == 8) {
-        if (debug) { if (its) FRISK_LAUNCH16(512, true, 16, true); else FRISK_LAUNCH16(1024, true, 0, true); }
-        else if (its == 4) FRISK_LAUNCH16(512, true, 4, false);
-        else if (its == 10) FRISK_LAUNCH16(512, true, 10, false);
-        else if (its == 16) FRISK_LAUNCH16(512, true, 16, false);
-        else FRISK_LAUNCH16(1024, true, 0, false);
-    } else {
-        if (debug) { if (its) FRISK_LAUNCH16(512, false, 16, true); else FRISK_LAUNCH16(1024, false, 0, true); }
-        else if (its == 4) FRISK_LAUNCH16(512, false, 4, false);
-        else if (its == 10) FRISK_LAUNCH16(512, false, 10, false);
-        else if (its == 16) FRISK_LAUNCH16(512, false, 16, false);
-        else FRISK_LAUNCH16(1024, false, 0, false);
-    }
-#undef FRISK_LAUNCH16
-    return le;
-}
-
-hipError_t launch_scan_two_wg(const ScanParams& P, int its, size_t lds, int grid, hipStream_t st) {
-    if (its == 8) return launch_scan<256, false, 8, false>(P, grid, lds, st);
-    return launch_scan<256, false, 20, false>(P, grid, lds, st);
+// the row of FRISK_SCAN16_FORMS (scan_forms.h) that equals the form, and no other
+hipError_t launch_scan16_form(const Scan16Form& form, const ScanParams& P, size_t lds, int grid, hipStream_t st) {
+#define FRISK_SCAN16_ROW(NT_, K8_, ITS_, DBG_) \
+    if (form == Scan16Form{NT_, K8_, ITS_, DBG_}) return launch_scan<NT_, K8_, ITS_, DBG_>(P, grid, lds, st);
+    FRISK_SCAN16_FORMS(FRISK_SCAN16_ROW)
+#undef FRISK_SCAN16_ROW
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_scan_big(const ScanParams& P, bool debug, int grid, uint32_t* big, int64_t stride, hipStream_t st) {

@@ -57,6 +57,20 @@ struct ScanParams {
                                   // the leaving and of the entering range per thread (= ceil(inc / threads)); 0: every window counted afresh
 };
 
+// The counter block of the narrow-counter path (frisk_ctx::d_ovf_count; zero when a scan's launches start): SCAN_CNT_TOTAL unsigned
+// ints, SCAN_CNT_SEGMENT of them per row segment.  Entries of a segment:
+enum ScanCounter {
+    SCAN_CNT_LIST1 = 0,             // length of list 1 (windows that wrapped a 4-bit counter) ...
+    SCAN_CNT_LIST2 = 1,             // ... and of list 2 (8-bit): ScanParams::in_count / out_count of the launches that walk / fill them
+    SCAN_CNT_SAMPLE_WOULD = 2,      // the sample: windows it scored that a plain 4-bit counter would have handed on ...
+    SCAN_CNT_SAMPLE_SCORED = 3,     // ... and windows it scored (both relative to the sample's out_count, which is the block's base)
+    SCAN_CNT_BULK_QUEUES = 8,       // [8, 16): the bulk launch's chunk queues, SCAN_CNT_BULK_QUEUE_N of them, one per XCD
+    SCAN_CNT_BULK_QUEUE_N = 8,
+    SCAN_CNT_QUEUE8 = 16,           // the chunk queue of the 8-bit launch over list 1
+    SCAN_CNT_SEGMENT = 32,          // stride from one row segment's counters to the next
+    SCAN_CNT_TOTAL = 64             // the block: two segments
+};
+
 #define ROW_KEPT 1u
 #define ROW_ZERO_WEIGHT 2u
 #define ROW_JUMPBACK 4u

@@ -1,7 +1,8 @@
 // scan_schedule.h - the launch schedule of one frisk_scan as a plain value: every decision between the call's arguments and its
-// launches (kernel form, chunk length, static deal or counters, sliding, ring slices, the sample and its stride, bulk width and side
-// table, where the tail segment is cut, the packed row block), computed by a pure function.  No HIP here: frisk_abi.hip fills a
-// ScanShape from the context and walks the ScanSchedule; tools/exp/san_host.cpp computes and checks schedules on a CPU.
+// launches (path, chunk length, static deal or counters, sliding, ring slices, the sample and its stride, bulk width and side
+// table, the kernel form of every launch - scan_forms.h -, where the tail segment is cut, the packed row block), computed by a pure
+// function.  No HIP here: frisk_abi.hip fills a ScanShape from the context and walks the ScanSchedule, handing each launch the form
+// named here; tools/exp/san_host.cpp, scan_dispatch_host.cpp and scan_forms_host.cpp compute and check schedules on a CPU.
 #pragma once
 
 #include <algorithm>
@@ -9,8 +10,8 @@
 #include <cstdint>
 
 #include "../../include/frisk_hip.h"      // FRISK_SCAN_*, FRISK_E_* (found without an include path of its own)
+#include "scan_forms.h"             // Scan8Form, Scan16Form, FRISK_K7_WPS
 
-#define FRISK_K7_WPS 4              // waves per SIMD (= 256-thread workgroups per CU) of the K = 6, 7 narrow-counter kernels
 #define FRISK_SIDE_SHARE 0.06       // 4-bit bulk takes the side-table form when the plain form would hand on more than this share of the sample
 #define FRISK_K8_WIDTH 0            // order-8 counters of the default K = 8 path (scan8_kernel.h): 0 = adaptive 4/8 bits, 4, 8, 16 = off
 
@@ -74,7 +75,7 @@ struct ScanSchedule {
     int32_t orphan_cap;
     // the narrow-counter path
     bool narrow8, small_w, can_slide, short_scan, dealt, sample, side;
-    bool kmin1_form;        // the 4-bit bulk launches take scan8_kernel's instantiations with the lowest order compiled in (ROLE bit 2)
+    bool kmin1_form;        // the 4-bit bulk launches take scan8_kernel's instantiations with the lowest order compiled in (SCAN8_ROLE_KMIN1)
     int64_t chunk8;         // consecutive windows per chunk
     int32_t slide_pp;       // ScanParams::slide_pp
     int64_t ring_slices;    // workgroup slices of the genome-value ring, 0 = no ring
@@ -88,6 +89,12 @@ struct ScanSchedule {
     int segments;
     bool packed_rows;
     RowBlock block;         // (with packed_rows)
+    // The kernel form of every launch (scan_forms.h), derived from the decisions above.  form16: scan_kernel.h's launch - the whole
+    // range off the narrow path, list 2 on it.  The narrow path: the sample, the bulk launch - or, with `sample`, the three that wait
+    // for the device's verdict: form_verdict[v - 1] runs where the verdict is v (1 plain 4-bit, 2 4-bit + side table, 3 8-bit) -
+    // and the 8-bit launch over list 1.  A launch that the schedule does not make has no form.
+    Scan16Form form16;
+    Scan8Form form_sample, form_bulk, form_verdict[3], form_handover;
 };
 
 inline int32_t scan_orphan_cap(int64_t plan_maxwin) { return int32_t(plan_maxwin / 8 + 2); }
@@ -143,6 +150,7 @@ inline ScanSchedule plan_scan_schedule(const ScanShape& s) {
         S.big_grid = int(std::min<int64_t>(n, s.num_cu));
         return S;
     }
+    S.form16 = scan16_form_of(s.kmax, S.its, debug, false);
     if (!narrow) {
         if (!k8 && !debug && !s.one_wg && s.plan_maxwin <= 5120 && S.lds_total <= 80 * 1024) {
             // K <= 7: the tables of a window take < 60 KB, so TWO independent 256-thread workgroups fit a CU.  The two waves of
@@ -154,6 +162,7 @@ inline ScanSchedule plan_scan_schedule(const ScanShape& s) {
             S.grid = grid;
             S.chunk = int32_t(std::max<int64_t>(1, std::min<int64_t>(n / (int64_t(grid) * 8), 8)));
             S.its = s.plan_maxwin <= 2048 ? 8 : 20;
+            S.form16 = scan16_form_of(s.kmax, S.its, debug, true);
         } else {
             S.path = SCAN_PATH_16BIT;
         }
@@ -224,9 +233,32 @@ inline ScanSchedule plan_scan_schedule(const ScanShape& s) {
     S.bulk = bulk; S.side = side;
     // The 4-bit bulk forms exist a second time, compiled for the lowest order 1 (scan8_kernel.h, KMIN1): K = 8 and kmin = 1 - the
     // default, and the reference's - take them, whatever width the bulk turns out to have (a launch of another width follows its own
-    // rule: launch_narrow); the debug instantiations, K = 6 and 7 and every other kmin keep the kernel that reads kmin as an argument,
+    // rule: scan8_form_of); the debug instantiations, K = 6 and 7 and every other kmin keep the kernel that reads kmin as an argument,
     // and so does a scan that asks for it (FRISK_SCAN_GENERIC: the two are compared bit for bit).
     S.kmin1_form = narrow8 && s.kmin == 1 && !debug && !(s.flags & FRISK_SCAN_GENERIC);
+    // the forms of the launches: a range launch slides where the schedule does, a hand-over launch walks a list and never slides
+    Scan8Ask ask = Scan8Ask();
+    ask.kmax = s.kmax; ask.kmin = s.kmin; ask.small_w = S.small_w; ask.kmin1_form = S.kmin1_form; ask.slides = S.slide_pp > 0;
+    if (S.sample) {         // (no debug dump: the sample is not taken with one)
+        Scan8Ask a = ask;
+        a.bits = 4; a.sample = true;
+        S.form_sample = scan8_form_of(a);
+        a.sample = false;
+        S.form_verdict[0] = scan8_form_of(a);
+        a.side = true;
+        S.form_verdict[1] = scan8_form_of(a);
+        a.bits = 8; a.side = false;
+        S.form_verdict[2] = scan8_form_of(a);
+    } else {
+        Scan8Ask a = ask;
+        a.bits = bulk; a.debug = debug; a.side = side;
+        S.form_bulk = scan8_form_of(a);
+    }
+    if (S.sample || bulk == 4) {
+        Scan8Ask a = ask;
+        a.bits = 8; a.debug = debug; a.listed = true;
+        S.form_handover = scan8_form_of(a);
+    }
     // The last sixteenth of a long scan goes to a second stream and starts when the kernels of the first fifteen are done:
     // it runs while their rows travel to the host (16 MB per 410 k windows: 0.36 ms that used to follow the scan).  The
     // cut is a multiple of 16 chunks: chunk numbering and the sample's stride stay aligned across it.

@@ -1,4 +1,4 @@
-// (CPU) which scans take the K = 8 4-bit bulk kernels compiled for the lowest order 1 (scan8_kernel.h, ROLE bit 2): plan_scan_schedule's
+// (CPU) which scans take the K = 8 4-bit bulk kernels compiled for the lowest order 1 (scan8_kernel.h, SCAN8_ROLE_KMIN1): plan_scan_schedule's
 // statement ScanSchedule::kmin1_form over a sweep of shapes - lowest order 1..5, highest order 6..8, both counter widths and the
 // adaptive choice (flags, the batch's hint, a scan long enough to sample), FRISK_SCAN_GENERIC on and off, the debug dump on and off,
 // windows of both classes and one beyond the narrow-counter kernels, sliding and not.  The form is named exactly where K = 8, kmin = 1,
